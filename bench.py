@@ -11,6 +11,11 @@ scaling: the total work per step is one frame at every N).
 
 value = W*H*spp*steps / max-over-ranks wall time of the timed region (scene resident on the
 GPU, output in HBM; no host transfers inside).
+
+A plain run sets up, warms up, times --steps frames and prints the line. --full adds, after the timed
+steps, the measurements with runs of their own (cpu_baseline, parity, the VALU roofline's work count,
+end_to_end_ms_per_frame); --dump-outputs DIR writes the last timed frame to DIR/image.npy. Every step
+renders the same frame with the same seed, so the image is the same from run to run.
 """
 import argparse
 import json
@@ -235,11 +240,21 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the CPU "
+                         "oracle baseline and the GPU-vs-oracle parity of its share, the VALU roofline (work "
+                         "count in a child process) and the end-to-end frame time. A run without it sets up, "
+                         "warms up, times the steps and prints the line with those fields null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the image the last timed step rendered (the ppmOut "
+                         "float image a caller of dt_render receives; at N > 1 rank 0's gathered frame) to "
+                         "DIR/image.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
     ap.add_argument("--cpu-frac", type=int, default=8, help="CPU baseline renders 1/N of the tiles")
     ap.add_argument("--cpu-all-cores", action="store_true",
                     help="also time the CPU baseline on every core of the affinity mask (not the GPU box's default)")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the VALU work count (child process)")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the VALU work count (child process)")
     ap.add_argument("--inflight", type=int, default=None, choices=(1, 2),
                     help="frames in flight per rank (2, the default: alternating streams and scene objects, "
                          "DESIGN.md §7)")
@@ -355,6 +370,14 @@ def main():
         elapsed = float(t.item())
     lib_stats = dt.collect_stats(scene, sh)
 
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step computed: the frame in the buffer step K-1 rendered into (N = 1),
+        # or the image rank 0 assembled from the gathered slabs
+        import numpy as np
+        last = pipe.image if distributed else images[(args.steps - 1) % len(images)]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "image.npy"), last.cpu().numpy().reshape(H, W, 3))
+
     if rank == 0:
         samples = W * H * spp * args.steps
         value = samples / elapsed / 1e6
@@ -374,12 +397,13 @@ def main():
                                   % pmc.get("tag")) if traffic else None,
                "alg_bytes_per_launch": int(alg_bytes)}
         cpu, parity, ref_work, ref_samples = None, None, None, 0
-        e2e = end_to_end_ms(dt, args.config, dev) if world == 1 else None
-        if world == 1 and not args.no_cpu_baseline:
+        # everything below that takes a run of its own is --full's: a plain run has its figure already
+        e2e = end_to_end_ms(dt, args.config, dev) if args.full and world == 1 else None
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu, parity, ref_work, ref_samples = cpu_baseline(dt, args.config, args.cpu_frac, scene, dev,
                                                               args.cpu_all_cores)
         roof = None
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             # at N > 1 the work is counted on rank 0's share of the split (the frame this GPU renders);
             # the committed PMC profile is of a whole-frame launch, so counter_fp64 is N = 1 only
             roof = valu_roofline(args.config, kernel_ms, W * H * spp, ref_work, ref_samples,
@@ -388,7 +412,7 @@ def main():
         if roof is not None:
             roof["kernel"] = trace_kernel_name(spp, g.use_model)
             roof["kernel_ms_basis"] = kernel_basis
-        if roof is None:   # no diagnostic library: the HBM line alone
+        if roof is None:   # a plain run, or no diagnostic library: the HBM line alone
             roof = dict(hbm, kernel=trace_kernel_name(spp, g.use_model), kernel_ms=round(kernel_ms, 3),
                         kernel_ms_basis=kernel_basis)
         else:

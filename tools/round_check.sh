@@ -6,10 +6,10 @@ timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 echo tests ok
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
 echo smoke ok
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err
 echo bench ok
-timeout -k 10 200 python bench.py --config c2 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_c2.log 2>&1
-timeout -k 10 200 python bench.py --config c4 --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_c4.log 2>&1
+timeout -k 10 200 python bench.py --full --config c2 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_c2.log 2>&1
+timeout -k 10 200 python bench.py --full --config c4 --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_c4.log 2>&1
 echo c2 c4 ok
 if [ -z "$NO_C5" ]; then timeout -k 10 300 python tools/animate.py --frames 0:300:30 --per-frame > $O/c5_animate.log 2>&1; echo c5 ok; fi
 cd /tmp; export TMPDIR=/tmp
