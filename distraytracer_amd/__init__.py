@@ -20,7 +20,9 @@ from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT
 __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_scene", "Scene",
            "render", "render_sky", "renderImage", "renderImageCloud", "write_ppm", "DATA_DIR",
            "DT_OUT_IMAGE", "DT_OUT_SLAB", "slab_floats", "slab_floats_max", "unpack_slabs", "tiles", "check", "lib",
-           "accel_info", "DT_KERNEL_AUTO", "DT_KERNEL_PRODUCT", "DT_KERNEL_DONATE"]
+           "accel_info", "DT_KERNEL_AUTO", "DT_KERNEL_PRODUCT", "DT_KERNEL_DONATE",
+           "accum_doubles", "window_check", "render_window", "render_window_async", "resolve", "Progressive",
+           "mean_abs_change"]
 
 
 def globals_default():
@@ -216,6 +218,172 @@ def unpack_slabs(g, tile, world, slabs, image, stream=None):
                               ctypes.c_void_p(stream) if stream else None), "dt_unpack_slabs")
 
 
+def _spp(g):
+    """sampled_n = int(sqrt(antialias_samples))^2 (cpp:1046,1061; host_flatten.cpp fill_params)"""
+    import math
+    n = int(math.sqrt(float(g.antialias_samples)))
+    return n * n
+
+
+def accum_doubles(g, tile=None):
+    """Length of the f64 accumulator of window renders for (g, tile): one double per float of the
+    output, in its layout (dt_accum_doubles)."""
+    n = int(lib.dt_accum_doubles(ctypes.byref(g), ctypes.byref(tile) if tile else None))
+    if n < 0:
+        raise DTError("dt_accum_doubles: invalid globals or tiles")
+    return n
+
+
+def window_check(g, begin, end):
+    """Raise DTError unless [begin, end) is a sample window (include/dt.h dt_window_check)."""
+    check(lib.dt_window_check(ctypes.byref(g), int(begin), int(end)), "dt_window_check")
+
+
+def _accum_ptr(accum, g, tile):
+    if not hasattr(accum, "data_ptr") or str(accum.dtype) != "torch.float64" or not accum.is_cuda \
+            or not accum.is_contiguous():
+        raise DTError("the accumulator must be a contiguous CUDA torch.float64 tensor")
+    if accum.numel() < accum_doubles(g, tile):
+        raise DTError("the accumulator holds %d doubles, (g, tile) need %d" % (accum.numel(), accum_doubles(g, tile)))
+    return ctypes.c_void_p(accum.data_ptr())
+
+
+def render_window(scene, g, frame, accum, begin, end, tile=None, stream=None):
+    """Add the samples [begin, end) of every owned pixel onto `accum`, in sample order
+    (dt_render_window). The caller orders the windows: ascending, gap-free, from 0 on a zeroed
+    accumulator reproduces dt_render's sums bit for bit. Returns the window's Stats."""
+    st = Stats()
+    check(lib.dt_render_window(scene.handle, ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None,
+                               int(begin), int(end), _accum_ptr(accum, g, tile),
+                               ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)), "dt_render_window")
+    return st
+
+
+def render_window_async(scene, g, frame, accum, begin, end, tile=None, stream=None):
+    """render_window, enqueue only (collect_stats then reports the window)."""
+    check(lib.dt_render_window_async(scene.handle, ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None,
+                                     int(begin), int(end), _accum_ptr(accum, g, tile),
+                                     ctypes.c_void_p(stream) if stream else None), "dt_render_window_async")
+
+
+def resolve(g, accum, n_samples, out, tile=None, stream=None):
+    """out[i] = clamp01(float32(accum[i] / n_samples)) * 255 (dt_resolve): torch CUDA tensors (a
+    kernel) or host numpy / torch arrays (a loop), both on the same side. Returns the number of
+    pixels with a NaN channel."""
+    ap, adev = _ptr_typed(accum, "torch.float64", "float64")
+    op, odev = _ptr(out)
+    if adev != odev:
+        raise DTError("accum and out must be on the same side")
+    need = accum_doubles(g, tile)
+    for a in (accum, out):
+        if (a.numel() if hasattr(a, "numel") else a.size) < need:
+            raise DTError("resolve: (g, tile) need %d elements" % need)
+    nan = ctypes.c_uint64(0)
+    check(lib.dt_resolve(ctypes.byref(g), ctypes.byref(tile) if tile else None, ap, int(n_samples), op, adev,
+                         ctypes.c_void_p(stream) if stream else None, ctypes.byref(nan)), "dt_resolve")
+    return nan.value
+
+
+class Progressive:
+    """A frame rendered in sample windows: a zeroed f64 accumulator on the device (24 B per pixel of
+    the output layout) and the count of samples added so far.
+
+        p = Progressive(scene, g, frame)
+        while not p.done:
+            p.step()              # the next 64-sample chunk of every pixel
+            preview = p.image()   # the mean of the samples so far, as dt_render would store it
+
+    After the last step image() is dt_render's output bit for bit. state() / restore() carry a frame
+    across processes."""
+
+    _STATE_INTS = ("samples_done", "frame", "seed", "xRes", "yRes", "spp")
+    _TILE_FIELDS = ("x0", "y0", "x1", "y1", "tile_w", "tile_h", "rank", "world", "layout")
+
+    def __init__(self, scene, g, frame, tile=None):
+        import torch
+        self.scene, self.g, self.frame = scene, g.copy(), int(frame)
+        self.tile = tile if tile is not None else tiles()
+        self.spp = _spp(g)
+        self.samples_done = 0
+        self.accum = torch.zeros(max(accum_doubles(self.g, self.tile), 1), dtype=torch.float64, device="cuda")
+
+    @property
+    def done(self):
+        return self.samples_done >= self.spp
+
+    def step(self, n_chunks=1):
+        """Render the next window: n_chunks 64-sample chunks (the rest of the frame if fewer are
+        left; with spp < 64 the one window [0, spp)). Returns the window's Stats."""
+        if self.done:
+            raise DTError("Progressive.step: all %d samples are rendered" % self.spp)
+        if n_chunks < 1:
+            raise DTError("Progressive.step: n_chunks < 1")
+        begin = self.samples_done
+        end = min(begin + 64 * int(n_chunks), self.spp)
+        st = render_window(self.scene, self.g, self.frame, self.accum, begin, end, self.tile)
+        self.samples_done = end
+        return st
+
+    def image(self, out=None):
+        """The resolved preview: the mean of the samples rendered so far (a CUDA float32 tensor in
+        the output layout; `out` to reuse one)."""
+        import torch
+        if self.samples_done < 1:
+            raise DTError("Progressive.image: no window rendered yet")
+        if out is None:
+            out = torch.empty(self.accum.numel(), dtype=torch.float32, device="cuda")
+        self.nan_pixels = resolve(self.g, self.accum, self.samples_done, out, self.tile)
+        return out
+
+    def run(self, until=None, n_chunks=1):
+        """step() until done, or until until(self) returns true after a step."""
+        while not self.done:
+            self.step(n_chunks)
+            if until is not None and until(self):
+                break
+        return self
+
+    def state(self):
+        """Host copy of the frame so far: numpy f64 accumulator and ints (samples done, frame, seed,
+        xRes, yRes, spp, the tile fields)."""
+        d = {"accum": self.accum.cpu().numpy().copy(), "samples_done": int(self.samples_done),
+             "frame": self.frame, "seed": int(self.g.seed), "xRes": int(self.g.xRes), "yRes": int(self.g.yRes),
+             "spp": int(self.spp)}
+        for f in self._TILE_FIELDS:
+            d["tile_" + f] = int(getattr(self.tile, f))
+        return d
+
+    @classmethod
+    def restore(cls, scene, g, state):
+        """Continue the frame of state() on `scene` (a scene of the same description) with globals g:
+        seed, resolution, spp and the tile must be the state's."""
+        import numpy as np
+        import torch
+        tile = tiles(**{f: int(state["tile_" + f]) for f in cls._TILE_FIELDS})
+        p = cls.__new__(cls)
+        p.scene, p.g, p.frame, p.tile = scene, g.copy(), int(state["frame"]), tile
+        p.spp = _spp(g)
+        for k, have in (("seed", g.seed), ("xRes", g.xRes), ("yRes", g.yRes), ("spp", p.spp)):
+            if int(state[k]) != int(have):
+                raise DTError("Progressive.restore: %s is %d, the state was rendered with %d" % (k, have, state[k]))
+        done = int(state["samples_done"])
+        if done < 0 or done > p.spp or (done < p.spp and done % 64):
+            raise DTError("Progressive.restore: samples_done %d is no window boundary" % done)
+        acc = np.ascontiguousarray(state["accum"], dtype=np.float64).reshape(-1)
+        if acc.size != max(accum_doubles(p.g, tile), 1):
+            raise DTError("Progressive.restore: the accumulator holds %d doubles, (g, tile) need %d"
+                          % (acc.size, accum_doubles(p.g, tile)))
+        p.samples_done = done
+        p.accum = torch.from_numpy(acc).to("cuda")
+        return p
+
+
+def mean_abs_change(a, b):
+    """Mean absolute difference of two resolved images (torch): an early-stop measure for
+    Progressive.run(until=...)."""
+    return float((a - b).abs().mean())
+
+
 def write_ppm(filename, g, values):
     import numpy as np
     v = np.ascontiguousarray(values, dtype=np.float32)
@@ -228,15 +396,24 @@ def write_png(filename, g, values):
     check(lib.dt_write_png(filename.encode(), g.xRes, g.yRes, ctypes.c_void_p(v.ctypes.data)), "dt_write_png")
 
 
-def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None):
+def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progressive=None):
     """render_final_project.cpp:965: build (sceneBuilder names a scene.h builder), render the
-    frame on the current GPU, write the PPM. Returns (image, stats)."""
+    frame on the current GPU, write the PPM. Returns (image, stats). progressive=callback renders in
+    one-chunk sample windows (Progressive) and calls callback(image, samples_done) with the resolved
+    preview (numpy) after every window; the image returned is the same bits, stats the last window's."""
     import numpy as np
     g = g if g is not None else globals_default()
     built = build_scene(sceneBuilder, frame if builder_frame is None else builder_frame, g)
     scene = Scene(built, g)
     img = np.zeros(3 * g.xRes * g.yRes, dtype=np.float32)
-    st = render(scene, g, frame, img)
+    if progressive is not None:
+        p = Progressive(scene, g, frame)
+        while not p.done:
+            st = p.step()
+            img = p.image().cpu().numpy()
+            progressive(img, p.samples_done)
+    else:
+        st = render(scene, g, frame, img)
     if filename:
         (write_png if filename.endswith(".png") else write_ppm)(filename, g, img)
     scene.close()

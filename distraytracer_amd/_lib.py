@@ -120,7 +120,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_render", "dt_render_async", "dt_collect_stats", "dt_debug_counters", "dt_debug_item_costs", "dt_render_sky",
            "dt_unpack_slabs", "dt_build_scene", "dt_scene_desc_free", "dt_write_ppm", "dt_write_png",
            "dt_mocap_bone_table", "dt_debug_normalize", "dt_intersect_primary",
-           "dt_debug_load_obj"]
+           "dt_debug_load_obj",
+           "dt_accum_doubles", "dt_window_check", "dt_render_window", "dt_render_window_async", "dt_resolve"]
 
 
 class DTError(RuntimeError):
@@ -173,6 +174,14 @@ def _load():
         "dt_render_async": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), ctypes.c_void_p,
                                       ctypes.c_void_p]),
         "dt_collect_stats": (c_int32, [ctypes.c_void_p, ctypes.c_void_p, P(Stats)]),
+        "dt_accum_doubles": (c_int64, [P(Globals), P(Tiles)]),
+        "dt_window_check": (c_int32, [P(Globals), c_int32, c_int32]),
+        "dt_render_window": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, c_int32,
+                                       ctypes.c_void_p, ctypes.c_void_p, P(Stats)]),
+        "dt_render_window_async": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, c_int32,
+                                             ctypes.c_void_p, ctypes.c_void_p]),
+        "dt_resolve": (c_int32, [P(Globals), P(Tiles), ctypes.c_void_p, c_int32, ctypes.c_void_p, c_int32,
+                                 ctypes.c_void_p, P(c_uint64)]),
         "dt_debug_counters": (c_int32, [ctypes.c_void_p, P(c_uint64), c_int32]),
         "dt_debug_item_costs": (c_int64, [ctypes.c_void_p, P(ctypes.c_uint32), c_int64]),
         "dt_debug_normalize": (c_int32, [P(c_double), P(c_double), c_int64]),

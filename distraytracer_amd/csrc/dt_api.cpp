@@ -46,7 +46,24 @@ DT_TRACE_BUILD(dt_trace_kernel_w5_blur)
 DT_TRACE_BUILD(dt_trace_kernel_w5_sky)
 DT_TRACE_BUILD(dt_trace_kernel_dn)
 DT_TRACE_BUILD(dt_trace_kernel_rpc)
+// ... and each of them with the window mode of the item loop (dt_kernels.hip DT_WINDOW, Makefile WIN_OBJ)
+DT_TRACE_BUILD(dt_trace_kernel_win)
+DT_TRACE_BUILD(dt_trace_kernel_mesh_win)
+DT_TRACE_BUILD(dt_trace_kernel_full_win)
+DT_TRACE_BUILD(dt_trace_kernel_tunnel_win)
+DT_TRACE_BUILD(dt_trace_kernel_blur_win)
+DT_TRACE_BUILD(dt_trace_kernel_sky_win)
+DT_TRACE_BUILD(dt_trace_kernel_w5_win)
+DT_TRACE_BUILD(dt_trace_kernel_w5_mesh_win)
+DT_TRACE_BUILD(dt_trace_kernel_w5_full_win)
+DT_TRACE_BUILD(dt_trace_kernel_w5_tunnel_win)
+DT_TRACE_BUILD(dt_trace_kernel_w5_blur_win)
+DT_TRACE_BUILD(dt_trace_kernel_w5_sky_win)
+DT_TRACE_BUILD(dt_trace_kernel_dn_win)
+DT_TRACE_BUILD(dt_trace_kernel_rpc_win)
 #undef DT_TRACE_BUILD
+extern "C" hipError_t dt_launch_resolve(const double* accum, float* out, int64_t n_px, int n_samples,
+                                        unsigned long long* nan_px, hipStream_t stream);
 extern "C" hipError_t dt_launch_isect(const void* dev_launch, int64_t first, int64_t n, int32_t* hit_shape, float* hit_t,
                                       int grid, hipStream_t stream);
 extern "C" const void* dt_isect_kernel_ptr(void);
@@ -85,7 +102,7 @@ struct HScene {
   int32_t n_clear0, n_clear1;
   double* chunk_cols;           // chunk items: per-pixel sample colours (dt_kernels.hip)
   uint32_t* item_cost;          // diagnostic builds: per-item durations (dt_debug_item_costs)
-  void* pad_;
+  double* accum;                // window launches: the caller's accumulator (dt_render_window)
 };
 
 // DT_N_STAMPS (dt_scene_dev.h): diagnostic counter slots of -DDT_STAMPS builds (dt_debug_counters):
@@ -235,6 +252,7 @@ struct dt_scene {
   void* d_pl_cells = nullptr;
   void* d_pl_list = nullptr;
   dtd::DParams last;
+  int last_px_samples = 0;   // samples per pixel of the last launch: spp, or a window's end - begin
 };
 
 extern "C" {
@@ -770,7 +788,30 @@ static Build g_builds[2][6] = {
     {DT_B(dt_trace_kernel_w5), DT_B(dt_trace_kernel_w5_mesh), DT_B(dt_trace_kernel_w5_full),
      DT_B(dt_trace_kernel_w5_tunnel), DT_B(dt_trace_kernel_w5_blur), DT_B(dt_trace_kernel_w5_sky)}};
 static Build g_dn_build = DT_B(dt_trace_kernel_dn), g_rpc_build = DT_B(dt_trace_kernel_rpc);
+// the same table of the window builds (dt_kernels.hip DT_WINDOW: trait bit 2), for dt_render_window
+static Build g_win_builds[2][6] = {
+    {DT_B(dt_trace_kernel_win), DT_B(dt_trace_kernel_mesh_win), DT_B(dt_trace_kernel_full_win),
+     DT_B(dt_trace_kernel_tunnel_win), DT_B(dt_trace_kernel_blur_win), DT_B(dt_trace_kernel_sky_win)},
+    {DT_B(dt_trace_kernel_w5_win), DT_B(dt_trace_kernel_w5_mesh_win), DT_B(dt_trace_kernel_w5_full_win),
+     DT_B(dt_trace_kernel_w5_tunnel_win), DT_B(dt_trace_kernel_w5_blur_win), DT_B(dt_trace_kernel_w5_sky_win)}};
+static Build g_dn_win_build = DT_B(dt_trace_kernel_dn_win), g_rpc_win_build = DT_B(dt_trace_kernel_rpc_win);
 #undef DT_B
+
+// the window build of the product build b: the same flags with the window mode of the item loop
+static Build& window_build_for(const Build& b)
+{
+  for (int w = 0; w < 2; ++w)
+    for (int v = 0; v < 6; ++v)
+      if (&b == &g_builds[w][v]) return g_win_builds[w][v];
+  return &b == &g_dn_build ? g_dn_win_build : g_rpc_win_build;
+}
+
+// A window launch (dt_render_window): the chunks [chunk_lo, chunk_hi) of every pixel item onto accum
+struct Window {
+  int32_t chunk_lo, chunk_hi;
+  int32_t samples;   // end - begin (dt_stats.samples per pixel)
+  double* accum;
+};
 
 // the feature mask a build was compiled for (its traits' bits 8..23: dt_kernels.hip DT_FEATURES)
 static unsigned build_features(const Build& b) { return ((unsigned)b.traits() >> 8) & 0xFFFFu; }
@@ -838,8 +879,9 @@ int dt_trace_build(const dt_scene_desc* desc, const dt_globals* g, int32_t frame
   return DT_OK;
 }
 
+// win: a window launch (dt_render_window) onto win->accum, out_dev unused; null: a whole render
 static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>& zs, float* out_dev,
-                          hipStream_t st)
+                          hipStream_t st, const Window* win = nullptr)
 {
   if (int rc = scene_upload(sc)) return rc;
   if (int rc = update_primary_lists(sc, P, true)) return rc;
@@ -868,9 +910,13 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
   hs.clear1 = nullptr;
   hs.n_clear1 = 0;
   const int kernel_choice = sc->kernel;
-  Build& kb = choose_build(sc->features, sc->no_cull, kernel_choice, P);
-  const bool donate = &kb == &g_dn_build;
-  Build& kb2 = sky_build_for(kb);
+  Build& kb_product = choose_build(sc->features, sc->no_cull, kernel_choice, P);
+  const bool donate = &kb_product == &g_dn_build;
+  // a window launch takes the window builds of the same choice (and of its *_sky build)
+  Build& kb = win ? window_build_for(kb_product) : kb_product;
+  Build& kb2 = win ? window_build_for(sky_build_for(kb_product)) : sky_build_for(kb_product);
+  if (win && (!(kb.traits() & 4) || !(kb2.traits() & 4)))
+    return fail(DT_E_INVALID, "the trace-kernel build has no window mode");
   // the build must handle every feature of the scene: its DT_FEATURES compile the others out to
   // __builtin_unreachable() (tests/test_host.py checks every builder scene; this guards the rest)
   if (sc->features & ~build_features(kb))
@@ -891,7 +937,13 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
   if (!(kb.traits() & 2) || !(kb2.traits() & 2) || P.chunks < 2 || P.chunks > 255 || chunk_items < 0 ||
       chunk_items > 2 || (double)P.n_items * P.chunks >= 4294967296.0)
     chunk_items = 0;
+  // a window launch runs per-pixel items whatever DT_CHUNK_ITEMS says: the window's chunks in turn
+  // on one wave, the pixel's sums going on from the accumulator (dt_kernels.hip DT_WINDOW)
+  if (win) chunk_items = 0;
   P.chunk_items = chunk_items;
+  P.chunk_lo = win ? win->chunk_lo : 0;
+  P.chunk_hi = win ? win->chunk_hi : 0;
+  hs.accum = win ? win->accum : nullptr;
   if (chunk_items) {
     const int64_t n_cols = P.n_items * (int64_t)P.spp * 3;
     if (n_cols > sc->chunk_cols_cap) {
@@ -976,7 +1028,9 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
   const int64_t n_px = PL.n_items * PL.ppw;
   PL.sky_defer = 0;
   hs.sky_miss = nullptr;
-  if (defer_on && PL.spp == 1 && PL.perlin_cloud && n_px > 0) {
+  // (not for a window launch: dt_sky_miss_kernel stores pixels, so the trace or sky-item launch
+  // computes the sky and the accumulator takes it like any sample colour)
+  if (defer_on && !win && PL.spp == 1 && PL.perlin_cloud && n_px > 0) {
     if (n_px > sc->sky_miss_cap) {
       HIPCHK(hipStreamSynchronize(st));
       if (sc->d_sky_miss) (void)hipFree(sc->d_sky_miss);
@@ -1102,6 +1156,7 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
   sc->timed = true;
   sc->launched = true;
   sc->last = P;
+  sc->last_px_samples = win ? win->samples : P.spp;
   return DT_OK;
 }
 
@@ -1147,7 +1202,7 @@ int dt_collect_stats(const dt_scene* sc_c, void* stream, dt_stats* stats)
     }
   }
   stats->pixels = px;
-  stats->samples = (uint64_t)px * P.spp;
+  stats->samples = (uint64_t)px * sc->last_px_samples;   // (a window launch: the window's samples)
   stats->rays = h[ST_RAYS];
   stats->shadow_rays = h[ST_SHADOW];
   stats->sky_pixels = h[ST_SKY];
@@ -1215,6 +1270,113 @@ int dt_render(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt
   if (rc == DT_OK) rc = dt_collect_stats(sc, stream, stats);
   if (!out_on_device) (void)hipFree(dout);
   return rc;
+}
+
+// ---- progressive rendering: sample windows into a resident accumulator ---------------------------
+// No reference counterpart: the reference renders a frame whole (render_final_project.cpp:1031-1218).
+// Its per-pixel sum is a left-to-right chain of f64 adds in sample order (cpp:1212), and a sample's
+// colour depends only on (seed, frame, pixel, sample index), so windows applied in ascending order
+// to an f64 accumulator reproduce the chain, and dt_resolve its / sampled_n and clamp*255 (1213-1217).
+int64_t dt_accum_doubles(const dt_globals* g, const dt_tiles* tiles)
+{
+  dtd::DParams P;
+  std::string err;
+  if (!g || fill_sky_params(*g, 0.0f, tiles, P, err)) return -1;
+  return P.layout == DT_OUT_SLAB ? P.n_owned_tiles * P.tw * P.th * 3 : (int64_t)3 * g->xRes * g->yRes;
+}
+
+int dt_window_check(const dt_globals* g, int32_t begin, int32_t end)
+{
+  if (!g) return fail(DT_E_INVALID, "null argument");
+  if (g->antialias_samples < 1) return fail(DT_E_INVALID, "invalid globals");
+  const int n = (int)sqrt((double)g->antialias_samples);
+  const int spp = n * n;   // sampled_n (cpp:1046,1061; fill_params)
+  char buf[160];
+  if (!(0 <= begin && begin < end && end <= spp)) {
+    snprintf(buf, sizeof buf, "window [%d,%d): need 0 <= begin < end <= spp (%d)", begin, end, spp);
+    return fail(DT_E_INVALID, buf);
+  }
+  if (spp < 64) {
+    if (begin != 0 || end != spp) {
+      snprintf(buf, sizeof buf, "window [%d,%d): with spp < 64 the only window is [0,%d)", begin, end, spp);
+      return fail(DT_E_INVALID, buf);
+    }
+    return DT_OK;
+  }
+  if (begin % 64 != 0) {
+    snprintf(buf, sizeof buf, "window [%d,%d): begin must be a multiple of 64 (whole chunks)", begin, end);
+    return fail(DT_E_INVALID, buf);
+  }
+  if (end % 64 != 0 && end != spp) {
+    snprintf(buf, sizeof buf, "window [%d,%d): end must be a multiple of 64 or spp (%d)", begin, end, spp);
+    return fail(DT_E_INVALID, buf);
+  }
+  return DT_OK;
+}
+
+int dt_render_window_async(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                           int32_t begin, int32_t end, double* accum_device, void* stream)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  if (!sc) return fail(DT_E_INVALID, "null scene");
+  if (!g || !accum_device) return fail(DT_E_INVALID, "null argument");
+  if (int rc = dt_window_check(g, begin, end)) return rc;
+  dtd::DParams P;
+  std::vector<float> zs;
+  int rc = prepare_render(sc, g, frame, tiles, P, zs);
+  if (rc) return rc;
+  Window w;
+  w.chunk_lo = begin / 64;
+  w.chunk_hi = (end + 63) / 64;
+  w.samples = end - begin;
+  w.accum = accum_device;
+  return enqueue_render(sc, P, zs, nullptr, (hipStream_t)stream, &w);
+}
+
+int dt_render_window(const dt_scene* sc, const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t begin,
+                     int32_t end, double* accum_device, void* stream, dt_stats* stats)
+{
+  int rc = dt_render_window_async(sc, g, frame, tiles, begin, end, accum_device, stream);
+  if (rc == DT_OK) rc = dt_collect_stats(sc, stream, stats);
+  return rc;
+}
+
+int dt_resolve(const dt_globals* g, const dt_tiles* tiles, const double* accum, int32_t n_samples, float* out,
+               int32_t on_device, void* stream, uint64_t* nan_pixels)
+{
+  if (!g || !accum || !out) return fail(DT_E_INVALID, "null argument");
+  if (n_samples < 1) return fail(DT_E_INVALID, "dt_resolve: n_samples < 1");
+  const int64_t n = dt_accum_doubles(g, tiles);
+  if (n < 0) return fail(DT_E_INVALID, "invalid globals or tiles");
+  const int64_t n_px = n / 3;
+  if (!on_device) {
+    uint64_t n_nan = 0;
+    for (int64_t q = 0; q < n_px; ++q) {
+      // divs then store_pixel (dt_kernels.hip), per channel
+      const double c[3] = {accum[3 * q] / (double)n_samples, accum[3 * q + 1] / (double)n_samples,
+                           accum[3 * q + 2] / (double)n_samples};
+      for (int k = 0; k < 3; ++k) out[3 * q + k] = dtm::clampf01((float)c[k]) * 255.0f;
+      if (std::isnan(c[0]) || std::isnan(c[1]) || std::isnan(c[2])) ++n_nan;
+    }
+    if (nan_pixels) *nan_pixels = n_nan;
+    return DT_OK;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (!nan_pixels) {   // enqueue only
+    if (n_px > 0) HIPCHK(dt_launch_resolve(accum, out, n_px, n_samples, nullptr, st));
+    return DT_OK;
+  }
+  unsigned long long* d_nan = nullptr;
+  unsigned long long h_nan = 0;
+  HIPCHK(hipMalloc((void**)&d_nan, sizeof(unsigned long long)));
+  hipError_t e = hipMemsetAsync(d_nan, 0, sizeof(unsigned long long), st);
+  if (e == hipSuccess && n_px > 0) e = dt_launch_resolve(accum, out, n_px, n_samples, d_nan, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&h_nan, d_nan, sizeof(h_nan), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_nan);
+  if (e != hipSuccess) return fail(DT_E_NO_DEVICE, std::string("dt_resolve: ") + hipGetErrorString(e));
+  *nan_pixels = h_nan;
+  return DT_OK;
 }
 
 // Intersection micro-benchmark: dt_isect_kernel over rays first_ray .. first_ray+n_rays-1

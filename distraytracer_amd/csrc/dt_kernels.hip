@@ -131,19 +131,39 @@ using namespace dtd;
 // motion-blur shifts in tunnel scenes (*_tunnel) and in any scene (*_blur), and the *_sky builds
 // that render the items the still builds list)
 #ifdef DT_KNAME
-#define DT_TRACE_KERNEL DT_KNAME
+#define DT_TRACE_KERNEL_BASE DT_KNAME
 #elif DT_WITH_RPC
-#define DT_TRACE_KERNEL dt_trace_kernel_rpc
+#define DT_TRACE_KERNEL_BASE dt_trace_kernel_rpc
 #elif DT_DONATE
-#define DT_TRACE_KERNEL dt_trace_kernel_dn
+#define DT_TRACE_KERNEL_BASE dt_trace_kernel_dn
 #elif DT_W5
-#define DT_TRACE_KERNEL dt_trace_kernel_w5
+#define DT_TRACE_KERNEL_BASE dt_trace_kernel_w5
 #else
-#define DT_TRACE_KERNEL dt_trace_kernel
+#define DT_TRACE_KERNEL_BASE dt_trace_kernel
 #endif
 // DT_HELPERS=1 (the 4-wave room build): also the small kernels and the launch-record helpers
 #ifndef DT_HELPERS
 #define DT_HELPERS 0
+#endif
+// DT_WINDOW=1 (build/win_*.o: every trace build once more, named <kernel>_win): the window mode of
+// the item loop for dt_render_window. A window launch runs the chunks [P.chunk_lo, P.chunk_hi) of
+// every pixel item, starts each pixel's sums from the caller's f64 accumulator (S.accum) and stores
+// the sums back there in place of a pixel: no division, no clamp (dt_resolve_kernel does those). The
+// summation chain is the same code, so ascending gap-free windows from 0 on a zeroed accumulator
+// add a pixel's samples in the one-shot render's order. Builds of their own, not runtime branches:
+// with DT_WINDOW=0 none of this is compiled, so the product kernels keep their register allocation
+// (this kernel is spill-sensitive, Makefile CODEGEN).
+#ifndef DT_WINDOW
+#define DT_WINDOW 0
+#endif
+#define DT_CAT2(a, b) a##b
+#define DT_CAT(a, b) DT_CAT2(a, b)
+#if DT_WINDOW
+#define DT_TRACE_KERNEL DT_CAT(DT_TRACE_KERNEL_BASE, _win)
+#undef DT_HELPERS
+#define DT_HELPERS 0
+#else
+#define DT_TRACE_KERNEL DT_TRACE_KERNEL_BASE
 #endif
 
 #define DT_STACK_MAX 48
@@ -218,7 +238,10 @@ struct DScene {
   // diagnostic builds (-DDT_ITEM_TIMES=2, DT_ITEM_COSTS=1): per queue code, the item's duration on the
   // 100 MHz clock (dt_debug_item_costs, tools/chunk_costs.py); null otherwise
   uint32_t* item_cost;
-  void* pad_;   // (keeps sizeof(DScene) a multiple of 16: DLaunch::P at the offset it had)
+  // window launches (P.chunk_lo/chunk_hi, the *_win builds): the caller's f64 accumulator, one double
+  // per float of the output and in its layout (store_pixel's offsets); null otherwise. (In the
+  // place of a pad word: sizeof(DScene) stays a multiple of 16, DLaunch::P at the offset it had.)
+  double* accum;
 };
 
 // pow(x, n) for the integer exponents the reference writes as pow(x, 2.0) etc. pow(x, 1) is x
@@ -3369,7 +3392,12 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
       chunk_lo = (int)ck;
       chunk_hi = chunk_lo + 1;
     }
-    bool px_done = true;   // false for chunk items: dt_chunk_sum_kernel stores their pixels
+#if DT_WINDOW
+    // window launches (per-pixel items always: the host sets chunk_items = 0): the window's chunks
+    chunk_lo = P.chunk_lo;
+    chunk_hi = P.chunk_hi;
+#endif
+    bool px_done = true;  // false for chunk items: dt_chunk_sum_kernel stores their pixels
     bool sky_again = false;
 #if DT_AGAIN_QUEUE
     // the item's counters are taken back: the launch that listed it counted it already
@@ -3385,6 +3413,20 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
     if (DT_PSUM_LDS == 1 || lane < 8) {   // pixel j's sums, in sample order
       psum[0][lane] = 0; psum[1][lane] = 0; psum[2][lane] = 0;
     }
+#if DT_WINDOW
+    // the sums go on from the pixel's accumulator values: the samples below chunk_lo, added by the
+    // earlier windows (the epilogue's lane and offset)
+    if (lane < group) {
+      int qx, qy;
+      int64_t qo;
+      bool qv;
+      pixel_of(P, item * group + lane, qx, qy, qo, qv);
+      if (qv) {
+        const double* const acc = S.accum + (P.layout == DT_OUT_SLAB ? qo : 3 * ((int64_t)(P.yRes - 1 - qy) * P.xRes + qx));
+        psum[0][lane] = acc[0]; psum[1][lane] = acc[1]; psum[2][lane] = acc[2];
+      }
+    }
+#endif
     int px_x = 0, px_y = 0;
     int64_t px_off = 0;
     bool px_valid = false;
@@ -3527,6 +3569,15 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
       int64_t qo;
       bool qv;
       pixel_of(P, item * group + lane, qx, qy, qo, qv);
+#if DT_WINDOW
+      // the window's sums back to the accumulator, where store_pixel would put the pixel: no division,
+      // no clamp (dt_resolve_kernel). An item listed for the *_sky build is stored by that launch,
+      // which runs its window again from the untouched accumulator values
+      if (qv && !item_again) {
+        double* const acc = S.accum + (P.layout == DT_OUT_SLAB ? qo : 3 * ((int64_t)(P.yRes - 1 - qy) * P.xRes + qx));
+        acc[0] = psum[0][lane]; acc[1] = psum[1][lane]; acc[2] = psum[2][lane];
+      }
+#else
       if (qv && !item_again && !(P.sky_defer && S.sky_miss[item * group + lane])) {
         V3 color = divs(v3(psum[0][lane], psum[1][lane], psum[2][lane]), spp);
 #ifdef DT_ITEM_TIMES   // diagnostic builds (tools/item_times.py): the item's wave cycles / 1e4, raw
@@ -3547,6 +3598,7 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
 #endif
         if (isnan(color.x) || isnan(color.y) || isnan(color.z)) atomicAdd(S.stats + ST_NAN, 1ull);
       }
+#endif
     }
 #if DT_AGAIN_QUEUE
     // a listed item is counted by the launch that listed it: the *_sky build takes its counts back
@@ -3671,6 +3723,32 @@ dt_chunk_sum_kernel(const DLaunch* __restrict__ Lp, float* __restrict__ out)
   if ((threadIdx.x & 63) == 0 && n) atomicAdd(S.stats + ST_NAN, n);
 }
 
+// dt_resolve: the accumulator of window launches (sums of the first n_samples sample colours, in the
+// output's layout) to the output's floats: / n_samples (cpp:1213, divs) and clamp*255 (store_pixel),
+// the trace kernel's epilogue on the same values. One pixel (three consecutive doubles) per thread:
+// a wave reads 1536 and writes 768 contiguous bytes; grid-stride over whole blocks, so every wave
+// reaches the ballot that counts its NaN pixels.
+extern "C" __global__ void __launch_bounds__(256)
+dt_resolve_kernel(const double* __restrict__ accum, float* __restrict__ out, int64_t n_px, int n_samples,
+                  unsigned long long* __restrict__ nan_px)
+{
+  unsigned long long n_nan = 0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n_px; base += stride) {
+    const int64_t q = base + threadIdx.x;
+    bool nan = false;
+    if (q < n_px) {
+      const V3 color = divs(v3(accum[3 * q], accum[3 * q + 1], accum[3 * q + 2]), n_samples);
+      out[3 * q + 0] = clampf01((float)color.x) * 255.0f;
+      out[3 * q + 1] = clampf01((float)color.y) * 255.0f;
+      out[3 * q + 2] = clampf01((float)color.z) * 255.0f;
+      nan = isnan(color.x) || isnan(color.y) || isnan(color.z);
+    }
+    n_nan += __popcll(__ballot(nan));
+  }
+  if ((threadIdx.x & 63) == 0 && n_nan && nan_px) atomicAdd(nan_px, n_nan);
+}
+
 // renderImageCloud (cpp:1224-1279): one pixel per lane
 extern "C" __global__ void __launch_bounds__(256)
 dt_sky_kernel(const DLaunch* __restrict__ Lp, float* __restrict__ out)
@@ -3762,6 +3840,14 @@ extern "C" hipError_t dt_launch_chunk_sum(const void* dev_launch, float* out, in
   hipLaunchKernelGGL(dt_chunk_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const DLaunch*)dev_launch, out);
   return hipGetLastError();
 }
+extern "C" hipError_t dt_launch_resolve(const double* accum, float* out, int64_t n_px, int n_samples,
+                                        unsigned long long* nan_px, hipStream_t stream)
+{
+  int64_t blocks = (n_px + 255) / 256;
+  if (blocks > 8192) blocks = 8192;   // (grid-stride past that: 32 waves per CU)
+  hipLaunchKernelGGL(dt_resolve_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, accum, out, n_px, n_samples, nan_px);
+  return hipGetLastError();
+}
 extern "C" hipError_t dt_launch_sky(const void* dev_launch, float* out, int64_t n_threads, hipStream_t stream)
 {
   int64_t blocks = (n_threads + 255) / 256;
@@ -3781,8 +3867,6 @@ extern "C" hipError_t dt_launch_unpack(const void* dev_launch, int world, int64_
 
 #if !DT_ISECT
 // every trace-kernel build: <kernel>_launch and <kernel>_ptr (dt_api.cpp's kernel table)
-#define DT_CAT2(a, b) a##b
-#define DT_CAT(a, b) DT_CAT2(a, b)
 #if DT_W5
 static_assert(DT_TRACE_MIN_WAVES == 5 && DT_PSUM_LDS == 2, "5-wave build: Makefile W5FLAGS");
 #endif
@@ -3793,11 +3877,11 @@ extern "C" hipError_t DT_CAT(DT_TRACE_KERNEL, _launch)(const void* dev_launch, f
 }
 extern "C" const void* DT_CAT(DT_TRACE_KERNEL, _ptr)(void) { return (const void*)DT_TRACE_KERNEL; }
 // bit 0: the build lists sky items for another launch (DT_SKY_AGAIN); bit 1: it runs chunk items
-// (DT_CHUNK_ITEMS); bits 8..23: the scene features
+// (DT_CHUNK_ITEMS); bit 2: it runs window launches (DT_WINDOW); bits 8..23: the scene features
 // it handles (DT_FEATURES; dt_api.cpp launches it only for scenes within them)
 extern "C" int DT_CAT(DT_TRACE_KERNEL, _traits)(void)
 {
-  return (DT_SKY_AGAIN ? 1 : 0) | (DT_CHUNK_ITEMS ? 2 : 0) | (int)(((DT_FEATURES) & 0xFFFFu) << 8);
+  return (DT_SKY_AGAIN ? 1 : 0) | (DT_CHUNK_ITEMS ? 2 : 0) | (DT_WINDOW ? 4 : 0) | (int)(((DT_FEATURES) & 0xFFFFu) << 8);
 }
 #endif
 #endif   // !DT_REPRO

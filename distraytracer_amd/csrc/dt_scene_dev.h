@@ -200,6 +200,10 @@ struct DParams {
   // adds every sample colour in sample order (dt_kernels.hip item loop). 2 = the same with the queue
   // chunk-major (code = chunk * n_items + pixel item: a pixel's chunks far apart; the tests' check)
   int32_t chunk_items;
+  // window launches (dt_render_window; the *_win builds, dt_kernels.hip DT_WINDOW): the item loop runs
+  // the chunks [chunk_lo, chunk_hi) of every pixel item, starting each pixel's sums from its
+  // accumulator values (DScene::accum) and storing them back instead of a pixel. 0, 0: no window
+  int32_t chunk_lo, chunk_hi;
 };
 
 #ifndef DT_HD

@@ -12,6 +12,12 @@
 //   dtrender spheres         buildSceneSpheres(0) 256x256 (config C1)
 //   dtrender prismcyl <n>    BuildScenePrismCylinder(n) 640x480 (1711-1723)
 // options (after the mode): --out FILE(.ppm|.png)  --spp N  --depth N  --res WxH  --seed S
+//   --progressive N   render in sample windows of N 64-sample chunks (dt_render_window) onto an f64
+//                     accumulator on the device; after every window the output file is overwritten
+//                     with the resolved preview (the mean of the samples so far) and samples_done/spp
+//                     is printed. The final file is byte-identical to the run without the flag.
+#include <hip/hip_runtime_api.h>
+
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -36,7 +42,7 @@ int main(int argc, char** argv)
   int arg = (argc > 2 && argv[2][0] != '-') ? atoi(argv[2]) : 0;
   std::string out;
   std::string data_dir = DT_DATA_DIR;
-  int spp = -1, depth = -1, W = -1, H = -1;
+  int spp = -1, depth = -1, W = -1, H = -1, progressive = 0;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     if (a == "--out" && i + 1 < argc) out = argv[++i];
@@ -45,6 +51,7 @@ int main(int argc, char** argv)
     else if (a == "--seed" && i + 1 < argc) g.seed = (uint32_t)strtoul(argv[++i], nullptr, 10);
     else if (a == "--data" && i + 1 < argc) data_dir = argv[++i];
     else if (a == "--res" && i + 1 < argc) sscanf(argv[++i], "%dx%d", &W, &H);
+    else if (a == "--progressive" && i + 1 < argc) progressive = atoi(argv[++i]);
   }
   std::string scene = "final";
   float build_frame = 0;
@@ -102,12 +109,49 @@ int main(int argc, char** argv)
   if (rc) return die("dt_scene_create", rc);
   std::vector<float> img((size_t)3 * g.xRes * g.yRes, 0.0f);
   dt_stats st;
-  rc = dt_render(s, &g, frame, nullptr, img.data(), 0, nullptr, &st);
-  if (rc) return die("dt_render", rc);
   std::string fn = out.empty() ? std::string(buf) : out;
   const bool png = fn.size() > 4 && fn.compare(fn.size() - 4, 4, ".png") == 0;
-  rc = png ? dt_write_png(fn.c_str(), g.xRes, g.yRes, img.data()) : dt_write_ppm(fn.c_str(), g.xRes, g.yRes, img.data());
-  if (rc) return die("dt_write_ppm/png", rc);
+  if (progressive > 0) {
+    // windows of `progressive` chunks in ascending order onto a zeroed accumulator; every window's
+    // preview (dt_resolve with the samples so far) overwrites the file, the last one is the frame
+    const int n = (int)sqrt((double)g.antialias_samples), total = n * n;
+    const int64_t n_acc = dt_accum_doubles(&g, nullptr);
+    double* acc = nullptr;
+    float* dimg = nullptr;
+    if (hipMalloc((void**)&acc, n_acc * sizeof(double)) != hipSuccess || hipMalloc((void**)&dimg, n_acc * sizeof(float)) != hipSuccess ||
+        hipMemset(acc, 0, n_acc * sizeof(double)) != hipSuccess) {
+      fprintf(stderr, "accumulator: hipMalloc failed\n");
+      return 1;
+    }
+    dt_stats sum;
+    memset(&sum, 0, sizeof sum);
+    for (int begin = 0; begin < total;) {
+      const int end = total < 64 || begin + 64 * progressive > total ? total : begin + 64 * progressive;
+      rc = dt_render_window(s, &g, frame, nullptr, begin, end, acc, nullptr, &st);
+      if (rc) return die("dt_render_window", rc);
+      sum.samples += st.samples;
+      sum.kernel_ms += st.kernel_ms;
+      rc = dt_resolve(&g, nullptr, acc, end, dimg, 1, nullptr, nullptr);
+      if (rc) return die("dt_resolve", rc);
+      if (hipMemcpy(img.data(), dimg, n_acc * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+        fprintf(stderr, "preview: hipMemcpy failed\n");
+        return 1;
+      }
+      rc = png ? dt_write_png(fn.c_str(), g.xRes, g.yRes, img.data()) : dt_write_ppm(fn.c_str(), g.xRes, g.yRes, img.data());
+      if (rc) return die("dt_write_ppm/png", rc);
+      printf("%d/%d\n", end, total);
+      fflush(stdout);
+      begin = end;
+    }
+    (void)hipFree(acc);
+    (void)hipFree(dimg);
+    st = sum;
+  } else {
+    rc = dt_render(s, &g, frame, nullptr, img.data(), 0, nullptr, &st);
+    if (rc) return die("dt_render", rc);
+    rc = png ? dt_write_png(fn.c_str(), g.xRes, g.yRes, img.data()) : dt_write_ppm(fn.c_str(), g.xRes, g.yRes, img.data());
+    if (rc) return die("dt_write_ppm/png", rc);
+  }
   double msps = st.samples / (st.kernel_ms * 1e-3) / 1e6;
   printf("Rendered %s frame %d: %dx%d, %d spp, depth %d in %.2f ms (kernel, %.1f Mpixel-samples/s) -> %s\n",
          scene.c_str(), frame, g.xRes, g.yRes, (int)st.samples / (g.xRes * g.yRes), g.max_depth, st.kernel_ms,

@@ -45,6 +45,8 @@ extern "C" {
 /* 6: dt_trace_build (the trace-kernel build a render launches, and the features it covers) */
 /* 7: dt_render_repeat_async; dt_accel_info.sg_sub_blocks / sg_sub_nodes / sg_sub_hash */
 /* 8: dt_render_repeat_async removed (a measurement stand-in with no product caller) */
+/* (still 8, new exports only, no struct changed: dt_accum_doubles, dt_window_check, dt_render_window,
+ *    dt_render_window_async, dt_resolve -- progressive rendering) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -345,6 +347,46 @@ int dt_render(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_ti
 int dt_render_async(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
                     float* out_device, void* stream);
 int dt_collect_stats(const dt_scene* s, void* stream, dt_stats* stats);
+
+/* ---- progressive rendering: sample windows into a resident accumulator ----
+ * No reference counterpart: the reference takes a frame whole (render_final_project.cpp:1031-1218).
+ * A window [begin, end) is the samples begin..end-1 of every owned pixel; a window render adds them,
+ * in sample order, onto an f64 accumulator on the device, and dt_resolve turns the accumulator into
+ * the usual output at any time (the mean of the samples added so far).
+ *
+ * The accumulator has one double per float of the output, in the output's layout (element i of the
+ * accumulator belongs to element i of the image): 3*xRes*yRes in ppmOut indexing for DT_OUT_IMAGE,
+ * dt_slab_floats for DT_OUT_SLAB. 24 bytes per pixel. dt_accum_doubles: its length (host only;
+ * < 0: invalid globals or tiles). */
+int64_t dt_accum_doubles(const dt_globals* g, const dt_tiles* tiles);
+/* The window rules, host only; spp = int(sqrt(antialias_samples))^2:
+ *   0 <= begin < end <= spp;
+ *   spp >= 64: begin % 64 == 0, and end % 64 == 0 or end == spp (whole 64-sample chunks, the unit
+ *              one wave traces);
+ *   spp <  64: the only window is [0, spp).
+ * DT_E_INVALID with a dt_last_error naming the rule otherwise. */
+int dt_window_check(const dt_globals* g, int32_t begin, int32_t end);
+/* Render the window onto accum_device (dt_accum_doubles doubles, device memory). Synchronous; stats
+ * reports this window alone: samples = pixels * (end - begin), rays etc. of the window's samples,
+ * nan_pixels 0 (dt_resolve counts them). A null scene, a null accumulator or a bad window:
+ * DT_E_INVALID before any device work.
+ * THE CALLER ORDERS THE WINDOWS. The accumulator equals the one-shot render's per-pixel sums (and
+ * dt_resolve with n_samples = spp dt_render's output, bit for bit) only for ascending, gap-free
+ * windows starting at 0 on a zeroed accumulator: f64 addition is not associative, and each window
+ * continues the pixel's chain from the value it finds. One window at a time per accumulator. */
+int dt_render_window(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                     int32_t begin, int32_t end, double* accum_device, void* stream, dt_stats* stats);
+/* enqueue only, as dt_render_async; dt_collect_stats then reports the window */
+int dt_render_window_async(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                           int32_t begin, int32_t end, double* accum_device, void* stream);
+/* out[i] = clamp01((float)(accum[i] / n_samples)) * 255.0f for every element of the accumulator: the
+ * division and store of dt_render's epilogue (cpp:1213-1217) on the sums of the first n_samples
+ * samples. accum and out on the same side: host (on_device=0, a plain loop) or device (1, a kernel
+ * on `stream`). Elements of pixels the rank does not own (DT_OUT_IMAGE with a tile share) are 0 in
+ * a zeroed accumulator and resolve to 0. nan_pixels (optional): pixels with a NaN channel; on the
+ * device the call is synchronous when it is asked for and only enqueues otherwise. */
+int dt_resolve(const dt_globals* g, const dt_tiles* tiles, const double* accum, int32_t n_samples,
+               float* out, int32_t on_device, void* stream, uint64_t* nan_pixels);
 
 /* diagnostic builds (-DDT_STAMPS): per-phase cycle sums of the last render; zeros otherwise */
 int dt_debug_counters(const dt_scene* s, uint64_t* out, int32_t n);
