@@ -22,7 +22,8 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "DT_OUT_IMAGE", "DT_OUT_SLAB", "slab_floats", "slab_floats_max", "unpack_slabs", "tiles", "check", "lib",
            "accel_info", "DT_KERNEL_AUTO", "DT_KERNEL_PRODUCT", "DT_KERNEL_DONATE",
            "accum_doubles", "window_check", "render_window", "render_window_async", "resolve", "Progressive",
-           "mean_abs_change"]
+           "mean_abs_change", "adapt_converged", "render_window_adaptive", "resolve_adaptive", "adapt_select_ms",
+           "AdaptiveProgressive"]
 
 
 def globals_default():
@@ -378,6 +379,154 @@ class Progressive:
         return p
 
 
+def adapt_converged(s1, s2, count, tol, min_samples=64):
+    """The convergence rule of adaptive sampling on host values (dt_adapt_converged): s1, s2 the
+    pixel's three sums of sample colours and of their squares, count the samples in them."""
+    a = (ctypes.c_double * 3)(*[float(v) for v in s1])
+    b = (ctypes.c_double * 3)(*[float(v) for v in s2])
+    rc = lib.dt_adapt_converged(a, b, int(count), float(tol), int(min_samples))
+    if rc < 0:
+        check(rc, "dt_adapt_converged")
+    return bool(rc)
+
+
+def _count_ptr(count, g, tile):
+    if not hasattr(count, "data_ptr") or str(count.dtype) != "torch.int32" or not count.is_cuda \
+            or not count.is_contiguous():
+        raise DTError("the sample counts must be a contiguous CUDA torch.int32 tensor (read as uint32)")
+    if 3 * count.numel() < accum_doubles(g, tile):
+        raise DTError("the sample counts hold %d entries, (g, tile) need %d" % (count.numel(), accum_doubles(g, tile) // 3))
+    return ctypes.c_void_p(count.data_ptr())
+
+
+def render_window_adaptive(scene, g, frame, accum, accum2, count, begin, end, tol, min_samples=64, tile=None,
+                           stream=None):
+    """render_window over the pixels that are live (count == begin) and have not converged
+    (dt_render_window_adaptive): accum2 the sums of squared sample colours (float64, like accum),
+    count the samples per pixel (int32 tensor, read as uint32). Returns the window's Stats: pixels is
+    the number of pixels traced."""
+    st = Stats()
+    check(lib.dt_render_window_adaptive(scene.handle, ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None,
+                                        int(begin), int(end), _accum_ptr(accum, g, tile), _accum_ptr(accum2, g, tile),
+                                        _count_ptr(count, g, tile), float(tol), int(min_samples),
+                                        ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)),
+          "dt_render_window_adaptive")
+    return st
+
+
+def adapt_select_ms(scene):
+    """Device time of the selection kernels of the scene's last adaptive window launch."""
+    ms = ctypes.c_float(0)
+    check(lib.dt_adapt_select_ms(scene.handle, ctypes.byref(ms)), "dt_adapt_select_ms")
+    return ms.value
+
+
+def resolve_adaptive(g, accum, count, out, tile=None, stream=None):
+    """out[3q+k] = clamp01(float32(accum[3q+k] / count[q])) * 255, 0 where count[q] is 0
+    (dt_resolve_adaptive): all three on the same side; count int32 (torch) or uint32 / int32 (numpy).
+    Returns the number of pixels with a NaN channel."""
+    ap, adev = _ptr_typed(accum, "torch.float64", "float64")
+    if hasattr(count, "data_ptr"):
+        cp, cdev = _ptr_typed(count, "torch.int32", "int32")
+    else:
+        cp, cdev = _ptr_typed(count, "", "int32" if str(count.dtype) == "int32" else "uint32")
+    op, odev = _ptr(out)
+    if not adev == cdev == odev:
+        raise DTError("accum, count and out must be on the same side")
+    need = accum_doubles(g, tile)
+    for a, k in ((accum, 1), (out, 1), (count, 3)):
+        if k * (a.numel() if hasattr(a, "numel") else a.size) < need:
+            raise DTError("resolve_adaptive: (g, tile) need %d elements" % (need // k))
+    nan = ctypes.c_uint64(0)
+    check(lib.dt_resolve_adaptive(ctypes.byref(g), ctypes.byref(tile) if tile else None, ap, cp, op, adev,
+                                  ctypes.c_void_p(stream) if stream else None, ctypes.byref(nan)), "dt_resolve_adaptive")
+    return nan.value
+
+
+class AdaptiveProgressive(Progressive):
+    """Progressive with adaptive sampling: between windows, pixels whose mean has converged stop.
+
+        p = AdaptiveProgressive(scene, g, frame, tol=0.5)
+        p.run()
+        img = p.image()             # every pixel the mean of its own samples
+        share = p.samples_taken / (p.sample_counts().numel() * p.spp)
+
+    tol is the standard error of a pixel's mean allowed, in grey levels of the 0..255 output; a pixel
+    may stop once it has min_samples (and at least 64) samples. The state is three device buffers:
+    accum, accum2 (sums of squares) and count (samples per pixel), 52 B per pixel; a pixel is live at
+    a window iff its count is the window's begin. A pixel that never stops has the one-shot render's
+    bits. done: a step traced no pixel, or all spp samples are rendered."""
+
+    def __init__(self, scene, g, frame, tol, min_samples=64, tile=None):
+        import torch
+        super().__init__(scene, g, frame, tile)
+        self.tol, self.min_samples = float(tol), int(min_samples)
+        self.accum2 = torch.zeros_like(self.accum)
+        self.count = torch.zeros(max(self.accum.numel() // 3, 1), dtype=torch.int32, device="cuda")
+        self.active_pixels = None
+        self._idle = False
+
+    @property
+    def done(self):
+        return self._idle or self.samples_done >= self.spp
+
+    def step(self, n_chunks=1):
+        """Render the next window over the live, unconverged pixels. Returns the window's Stats."""
+        if self.done:
+            raise DTError("AdaptiveProgressive.step: the frame is done")
+        if n_chunks < 1:
+            raise DTError("AdaptiveProgressive.step: n_chunks < 1")
+        begin = self.samples_done
+        end = min(begin + 64 * int(n_chunks), self.spp)
+        st = render_window_adaptive(self.scene, self.g, self.frame, self.accum, self.accum2, self.count, begin, end,
+                                    self.tol, self.min_samples, self.tile)
+        self.samples_done = end
+        self.active_pixels = int(st.pixels)
+        self._idle = st.pixels == 0
+        return st
+
+    def sample_counts(self):
+        """The samples added per pixel so far (the count tensor: int32, in the accumulator's pixel order)."""
+        return self.count
+
+    @property
+    def samples_taken(self):
+        import torch
+        return int(self.count.sum(dtype=torch.int64).item())
+
+    def image(self, out=None):
+        """The resolved image: every pixel the mean of its own samples (0 where it has none)."""
+        import torch
+        if self.samples_done < 1:
+            raise DTError("AdaptiveProgressive.image: no window rendered yet")
+        if out is None:
+            out = torch.empty(self.accum.numel(), dtype=torch.float32, device="cuda")
+        self.nan_pixels = resolve_adaptive(self.g, self.accum, self.count, out, self.tile)
+        return out
+
+    def state(self):
+        d = super().state()
+        d.update({"accum2": self.accum2.cpu().numpy().copy(), "count": self.count.cpu().numpy().copy(),
+                  "tol": self.tol, "min_samples": self.min_samples})
+        return d
+
+    @classmethod
+    def restore(cls, scene, g, state):
+        import numpy as np
+        import torch
+        p = super().restore(scene, g, state)
+        acc2 = np.ascontiguousarray(state["accum2"], dtype=np.float64).reshape(-1)
+        cnt = np.ascontiguousarray(state["count"], dtype=np.int32).reshape(-1)
+        if acc2.size != p.accum.numel() or cnt.size != max(p.accum.numel() // 3, 1):
+            raise DTError("AdaptiveProgressive.restore: accum2 / count do not match the accumulator")
+        p.accum2 = torch.from_numpy(acc2).to("cuda")
+        p.count = torch.from_numpy(cnt).to("cuda")
+        p.tol, p.min_samples = float(state["tol"]), int(state["min_samples"])
+        p.active_pixels = None
+        p._idle = False
+        return p
+
+
 def mean_abs_change(a, b):
     """Mean absolute difference of two resolved images (torch): an early-stop measure for
     Progressive.run(until=...)."""
@@ -396,17 +545,27 @@ def write_png(filename, g, values):
     check(lib.dt_write_png(filename.encode(), g.xRes, g.yRes, ctypes.c_void_p(v.ctypes.data)), "dt_write_png")
 
 
-def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progressive=None):
+def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progressive=None, adaptive=None):
     """render_final_project.cpp:965: build (sceneBuilder names a scene.h builder), render the
     frame on the current GPU, write the PPM. Returns (image, stats). progressive=callback renders in
     one-chunk sample windows (Progressive) and calls callback(image, samples_done) with the resolved
-    preview (numpy) after every window; the image returned is the same bits, stats the last window's."""
+    preview (numpy) after every window; the image returned is the same bits, stats the last window's.
+    adaptive=tol renders with adaptive sampling (AdaptiveProgressive at that tolerance, in grey levels):
+    converged pixels stop between windows, every pixel is the mean of its own samples; a progressive
+    callback is called after every window as well."""
     import numpy as np
     g = g if g is not None else globals_default()
     built = build_scene(sceneBuilder, frame if builder_frame is None else builder_frame, g)
     scene = Scene(built, g)
     img = np.zeros(3 * g.xRes * g.yRes, dtype=np.float32)
-    if progressive is not None:
+    if adaptive is not None:
+        p = AdaptiveProgressive(scene, g, frame, tol=adaptive)
+        while not p.done:
+            st = p.step()
+            if progressive is not None:
+                progressive(p.image().cpu().numpy(), p.samples_done)
+        img = p.image().cpu().numpy()
+    elif progressive is not None:
         p = Progressive(scene, g, frame)
         while not p.done:
             st = p.step()

@@ -121,7 +121,9 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_unpack_slabs", "dt_build_scene", "dt_scene_desc_free", "dt_write_ppm", "dt_write_png",
            "dt_mocap_bone_table", "dt_debug_normalize", "dt_intersect_primary",
            "dt_debug_load_obj",
-           "dt_accum_doubles", "dt_window_check", "dt_render_window", "dt_render_window_async", "dt_resolve"]
+           "dt_accum_doubles", "dt_window_check", "dt_render_window", "dt_render_window_async", "dt_resolve",
+           "dt_adapt_converged", "dt_render_window_adaptive", "dt_render_window_adaptive_async",
+           "dt_resolve_adaptive", "dt_adapt_select_ms"]
 
 
 class DTError(RuntimeError):
@@ -182,6 +184,16 @@ def _load():
                                              ctypes.c_void_p, ctypes.c_void_p]),
         "dt_resolve": (c_int32, [P(Globals), P(Tiles), ctypes.c_void_p, c_int32, ctypes.c_void_p, c_int32,
                                  ctypes.c_void_p, P(c_uint64)]),
+        "dt_adapt_converged": (c_int32, [P(c_double), P(c_double), ctypes.c_uint32, c_double, c_int32]),
+        "dt_render_window_adaptive": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, c_int32,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double, c_int32,
+                                                ctypes.c_void_p, P(Stats)]),
+        "dt_render_window_adaptive_async": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, c_int32,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_double,
+                                                      c_int32, ctypes.c_void_p]),
+        "dt_resolve_adaptive": (c_int32, [P(Globals), P(Tiles), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          c_int32, ctypes.c_void_p, P(c_uint64)]),
+        "dt_adapt_select_ms": (c_int32, [ctypes.c_void_p, P(ctypes.c_float)]),
         "dt_debug_counters": (c_int32, [ctypes.c_void_p, P(c_uint64), c_int32]),
         "dt_debug_item_costs": (c_int64, [ctypes.c_void_p, P(ctypes.c_uint32), c_int64]),
         "dt_debug_normalize": (c_int32, [P(c_double), P(c_double), c_int64]),

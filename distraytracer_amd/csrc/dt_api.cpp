@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "dt_adapt.h"
 #include "host_internal.h"
 
 using namespace dth;
@@ -61,9 +62,28 @@ DT_TRACE_BUILD(dt_trace_kernel_w5_blur_win)
 DT_TRACE_BUILD(dt_trace_kernel_w5_sky_win)
 DT_TRACE_BUILD(dt_trace_kernel_dn_win)
 DT_TRACE_BUILD(dt_trace_kernel_rpc_win)
+// ... and the window builds with adaptive sampling (DT_WINDOW=2, Makefile AWIN_OBJ)
+DT_TRACE_BUILD(dt_trace_kernel_awin)
+DT_TRACE_BUILD(dt_trace_kernel_mesh_awin)
+DT_TRACE_BUILD(dt_trace_kernel_full_awin)
+DT_TRACE_BUILD(dt_trace_kernel_tunnel_awin)
+DT_TRACE_BUILD(dt_trace_kernel_blur_awin)
+DT_TRACE_BUILD(dt_trace_kernel_sky_awin)
+DT_TRACE_BUILD(dt_trace_kernel_w5_awin)
+DT_TRACE_BUILD(dt_trace_kernel_w5_mesh_awin)
+DT_TRACE_BUILD(dt_trace_kernel_w5_full_awin)
+DT_TRACE_BUILD(dt_trace_kernel_w5_tunnel_awin)
+DT_TRACE_BUILD(dt_trace_kernel_w5_blur_awin)
+DT_TRACE_BUILD(dt_trace_kernel_w5_sky_awin)
+DT_TRACE_BUILD(dt_trace_kernel_dn_awin)
+DT_TRACE_BUILD(dt_trace_kernel_rpc_awin)
 #undef DT_TRACE_BUILD
 extern "C" hipError_t dt_launch_resolve(const double* accum, float* out, int64_t n_px, int n_samples,
                                         unsigned long long* nan_px, hipStream_t stream);
+extern "C" hipError_t dt_launch_resolve_adaptive(const double* accum, const uint32_t* count, float* out, int64_t n_px,
+                                                 unsigned long long* nan_px, hipStream_t stream);
+extern "C" int64_t dt_adapt_select_blocks(int64_t n_items);
+extern "C" hipError_t dt_launch_adapt_select(const void* dev_launch, int64_t n_items, hipStream_t stream);
 extern "C" hipError_t dt_launch_isect(const void* dev_launch, int64_t first, int64_t n, int32_t* hit_shape, float* hit_t,
                                       int grid, hipStream_t stream);
 extern "C" const void* dt_isect_kernel_ptr(void);
@@ -253,6 +273,13 @@ struct dt_scene {
   void* d_pl_list = nullptr;
   dtd::DParams last;
   int last_px_samples = 0;   // samples per pixel of the last launch: spp, or a window's end - begin
+  // adaptive window launches (dt_render_window_adaptive): the selection's buffers in one allocation
+  // (the list's length, the list, the per-wave offsets and keep bits; adapt_layout) for up to
+  // adapt_cap items; ev_sel fires when the selection kernels have run (dt_adapt_select_ms)
+  uint8_t* d_adapt = nullptr;
+  int64_t adapt_cap = -1;
+  hipEvent_t ev_sel = nullptr;
+  bool last_adaptive = false;   // the last launch ran over the selection's list: stats.pixels is its length
 };
 
 extern "C" {
@@ -405,12 +432,14 @@ static void release_device(dt_scene* s)
                    &s->d_sg_cells, &s->d_sg_list, &s->d_sub_nodes, &s->d_sub_blocks, &s->d_leaf, &s->d_hdr, &s->d_geom, &s->d_mat, &s->d_lights,
                    &s->d_tex, &s->d_zs, (void**)&s->d_stats, &s->d_launch, (void**)&s->d_sky_miss, &s->d_dn_pool,
                    (void**)&s->d_again, &s->d_launch2, (void**)&s->d_stats2, (void**)&s->d_chunk_cols,
-                   (void**)&s->d_item_cost};
+                   (void**)&s->d_item_cost, (void**)&s->d_adapt};
   for (void** b : bufs) {
     if (*b) (void)hipFree(*b);
     *b = nullptr;
   }
-  for (hipEvent_t* e : {&s->ev0, &s->ev1, &s->ev_copy}) {
+  s->adapt_cap = -1;
+  s->last_adaptive = false;
+  for (hipEvent_t* e : {&s->ev0, &s->ev1, &s->ev_copy, &s->ev_sel}) {
     if (*e) (void)hipEventDestroy(*e);
     *e = nullptr;
   }
@@ -795,15 +824,24 @@ static Build g_win_builds[2][6] = {
     {DT_B(dt_trace_kernel_w5_win), DT_B(dt_trace_kernel_w5_mesh_win), DT_B(dt_trace_kernel_w5_full_win),
      DT_B(dt_trace_kernel_w5_tunnel_win), DT_B(dt_trace_kernel_w5_blur_win), DT_B(dt_trace_kernel_w5_sky_win)}};
 static Build g_dn_win_build = DT_B(dt_trace_kernel_dn_win), g_rpc_win_build = DT_B(dt_trace_kernel_rpc_win);
+// ... and of the adaptive window builds (trait bit 3), for dt_render_window_adaptive
+static Build g_awin_builds[2][6] = {
+    {DT_B(dt_trace_kernel_awin), DT_B(dt_trace_kernel_mesh_awin), DT_B(dt_trace_kernel_full_awin),
+     DT_B(dt_trace_kernel_tunnel_awin), DT_B(dt_trace_kernel_blur_awin), DT_B(dt_trace_kernel_sky_awin)},
+    {DT_B(dt_trace_kernel_w5_awin), DT_B(dt_trace_kernel_w5_mesh_awin), DT_B(dt_trace_kernel_w5_full_awin),
+     DT_B(dt_trace_kernel_w5_tunnel_awin), DT_B(dt_trace_kernel_w5_blur_awin), DT_B(dt_trace_kernel_w5_sky_awin)}};
+static Build g_dn_awin_build = DT_B(dt_trace_kernel_dn_awin), g_rpc_awin_build = DT_B(dt_trace_kernel_rpc_awin);
 #undef DT_B
 
 // the window build of the product build b: the same flags with the window mode of the item loop
-static Build& window_build_for(const Build& b)
+// (adaptive: its adaptive window build)
+static Build& window_build_for(const Build& b, bool adaptive)
 {
   for (int w = 0; w < 2; ++w)
     for (int v = 0; v < 6; ++v)
-      if (&b == &g_builds[w][v]) return g_win_builds[w][v];
-  return &b == &g_dn_build ? g_dn_win_build : g_rpc_win_build;
+      if (&b == &g_builds[w][v]) return adaptive ? g_awin_builds[w][v] : g_win_builds[w][v];
+  if (&b == &g_dn_build) return adaptive ? g_dn_awin_build : g_dn_win_build;
+  return adaptive ? g_rpc_awin_build : g_rpc_win_build;
 }
 
 // A window launch (dt_render_window): the chunks [chunk_lo, chunk_hi) of every pixel item onto accum
@@ -811,7 +849,29 @@ struct Window {
   int32_t chunk_lo, chunk_hi;
   int32_t samples;   // end - begin (dt_stats.samples per pixel)
   double* accum;
+  // dt_render_window_adaptive (null / 0 for dt_render_window): the sums of squares, the per-pixel
+  // sample counts, the window's bounds in samples and the convergence rule's constants (dt_adapt.h)
+  double* accum2 = nullptr;
+  uint32_t* count = nullptr;
+  int32_t begin = 0, end = 0, min_samples = 0;
+  double thr2 = 0;
 };
+
+// the selection's buffers inside dt_scene::d_adapt for n_items items: byte offsets and the total
+struct AdaptLayout {
+  int64_t waves;   // keep-bit words: four per 256-item block of the selection's grid
+  size_t list, off, mask, bytes;
+};
+static AdaptLayout adapt_layout(int64_t n_items)
+{
+  AdaptLayout L;
+  L.waves = 4 * dt_adapt_select_blocks(n_items > 0 ? n_items : 1);
+  L.list = 16;   // (the list's length in the first word)
+  L.off = L.list + sizeof(uint32_t) * (size_t)(n_items > 0 ? n_items : 1);
+  L.mask = (L.off + sizeof(uint32_t) * (size_t)L.waves + 15) & ~(size_t)15;
+  L.bytes = L.mask + sizeof(unsigned long long) * (size_t)L.waves;
+  return L;
+}
 
 // the feature mask a build was compiled for (its traits' bits 8..23: dt_kernels.hip DT_FEATURES)
 static unsigned build_features(const Build& b) { return ((unsigned)b.traits() >> 8) & 0xFFFFu; }
@@ -913,10 +973,13 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
   Build& kb_product = choose_build(sc->features, sc->no_cull, kernel_choice, P);
   const bool donate = &kb_product == &g_dn_build;
   // a window launch takes the window builds of the same choice (and of its *_sky build)
-  Build& kb = win ? window_build_for(kb_product) : kb_product;
-  Build& kb2 = win ? window_build_for(sky_build_for(kb_product)) : sky_build_for(kb_product);
+  const bool adaptive = win && win->accum2;
+  Build& kb = win ? window_build_for(kb_product, adaptive) : kb_product;
+  Build& kb2 = win ? window_build_for(sky_build_for(kb_product), adaptive) : sky_build_for(kb_product);
   if (win && (!(kb.traits() & 4) || !(kb2.traits() & 4)))
     return fail(DT_E_INVALID, "the trace-kernel build has no window mode");
+  if (win && (bool)(kb.traits() & 8) != adaptive)
+    return fail(DT_E_INVALID, "the trace-kernel build does not match the window launch (adaptive or plain)");
   // the build must handle every feature of the scene: its DT_FEATURES compile the others out to
   // __builtin_unreachable() (tests/test_host.py checks every builder scene; this guards the rest)
   if (sc->features & ~build_features(kb))
@@ -944,6 +1007,31 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
   P.chunk_lo = win ? win->chunk_lo : 0;
   P.chunk_hi = win ? win->chunk_hi : 0;
   hs.accum = win ? win->accum : nullptr;
+  if (adaptive) {
+    if ((double)P.n_items >= 4294967296.0) return fail(DT_E_INVALID, "adaptive window: more than 2^32 items");
+    if (P.n_items > sc->adapt_cap) {
+      HIPCHK(hipStreamSynchronize(st));
+      if (sc->d_adapt) (void)hipFree(sc->d_adapt);
+      sc->d_adapt = nullptr;
+      sc->adapt_cap = -1;
+      HIPCHK(hipMalloc((void**)&sc->d_adapt, adapt_layout(P.n_items).bytes));
+      sc->adapt_cap = P.n_items;
+    }
+    if (!sc->ev_sel) HIPCHK(hipEventCreate(&sc->ev_sel));
+    // (the offsets of the items of this launch: a smaller launch uses the head of a larger buffer)
+    const AdaptLayout L = adapt_layout(P.n_items);
+    P.adapt_begin = win->begin;
+    P.adapt_end = win->end;
+    P.adapt_min = win->min_samples;
+    P.adapt_thr2 = win->thr2;
+    P.act_waves = (int32_t)L.waves;
+    P.accum2 = win->accum2;
+    P.count = win->count;
+    P.act_n = (uint32_t*)sc->d_adapt;
+    P.act_list = (uint32_t*)(sc->d_adapt + L.list);
+    P.act_off = (uint32_t*)(sc->d_adapt + L.off);
+    P.act_mask = (unsigned long long*)(sc->d_adapt + L.mask);
+  }
   if (chunk_items) {
     const int64_t n_cols = P.n_items * (int64_t)P.spp * 3;
     if (n_cols > sc->chunk_cols_cap) {
@@ -1137,6 +1225,13 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
   HIPCHK(hipEventRecord(sc->ev_copy, st));
   sc->copy_pending = true;
   HIPCHK(hipEventRecord(sc->ev0, st));
+  if (adaptive) {
+    // the selection writes the list this launch's queue runs over and its length, read by the trace
+    // kernel as the sky-item launch reads *again_n: stream order, no host synchronisation
+    if (P.n_items > 0) HIPCHK(dt_launch_adapt_select(d_rec, P.n_items, st));
+    else HIPCHK(hipMemsetAsync(sc->d_adapt, 0, sizeof(uint32_t), st));
+    HIPCHK(hipEventRecord(sc->ev_sel, st));
+  }
   HIPCHK(kb.launch(d_rec, out_dev, (int)grid, st));
   sc->last_parity = par;
   sc->n_launch++;
@@ -1157,6 +1252,7 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
   sc->launched = true;
   sc->last = P;
   sc->last_px_samples = win ? win->samples : P.spp;
+  sc->last_adaptive = adaptive;
   return DT_OK;
 }
 
@@ -1200,6 +1296,12 @@ int dt_collect_stats(const dt_scene* sc_c, void* stream, dt_stats* stats)
       hh = hh < P.th ? hh : P.th;
       px += (int64_t)w * hh;
     }
+  }
+  // an adaptive window launch of one-pixel items (spp >= 64): the pixels it traced are the selection's list
+  if (sc->last_adaptive && P.spp >= 64) {
+    uint32_t n_act = 0;
+    HIPCHK(hipMemcpy(&n_act, sc->d_adapt, sizeof(n_act), hipMemcpyDeviceToHost));
+    px = n_act;
   }
   stats->pixels = px;
   stats->samples = (uint64_t)px * sc->last_px_samples;   // (a window launch: the window's samples)
@@ -1375,6 +1477,114 @@ int dt_resolve(const dt_globals* g, const dt_tiles* tiles, const double* accum, 
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   (void)hipFree(d_nan);
   if (e != hipSuccess) return fail(DT_E_NO_DEVICE, std::string("dt_resolve: ") + hipGetErrorString(e));
+  *nan_pixels = h_nan;
+  return DT_OK;
+}
+
+// ---- adaptive sampling: converged pixels stop between sample windows ------------------------------
+// No reference counterpart. Beside the accumulator the caller owns accum2 (the sums of squared sample
+// colours, the accumulator's length and indexing) and count (uint32 per pixel: the samples added so
+// far). A pixel is live at a window [begin, end) iff its count is begin; a selection on the device
+// lists the live pixels the rule of dt_adapt.h does not call converged, in ascending order, and the
+// window's trace launch runs its queue over that list. A pixel that never stops receives the chain of
+// f64 adds dt_render_window gives it.
+static int adapt_thr2(double tol, double* thr2)
+{
+  if (!std::isfinite(tol) || tol < 0) return fail(DT_E_INVALID, "adaptive: tol must be finite and >= 0");
+  *thr2 = (tol / 255.0) * (tol / 255.0);
+  return DT_OK;
+}
+
+int dt_adapt_converged(const double s1[3], const double s2[3], uint32_t count, double tol, int32_t min_samples)
+{
+  double thr2 = 0;
+  if (!s1 || !s2) return fail(DT_E_INVALID, "null argument");
+  if (int rc = adapt_thr2(tol, &thr2)) return rc;
+  return dtd::adapt_converged(s1, s2, count, thr2, min_samples) ? 1 : 0;
+}
+
+int dt_render_window_adaptive_async(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                                    int32_t begin, int32_t end, double* accum_device, double* accum2_device,
+                                    uint32_t* count_device, double tol, int32_t min_samples, void* stream)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  if (!sc) return fail(DT_E_INVALID, "null scene");
+  if (!g) return fail(DT_E_INVALID, "null argument");
+  if (!accum_device) return fail(DT_E_INVALID, "null accumulator");
+  if (!accum2_device) return fail(DT_E_INVALID, "null accum2");
+  if (!count_device) return fail(DT_E_INVALID, "null count");
+  Window w;
+  if (int rc = adapt_thr2(tol, &w.thr2)) return rc;
+  if (int rc = dt_window_check(g, begin, end)) return rc;
+  dtd::DParams P;
+  std::vector<float> zs;
+  int rc = prepare_render(sc, g, frame, tiles, P, zs);
+  if (rc) return rc;
+  w.chunk_lo = begin / 64;
+  w.chunk_hi = (end + 63) / 64;
+  w.samples = end - begin;
+  w.accum = accum_device;
+  w.accum2 = accum2_device;
+  w.count = count_device;
+  w.begin = begin;
+  w.end = end;
+  w.min_samples = min_samples;
+  return enqueue_render(sc, P, zs, nullptr, (hipStream_t)stream, &w);
+}
+
+int dt_render_window_adaptive(const dt_scene* sc, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                              int32_t begin, int32_t end, double* accum_device, double* accum2_device,
+                              uint32_t* count_device, double tol, int32_t min_samples, void* stream, dt_stats* stats)
+{
+  int rc = dt_render_window_adaptive_async(sc, g, frame, tiles, begin, end, accum_device, accum2_device, count_device,
+                                           tol, min_samples, stream);
+  if (rc == DT_OK) rc = dt_collect_stats(sc, stream, stats);
+  return rc;
+}
+
+int dt_adapt_select_ms(const dt_scene* sc, float* ms)
+{
+  if (!sc || !ms) return fail(DT_E_INVALID, "null argument");
+  if (!sc->last_adaptive || !sc->ev_sel) return fail(DT_E_INVALID, "the last launch was no adaptive window");
+  HIPCHK(hipEventSynchronize(sc->ev_sel));
+  HIPCHK(hipEventElapsedTime(ms, sc->ev0, sc->ev_sel));
+  return DT_OK;
+}
+
+int dt_resolve_adaptive(const dt_globals* g, const dt_tiles* tiles, const double* accum, const uint32_t* count,
+                        float* out, int32_t on_device, void* stream, uint64_t* nan_pixels)
+{
+  if (!g || !accum || !count || !out) return fail(DT_E_INVALID, "null argument");
+  const int64_t n = dt_accum_doubles(g, tiles);
+  if (n < 0) return fail(DT_E_INVALID, "invalid globals or tiles");
+  const int64_t n_px = n / 3;
+  if (!on_device) {
+    uint64_t n_nan = 0;
+    for (int64_t q = 0; q < n_px; ++q) {
+      // dt_resolve's loop with the pixel's own count; no samples: 0
+      double c[3] = {0, 0, 0};
+      if (count[q])
+        for (int k = 0; k < 3; ++k) c[k] = accum[3 * q + k] / (double)count[q];
+      for (int k = 0; k < 3; ++k) out[3 * q + k] = dtm::clampf01((float)c[k]) * 255.0f;
+      if (std::isnan(c[0]) || std::isnan(c[1]) || std::isnan(c[2])) ++n_nan;
+    }
+    if (nan_pixels) *nan_pixels = n_nan;
+    return DT_OK;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (!nan_pixels) {   // enqueue only
+    if (n_px > 0) HIPCHK(dt_launch_resolve_adaptive(accum, count, out, n_px, nullptr, st));
+    return DT_OK;
+  }
+  unsigned long long* d_nan = nullptr;
+  unsigned long long h_nan = 0;
+  HIPCHK(hipMalloc((void**)&d_nan, sizeof(unsigned long long)));
+  hipError_t e = hipMemsetAsync(d_nan, 0, sizeof(unsigned long long), st);
+  if (e == hipSuccess && n_px > 0) e = dt_launch_resolve_adaptive(accum, count, out, n_px, d_nan, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&h_nan, d_nan, sizeof(h_nan), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_nan);
+  if (e != hipSuccess) return fail(DT_E_NO_DEVICE, std::string("dt_resolve_adaptive: ") + hipGetErrorString(e));
   *nan_pixels = h_nan;
   return DT_OK;
 }

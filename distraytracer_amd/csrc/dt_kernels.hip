@@ -25,6 +25,7 @@
 #include "../../include/dt_work.h"
 #include "dt_math.h"
 #include "dt_scene_dev.h"
+#include "dt_adapt.h"
 
 using namespace dtm;
 using namespace dtd;
@@ -158,7 +159,18 @@ using namespace dtd;
 #endif
 #define DT_CAT2(a, b) a##b
 #define DT_CAT(a, b) DT_CAT2(a, b)
-#if DT_WINDOW
+// DT_WINDOW=2 (build/awin_*.o, named <kernel>_awin): the window builds once more with adaptive
+// sampling (DT_ADAPT) for dt_render_window_adaptive: a second set of sums (the squared sample colours,
+// P.accum2), the per-pixel sample count, and the first launch's queue running over the selection's
+// list (P.act_list). Builds of their own: with the code as runtime branches of the *_win builds,
+// those spilled 32 more VGPRs and a plain C4 window ran 0.95% slower, ten times the spread of the
+// runs; so the *_win objects stay the same bytes.
+#define DT_ADAPT (DT_WINDOW == 2)
+#if DT_ADAPT
+#define DT_TRACE_KERNEL DT_CAT(DT_TRACE_KERNEL_BASE, _awin)
+#undef DT_HELPERS
+#define DT_HELPERS 0
+#elif DT_WINDOW
 #define DT_TRACE_KERNEL DT_CAT(DT_TRACE_KERNEL_BASE, _win)
 #undef DT_HELPERS
 #define DT_HELPERS 0
@@ -3284,6 +3296,13 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
   __shared__ double ocol[3][DT_WAVE];
   // DT_PSUM_LDS=2: slots for up to 8 pixels per wave only (spp >= 8; 192 B instead of 1536 B)
   __shared__ double psum[3][DT_PSUM_LDS == 2 ? 8 : DT_WAVE];
+#if DT_ADAPT
+  // the pixel's sums of squared sample colours, psum's twin
+  __shared__ double psum2[3][DT_PSUM_LDS == 2 ? 8 : DT_WAVE];
+  // the first launch runs its queue over the selection's list (dt_adapt_*_kernel), as the sky-item
+  // launch runs over again_list (which then holds item indices taken from this list)
+  const bool act_queue = P.sky_again != 2;
+#endif
   __shared__ double chan[4];
   __shared__ double tcol[3][DT_WAVE];   // the lit lights' colour sum of the node being shaded
   __shared__ unsigned long long item_s;
@@ -3334,13 +3353,23 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
   // behind one another on the one atomic word; the shared counter hands out the items after them.
   const int batch = P.item_batch > 1 ? P.item_batch : 1;
   // P.sky_again == 2: the queue runs over the items a launch without the sky listed
+#if DT_ADAPT
+  const int64_t n_queue = act_queue ? (int64_t)*P.act_n
+                          : DT_AGAIN_QUEUE && P.sky_again == 2 ? (int64_t)*S.again_n
+                                                               : P.n_items * (DT_CHUNK_ITEMS && P.chunk_items ? P.chunks : 1);
+#else
   const int64_t n_queue = DT_AGAIN_QUEUE && P.sky_again == 2 ? (int64_t)*S.again_n
                                                              : P.n_items * (DT_CHUNK_ITEMS && P.chunk_items ? P.chunks : 1);
+#endif
   // P.queue_segs > 1: the queue in that many contiguous segments with a counter each; wave b starts
   // in segment b % segs (workgroups go round-robin to the XCDs) and takes its first batch there by
   // block index, then from the segment's counter; a drained segment sends the wave to the next one,
   // and the wave ends once it has found every segment drained in turn (counters only grow)
+#if DT_ADAPT
+  const int segs = act_queue || (DT_AGAIN_QUEUE && P.sky_again == 2) || P.queue_segs < 2 ? 1 : P.queue_segs;
+#else
   const int segs = (DT_AGAIN_QUEUE && P.sky_again == 2) || P.queue_segs < 2 ? 1 : P.queue_segs;
+#endif
   const int64_t seg_len = (n_queue + segs - 1) / segs;
   int seg = (int)(blockIdx.x % (unsigned)segs), seg_fails = 0;
   int64_t seg_lo = seg * seg_len, seg_hi = seg_lo + seg_len < n_queue ? seg_lo + seg_len : n_queue;
@@ -3373,7 +3402,12 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
       if (drained) break;
     }
     if (qpos >= n_queue) break;
+#if DT_ADAPT
+    const int64_t code = act_queue ? (int64_t)P.act_list[qpos]
+                         : DT_AGAIN_QUEUE && P.sky_again == 2 ? (int64_t)S.again_list[qpos] : qpos;
+#else
     const int64_t code = DT_AGAIN_QUEUE && P.sky_again == 2 ? (int64_t)S.again_list[qpos] : qpos;
+#endif
     int64_t item = code;
     float* const outc = out;
     // P.chunk_items: the item is one 64-sample chunk of a pixel item (a listed sky item likewise)
@@ -3413,6 +3447,11 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
     if (DT_PSUM_LDS == 1 || lane < 8) {   // pixel j's sums, in sample order
       psum[0][lane] = 0; psum[1][lane] = 0; psum[2][lane] = 0;
     }
+#if DT_ADAPT
+    if (DT_PSUM_LDS == 1 || lane < 8) {
+      psum2[0][lane] = 0; psum2[1][lane] = 0; psum2[2][lane] = 0;
+    }
+#endif
 #if DT_WINDOW
     // the sums go on from the pixel's accumulator values: the samples below chunk_lo, added by the
     // earlier windows (the epilogue's lane and offset)
@@ -3424,6 +3463,12 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
       if (qv) {
         const double* const acc = S.accum + (P.layout == DT_OUT_SLAB ? qo : 3 * ((int64_t)(P.yRes - 1 - qy) * P.xRes + qx));
         psum[0][lane] = acc[0]; psum[1][lane] = acc[1]; psum[2][lane] = acc[2];
+#if DT_ADAPT
+        {   // the second set of sums goes on from accum2 likewise
+          const double* const acc2 = P.accum2 + (acc - S.accum);
+          psum2[0][lane] = acc2[0]; psum2[1][lane] = acc2[1]; psum2[2][lane] = acc2[2];
+        }
+#endif
       }
     }
 #endif
@@ -3550,13 +3595,34 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
           if (lane < group * 3) {
             const int jj = lane / 3, ch = lane - 3 * jj, base = jj * per;
             double ps = psum[ch][jj];
+#if DT_ADAPT
+            // the same lanes, the same loop: one product and one add per sample more
+            double ps2 = psum2[ch][jj];
+            for (int s = 0; s < ns; ++s) {
+              const double r = red[(base + s) * 3 + ch];
+              ps = ps + r;
+              ps2 = ps2 + r * r;
+            }
+            psum2[ch][jj] = ps2;
+#else
             for (int s = 0; s < ns; ++s) ps = ps + red[(base + s) * 3 + ch];
+#endif
             psum[ch][jj] = ps;
           }
         } else if (lane < group) {   // (up to 64 pixels per wave: 1 or 2 spp)
           const int base = lane * per;
           V3 ps = v3(psum[0][lane], psum[1][lane], psum[2][lane]);
+#if DT_ADAPT
+          V3 ps2 = v3(psum2[0][lane], psum2[1][lane], psum2[2][lane]);
+          for (int s = 0; s < ns; ++s) {
+            const V3 r = v3(red[(base + s) * 3], red[(base + s) * 3 + 1], red[(base + s) * 3 + 2]);
+            ps = add(ps, r);
+            ps2 = add(ps2, v3(r.x * r.x, r.y * r.y, r.z * r.z));
+          }
+          psum2[0][lane] = ps2.x; psum2[1][lane] = ps2.y; psum2[2][lane] = ps2.z;
+#else
           for (int s = 0; s < ns; ++s) ps = add(ps, v3(red[(base + s) * 3], red[(base + s) * 3 + 1], red[(base + s) * 3 + 2]));
+#endif
           psum[0][lane] = ps.x; psum[1][lane] = ps.y; psum[2][lane] = ps.z;
         }
         __syncthreads();
@@ -3576,6 +3642,14 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
       if (qv && !item_again) {
         double* const acc = S.accum + (P.layout == DT_OUT_SLAB ? qo : 3 * ((int64_t)(P.yRes - 1 - qy) * P.xRes + qx));
         acc[0] = psum[0][lane]; acc[1] = psum[1][lane]; acc[2] = psum[2][lane];
+#if DT_ADAPT
+        {   // both sets of sums, and the pixel's sample count: the window's end
+          const int64_t aoff = acc - S.accum;
+          double* const acc2 = P.accum2 + aoff;
+          acc2[0] = psum2[0][lane]; acc2[1] = psum2[1][lane]; acc2[2] = psum2[2][lane];
+          P.count[aoff / 3] = (uint32_t)P.adapt_end;
+        }
+#endif
       }
 #else
       if (qv && !item_again && !(P.sky_defer && S.sky_miss[item * group + lane])) {
@@ -3749,6 +3823,122 @@ dt_resolve_kernel(const double* __restrict__ accum, float* __restrict__ out, int
   if ((threadIdx.x & 63) == 0 && n_nan && nan_px) atomicAdd(nan_px, n_nan);
 }
 
+// dt_resolve_adaptive: dt_resolve_kernel with every pixel divided by its own sample count (count[q]
+// for the doubles 3q..3q+2); a pixel without samples resolves to 0.
+extern "C" __global__ void __launch_bounds__(256)
+dt_resolve_adaptive_kernel(const double* __restrict__ accum, const uint32_t* __restrict__ count,
+                           float* __restrict__ out, int64_t n_px, unsigned long long* __restrict__ nan_px)
+{
+  unsigned long long n_nan = 0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n_px; base += stride) {
+    const int64_t q = base + threadIdx.x;
+    bool nan = false;
+    if (q < n_px) {
+      const uint32_t n = count[q];
+      V3 color = v3(0, 0, 0);
+      if (n) color = divs(v3(accum[3 * q], accum[3 * q + 1], accum[3 * q + 2]), (double)n);
+      out[3 * q + 0] = clampf01((float)color.x) * 255.0f;
+      out[3 * q + 1] = clampf01((float)color.y) * 255.0f;
+      out[3 * q + 2] = clampf01((float)color.z) * 255.0f;
+      nan = isnan(color.x) || isnan(color.y) || isnan(color.z);
+    }
+    n_nan += __popcll(__ballot(nan));
+  }
+  if ((threadIdx.x & 63) == 0 && n_nan && nan_px) atomicAdd(nan_px, n_nan);
+}
+
+// ---- adaptive sampling: the selection of a window's items (dt_render_window_adaptive) -------------
+// Three small kernels in front of the trace launch write P.act_list, the items it runs, in ascending
+// order: the order makes launches reproducible and keeps neighbouring pixels neighbours in the queue
+// (the scalar-cache locality of the tree walks). A per-wave count, an exclusive scan and a scatter:
+// the selection is memory-bound (52 B per pixel read once, 12 B per 64 items of scratch), so three
+// streaming launches cost less than the cross-block look-back of a single pass would save.
+//
+// (1) one item per lane: keep iff the item's pixel is live (count == P.adapt_begin) and the rule of
+// dt_adapt.h does not say it has converged. The wave's keep bits and their number go to act_mask /
+// act_off (P.act_waves words each: the grid's waves). With spp < 64 an item is several pixels and
+// the only window is the whole frame: every item is kept.
+extern "C" __global__ void __launch_bounds__(256)
+dt_adapt_flag_kernel(const DLaunch* __restrict__ Lp)
+{
+  const DParams& P = Lp->P;
+  const DScene& S = Lp->S;
+  const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool keep = false;
+  if (item < P.n_items) {
+    if (P.spp < DT_WAVE) {
+      keep = true;
+    } else {   // one item is one pixel
+      int x, y;
+      int64_t so;
+      bool valid;
+      pixel_of(P, item, x, y, so, valid);
+      if (valid) {
+        const int64_t off = P.layout == DT_OUT_SLAB ? so : 3 * ((int64_t)(P.yRes - 1 - y) * P.xRes + x);
+        const uint32_t n = P.count[off / 3];
+        if (n == (uint32_t)P.adapt_begin) {
+          const double s1[3] = {S.accum[off], S.accum[off + 1], S.accum[off + 2]};
+          const double s2[3] = {P.accum2[off], P.accum2[off + 1], P.accum2[off + 2]};
+          keep = !adapt_converged(s1, s2, n, P.adapt_thr2, P.adapt_min);
+        }
+      }
+    }
+  }
+  const unsigned long long m = __ballot(keep);
+  const int64_t w = item >> 6;   // (256-thread blocks: a wave's items share item >> 6)
+  if ((threadIdx.x & 63) == 0 && w < P.act_waves) {
+    P.act_mask[w] = m;
+    P.act_off[w] = (uint32_t)__popcll(m);
+  }
+}
+
+// (2) one block: act_off's counts to their exclusive scan in place, the total to *P.act_n. Thread t
+// takes a contiguous run of the words; the runs' sums are scanned per wave with shuffles and across
+// the block's 16 waves through LDS.
+extern "C" __global__ void __launch_bounds__(1024)
+dt_adapt_scan_kernel(const DLaunch* __restrict__ Lp)
+{
+  const DParams& P = Lp->P;
+  __shared__ uint32_t wave_sum[16];
+  const int t = (int)threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int64_t n = P.act_waves;
+  const int64_t per = (n + 1023) / 1024;
+  const int64_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+  uint32_t sum = 0;
+  for (int64_t i = lo; i < hi; ++i) sum += P.act_off[i];
+  uint32_t inc = sum;
+  for (int d = 1; d < DT_WAVE; d <<= 1) {
+    const uint32_t up = __shfl_up(inc, d);
+    if (lane >= d) inc += up;
+  }
+  if (lane == DT_WAVE - 1) wave_sum[wv] = inc;
+  __syncthreads();
+  uint32_t run = inc - sum;
+  for (int k = 0; k < wv; ++k) run += wave_sum[k];
+  for (int64_t i = lo; i < hi; ++i) {
+    const uint32_t c = P.act_off[i];
+    P.act_off[i] = run;
+    run += c;
+  }
+  if (t == 1023) *P.act_n = run;
+}
+
+// (3) one item per lane again: a kept item goes to act_list at its wave's offset plus the kept
+// items below it in the wave
+extern "C" __global__ void __launch_bounds__(256)
+dt_adapt_scatter_kernel(const DLaunch* __restrict__ Lp)
+{
+  const DParams& P = Lp->P;
+  const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t w = item >> 6;
+  const int lane = (int)(threadIdx.x & 63);
+  if (w >= P.act_waves || item >= P.n_items) return;
+  const unsigned long long m = P.act_mask[w];
+  if ((m >> lane) & 1ull)
+    P.act_list[P.act_off[w] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)item;
+}
+
 // renderImageCloud (cpp:1224-1279): one pixel per lane
 extern "C" __global__ void __launch_bounds__(256)
 dt_sky_kernel(const DLaunch* __restrict__ Lp, float* __restrict__ out)
@@ -3848,6 +4038,25 @@ extern "C" hipError_t dt_launch_resolve(const double* accum, float* out, int64_t
   hipLaunchKernelGGL(dt_resolve_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, accum, out, n_px, n_samples, nan_px);
   return hipGetLastError();
 }
+extern "C" hipError_t dt_launch_resolve_adaptive(const double* accum, const uint32_t* count, float* out, int64_t n_px,
+                                                 unsigned long long* nan_px, hipStream_t stream)
+{
+  int64_t blocks = (n_px + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(dt_resolve_adaptive_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, accum, count, out, n_px,
+                     nan_px);
+  return hipGetLastError();
+}
+// the selection in front of an adaptive window launch: n_items > 0; P.act_waves = 4 * blocks
+extern "C" int64_t dt_adapt_select_blocks(int64_t n_items) { return (n_items + 255) / 256; }
+extern "C" hipError_t dt_launch_adapt_select(const void* dev_launch, int64_t n_items, hipStream_t stream)
+{
+  const unsigned blocks = (unsigned)dt_adapt_select_blocks(n_items);
+  hipLaunchKernelGGL(dt_adapt_flag_kernel, dim3(blocks), dim3(256), 0, stream, (const DLaunch*)dev_launch);
+  hipLaunchKernelGGL(dt_adapt_scan_kernel, dim3(1), dim3(1024), 0, stream, (const DLaunch*)dev_launch);
+  hipLaunchKernelGGL(dt_adapt_scatter_kernel, dim3(blocks), dim3(256), 0, stream, (const DLaunch*)dev_launch);
+  return hipGetLastError();
+}
 extern "C" hipError_t dt_launch_sky(const void* dev_launch, float* out, int64_t n_threads, hipStream_t stream)
 {
   int64_t blocks = (n_threads + 255) / 256;
@@ -3877,11 +4086,12 @@ extern "C" hipError_t DT_CAT(DT_TRACE_KERNEL, _launch)(const void* dev_launch, f
 }
 extern "C" const void* DT_CAT(DT_TRACE_KERNEL, _ptr)(void) { return (const void*)DT_TRACE_KERNEL; }
 // bit 0: the build lists sky items for another launch (DT_SKY_AGAIN); bit 1: it runs chunk items
-// (DT_CHUNK_ITEMS); bit 2: it runs window launches (DT_WINDOW); bits 8..23: the scene features
+// (DT_CHUNK_ITEMS); bit 2: it runs window launches (DT_WINDOW); bit 3: adaptive ones (DT_ADAPT);
+// bits 8..23: the scene features
 // it handles (DT_FEATURES; dt_api.cpp launches it only for scenes within them)
 extern "C" int DT_CAT(DT_TRACE_KERNEL, _traits)(void)
 {
-  return (DT_SKY_AGAIN ? 1 : 0) | (DT_CHUNK_ITEMS ? 2 : 0) | (DT_WINDOW ? 4 : 0) | (int)(((DT_FEATURES) & 0xFFFFu) << 8);
+  return (DT_SKY_AGAIN ? 1 : 0) | (DT_CHUNK_ITEMS ? 2 : 0) | (DT_WINDOW ? 4 : 0) | (DT_ADAPT ? 8 : 0) | (int)(((DT_FEATURES) & 0xFFFFu) << 8);
 }
 #endif
 #endif   // !DT_REPRO

@@ -204,6 +204,24 @@ struct DParams {
   // the chunks [chunk_lo, chunk_hi) of every pixel item, starting each pixel's sums from its
   // accumulator values (DScene::accum) and storing them back instead of a pixel. 0, 0: no window
   int32_t chunk_lo, chunk_hi;
+  // adaptive window launches (dt_render_window_adaptive; runtime branches of the *_win builds on
+  // accum2 != nullptr, and the selection kernels). Appended here, after every field a product build
+  // reads, so that no existing offset of the launch record moves. All null / 0 otherwise.
+  // accum2: the sums of squared sample colours, indexed like DScene::accum; count: samples added per
+  // pixel, entry q for the doubles 3q..3q+2. A pixel is live in the window iff count == adapt_begin;
+  // the epilogue stores adapt_end. act_list[0 .. *act_n): the items of this launch in ascending
+  // order (the queue runs over it); act_mask / act_off: one word per 64 items (act_waves of them),
+  // the selection's keep bits and their exclusive scan.
+  int32_t adapt_begin, adapt_end;
+  int32_t adapt_min;      // min_samples
+  int32_t act_waves;
+  double adapt_thr2;      // (tol / 255)^2
+  double* accum2;
+  uint32_t* count;
+  uint32_t* act_list;
+  uint32_t* act_n;
+  unsigned long long* act_mask;
+  uint32_t* act_off;
 };
 
 #ifndef DT_HD

@@ -16,6 +16,10 @@
 //                     accumulator on the device; after every window the output file is overwritten
 //                     with the resolved preview (the mean of the samples so far) and samples_done/spp
 //                     is printed. The final file is byte-identical to the run without the flag.
+//   --adaptive TOL    adaptive sampling (dt_render_window_adaptive): one-chunk windows in which pixels
+//                     whose mean has a standard error of at most TOL grey levels stop. --min-samples N:
+//                     no pixel stops with fewer (default 64). --counts FILE: samples taken / spp per
+//                     pixel as a grey PNG. Prints the share of pixels * spp that was taken.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -42,7 +46,9 @@ int main(int argc, char** argv)
   int arg = (argc > 2 && argv[2][0] != '-') ? atoi(argv[2]) : 0;
   std::string out;
   std::string data_dir = DT_DATA_DIR;
-  int spp = -1, depth = -1, W = -1, H = -1, progressive = 0;
+  int spp = -1, depth = -1, W = -1, H = -1, progressive = 0, min_samples = 64;
+  double adaptive = -1.0;
+  std::string counts_file;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     if (a == "--out" && i + 1 < argc) out = argv[++i];
@@ -52,6 +58,9 @@ int main(int argc, char** argv)
     else if (a == "--data" && i + 1 < argc) data_dir = argv[++i];
     else if (a == "--res" && i + 1 < argc) sscanf(argv[++i], "%dx%d", &W, &H);
     else if (a == "--progressive" && i + 1 < argc) progressive = atoi(argv[++i]);
+    else if (a == "--adaptive" && i + 1 < argc) adaptive = atof(argv[++i]);
+    else if (a == "--min-samples" && i + 1 < argc) min_samples = atoi(argv[++i]);
+    else if (a == "--counts" && i + 1 < argc) counts_file = argv[++i];
   }
   std::string scene = "final";
   float build_frame = 0;
@@ -111,7 +120,59 @@ int main(int argc, char** argv)
   dt_stats st;
   std::string fn = out.empty() ? std::string(buf) : out;
   const bool png = fn.size() > 4 && fn.compare(fn.size() - 4, 4, ".png") == 0;
-  if (progressive > 0) {
+  if (adaptive >= 0.0) {
+    // one-chunk windows over the live, unconverged pixels until a window traces none or all samples
+    // are rendered; every pixel resolved with its own count
+    const int n = (int)sqrt((double)g.antialias_samples), total = n * n;
+    const int64_t n_acc = dt_accum_doubles(&g, nullptr), n_px = n_acc / 3;
+    double *acc = nullptr, *acc2 = nullptr;
+    uint32_t* cnt = nullptr;
+    float* dimg = nullptr;
+    if (hipMalloc((void**)&acc, n_acc * sizeof(double)) != hipSuccess || hipMalloc((void**)&acc2, n_acc * sizeof(double)) != hipSuccess ||
+        hipMalloc((void**)&cnt, n_px * sizeof(uint32_t)) != hipSuccess || hipMalloc((void**)&dimg, n_acc * sizeof(float)) != hipSuccess ||
+        hipMemset(acc, 0, n_acc * sizeof(double)) != hipSuccess || hipMemset(acc2, 0, n_acc * sizeof(double)) != hipSuccess ||
+        hipMemset(cnt, 0, n_px * sizeof(uint32_t)) != hipSuccess) {
+      fprintf(stderr, "adaptive buffers: hipMalloc failed\n");
+      return 1;
+    }
+    dt_stats sum;
+    memset(&sum, 0, sizeof sum);
+    for (int begin = 0; begin < total;) {
+      const int end = total < 64 || begin + 64 > total ? total : begin + 64;
+      rc = dt_render_window_adaptive(s, &g, frame, nullptr, begin, end, acc, acc2, cnt, adaptive, min_samples, nullptr, &st);
+      if (rc) return die("dt_render_window_adaptive", rc);
+      sum.samples += st.samples;
+      sum.kernel_ms += st.kernel_ms;
+      printf("%d/%d: %llu pixels\n", end, total, (unsigned long long)st.pixels);
+      fflush(stdout);
+      begin = end;
+      if (st.pixels == 0) break;
+    }
+    rc = dt_resolve_adaptive(&g, nullptr, acc, cnt, dimg, 1, nullptr, nullptr);
+    if (rc) return die("dt_resolve_adaptive", rc);
+    std::vector<uint32_t> hcnt((size_t)n_px);
+    if (hipMemcpy(img.data(), dimg, n_acc * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(hcnt.data(), cnt, n_px * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+      fprintf(stderr, "adaptive: hipMemcpy failed\n");
+      return 1;
+    }
+    rc = png ? dt_write_png(fn.c_str(), g.xRes, g.yRes, img.data()) : dt_write_ppm(fn.c_str(), g.xRes, g.yRes, img.data());
+    if (rc) return die("dt_write_ppm/png", rc);
+    if (!counts_file.empty()) {   // count / spp as grey, in the image's pixel order
+      std::vector<float> cimg((size_t)n_acc);
+      for (int64_t q = 0; q < n_px; ++q)
+        for (int k = 0; k < 3; ++k) cimg[3 * q + k] = 255.0f * (float)hcnt[q] / (float)total;
+      rc = dt_write_png(counts_file.c_str(), g.xRes, g.yRes, cimg.data());
+      if (rc) return die("dt_write_png (counts)", rc);
+    }
+    printf("adaptive tol %g: %.2f%% of %lld pixels x %d spp taken\n", adaptive,
+           100.0 * (double)sum.samples / ((double)n_px * total), (long long)n_px, total);
+    (void)hipFree(acc);
+    (void)hipFree(acc2);
+    (void)hipFree(cnt);
+    (void)hipFree(dimg);
+    st = sum;
+  } else if (progressive > 0) {
     // windows of `progressive` chunks in ascending order onto a zeroed accumulator; every window's
     // preview (dt_resolve with the samples so far) overwrites the file, the last one is the frame
     const int n = (int)sqrt((double)g.antialias_samples), total = n * n;

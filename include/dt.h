@@ -47,6 +47,8 @@ extern "C" {
 /* 8: dt_render_repeat_async removed (a measurement stand-in with no product caller) */
 /* (still 8, new exports only, no struct changed: dt_accum_doubles, dt_window_check, dt_render_window,
  *    dt_render_window_async, dt_resolve -- progressive rendering) */
+/* (still 8, new exports only, no struct changed: dt_adapt_converged, dt_render_window_adaptive,
+ *    dt_render_window_adaptive_async, dt_resolve_adaptive, dt_adapt_select_ms -- adaptive sampling) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -387,6 +389,43 @@ int dt_render_window_async(const dt_scene* s, const dt_globals* g, int32_t frame
  * device the call is synchronous when it is asked for and only enqueues otherwise. */
 int dt_resolve(const dt_globals* g, const dt_tiles* tiles, const double* accum, int32_t n_samples,
                float* out, int32_t on_device, void* stream, uint64_t* nan_pixels);
+
+/* ---- adaptive sampling: converged pixels stop between sample windows ----
+ * No reference counterpart. Beside the accumulator the caller owns two more device buffers:
+ *   accum2: dt_accum_doubles doubles, indexed like the accumulator; element i is the left-to-right
+ *           f64 sum of c*c over the sample colours c whose sum is accum[i];
+ *   count:  uint32, dt_accum_doubles / 3 entries; entry q (the pixel of accum[3q..3q+2]) is the
+ *           number of samples added to that pixel so far.
+ * 52 bytes per pixel in all, zeroed before the first window. A pixel is LIVE at a window
+ * [begin, end) iff count[q] == begin: there is no other state. A live pixel is traced unless it has
+ * converged. With n = (double)count, per channel c:
+ *   d = S2[c] - (S1[c] * S1[c]) / n;   v = d / (n * (n - 1.0));      (variance of the mean)
+ *   converged iff v <= thr2 for all three channels, thr2 = (tol / 255.0) * (tol / 255.0),
+ * and only when count >= min_samples and count >= 64. tol: the standard error allowed, in grey
+ * levels of the 0..255 output, finite and >= 0. The comparisons are <=: a NaN sum never converges, a
+ * d that rounding makes slightly negative does. min_samples >= spp: nothing ever stops.
+ * dt_adapt_converged: the rule on host values, 1 or 0 (DT_E_INVALID for a bad tol). */
+int dt_adapt_converged(const double s1[3], const double s2[3], uint32_t count, double tol, int32_t min_samples);
+/* dt_render_window over the live, unconverged pixels only: a selection on the device lists them in
+ * ascending item order and the window's trace launch runs over that list; each traced pixel gets its
+ * samples added to accum and accum2 and count[q] = end. Windows as dt_window_check; with spp < 64
+ * the one window traces every pixel. stats.pixels: the pixels traced in this window,
+ * stats.samples = pixels * (end - begin), rays etc. of those samples. A pixel that is never stopped
+ * receives dt_render_window's chain of adds: its accumulator bits are the one-shot render's.
+ * A null scene or buffer, a bad tol or a bad window: DT_E_INVALID before any device work. */
+int dt_render_window_adaptive(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                              int32_t begin, int32_t end, double* accum_device, double* accum2_device,
+                              uint32_t* count_device, double tol, int32_t min_samples, void* stream,
+                              dt_stats* stats);
+int dt_render_window_adaptive_async(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                                    int32_t begin, int32_t end, double* accum_device, double* accum2_device,
+                                    uint32_t* count_device, double tol, int32_t min_samples, void* stream);
+/* dt_resolve with every pixel divided by its own count:
+ * out[3q+k] = clamp01((float)(accum[3q+k] / count[q])) * 255.0f, 0 where count[q] == 0. */
+int dt_resolve_adaptive(const dt_globals* g, const dt_tiles* tiles, const double* accum, const uint32_t* count,
+                        float* out, int32_t on_device, void* stream, uint64_t* nan_pixels);
+/* the device time of the selection kernels of the scene's last adaptive window launch (waits for them) */
+int dt_adapt_select_ms(const dt_scene* s, float* ms);
 
 /* diagnostic builds (-DDT_STAMPS): per-phase cycle sums of the last render; zeros otherwise */
 int dt_debug_counters(const dt_scene* s, uint64_t* out, int32_t n);
