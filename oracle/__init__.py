@@ -2,7 +2,10 @@
 reference-compiled harness (oracle/_ref/libref_noise.so). Imported only by tests/,
 __graft_entry__.smoke() and bench.py's cpu_baseline leg; never by distraytracer_amd/.
 The struct layouts come from the C-ABI header mirror (distraytracer_amd._lib), since the
-oracle consumes the same dt_scene_desc / dt_globals the device path does."""
+oracle consumes the same dt_scene_desc / dt_globals the device path does.
+The geometry.cpp parity vectors have a module of their own, oracle/geom.py: the bindings of the
+oracle's test-only or_shape_* / or_box_intersect / or_primary_ray exports and of the reference-compiled
+oracle/_ref/libref_geom.so, what is drawn and how answers compare."""
 import ctypes
 import os
 

@@ -1958,18 +1958,45 @@ int or_sample_color(const dt_scene_desc* d, const dt_globals* g, int frame, int 
   return rc;
 }
 
+/* Primary ray r of the intersection micro-benchmark (include/dt.h dt_intersect_primary): q = r / 8, pixel
+ * q mod W*H, sample r mod 8 + 8 (q div W*H); the camera ray of render_sample (getDOFSamples +
+ * getPerspEyeRay, cpp:195-210, 1062-1072). c receives the sample's RNG state. */
+static void primary_ray(const RenderCtx* R, const dt_globals* g, int frame, long long r, Ctx* c, V3* eye_sample,
+                        V3* ray)
+{
+  const long long npx = (long long)g->xRes * g->yRes;
+  const long long q = r / 8, p = q % npx;
+  const int x = (int)(p % g->xRes), y = (int)(p / g->xRes);
+  const Cam* cam = &R->cam;
+  c->s = &R->scene;
+  c->st = NULL;
+  c->wk = NULL;
+  c->shift = 0.0f;
+  c->rng.key[0] = g->seed;
+  c->rng.key[1] = (uint32_t)frame;
+  c->rng.pixel = (uint32_t)(y * g->xRes + x);
+  c->rng.sample = (uint32_t)(r % 8 + 8 * (q / npx));
+  *eye_sample = cam->eye;
+  if (g->aperture > 0) {
+    double u0, u1;
+    rng2(&c->rng, 0, P_DOF, 0, &u0, &u1);
+    float rr = (float)(g->aperture / 2 * u0);
+    float theta = (float)(2 * M_PI * u1);
+    *eye_sample = add(add(cam->eye, mul(rr * cr_cosf(theta), cam->X)), mul(rr * cr_sinf(theta), cam->Y));
+  }
+  V3 focalPoint = add(cam->eye, mul(g->focal_length, persp_eye_ray(g, cam, x, y)));
+  *ray = sub(focalPoint, *eye_sample);
+}
+
 /* The intersection micro-benchmark's reference (include/dt.h dt_intersect_primary): for primary rays
- * first .. first+n-1 (ray r: q = r / 8, pixel q mod W*H, sample r mod 8 + 8 (q div W*H)), the
- * camera ray of render_sample (getDOFSamples + getPerspEyeRay, cpp:195-210, 1062-1072) and
- * rayColor's gather + closest hit (cpp:491-538, ray_color above): the closest shape (-1: none)
- * and its t (FLT_MAX: none). */
+ * first .. first+n-1 (primary_ray above), rayColor's gather + closest hit (cpp:491-538, ray_color
+ * above): the closest shape (-1: none) and its t (FLT_MAX: none). */
 int or_primary_hit(const dt_scene_desc* d, const dt_globals* g, int frame, long long first, long long n,
                    int* shape, float* t, int nthreads)
 {
   RenderCtx R;
   int rc = render_setup(&R, d, g, frame);
   if (rc != DT_OK) { scene_free(&R.scene); return rc; }
-  const long long npx = (long long)g->xRes * g->yRes;
 #ifdef _OPENMP
   if (nthreads > 0) omp_set_num_threads(nthreads);
 #pragma omp parallel
@@ -1980,28 +2007,9 @@ int or_primary_hit(const dt_scene_desc* d, const dt_globals* g, int frame, long 
 #pragma omp for schedule(dynamic, 256)
 #endif
     for (long long i = 0; i < n; ++i) {
-      const long long r = first + i, q = r / 8, p = q % npx;
-      const int x = (int)(p % g->xRes), y = (int)(p / g->xRes);
-      const Cam* cam = &R.cam;
       Ctx c;
-      c.s = &R.scene;
-      c.st = NULL;
-      c.wk = NULL;
-      c.shift = 0.0f;
-      c.rng.key[0] = g->seed;
-      c.rng.key[1] = (uint32_t)frame;
-      c.rng.pixel = (uint32_t)(y * g->xRes + x);
-      c.rng.sample = (uint32_t)(r % 8 + 8 * (q / npx));
-      V3 eye_sample = cam->eye;
-      if (g->aperture > 0) {
-        double u0, u1;
-        rng2(&c.rng, 0, P_DOF, 0, &u0, &u1);
-        float rr = (float)(g->aperture / 2 * u0);
-        float theta = (float)(2 * M_PI * u1);
-        eye_sample = add(add(cam->eye, mul(rr * cr_cosf(theta), cam->X)), mul(rr * cr_sinf(theta), cam->Y));
-      }
-      V3 focalPoint = add(cam->eye, mul(g->focal_length, persp_eye_ray(g, cam, x, y)));
-      V3 ray = sub(focalPoint, eye_sample);
+      V3 eye_sample, ray;
+      primary_ray(&R, g, frame, first + i, &c, &eye_sample, &ray);
       int n_inds = bvh_gather(&c, ray, eye_sample, inds);
       float t_dist = FLT_MAX, t_min = FLT_MAX;
       int any = 0, hit_i = -1;
@@ -2024,6 +2032,153 @@ int or_primary_hit(const dt_scene_desc* d, const dt_globals* g, int frame, long 
   }
   scene_free(&R.scene);
   return DT_OK;
+}
+
+/* the start and direction of the rays or_primary_hit (and dt_intersect_primary) trace; needs no scene */
+int or_primary_ray(const dt_globals* g, int frame, long long first, long long n, double* start, double* dir)
+{
+  dt_scene_desc empty;
+  memset(&empty, 0, sizeof(empty));
+  RenderCtx R;
+  int rc = render_setup(&R, &empty, g, frame);
+  if (rc != DT_OK) { scene_free(&R.scene); return rc; }
+  for (long long i = 0; i < n; ++i) {
+    Ctx c;
+    V3 eye_sample, ray;
+    primary_ray(&R, g, frame, first + i, &c, &eye_sample, &ray);
+    start[3 * i] = eye_sample.x; start[3 * i + 1] = eye_sample.y; start[3 * i + 2] = eye_sample.z;
+    dir[3 * i] = ray.x; dir[3 * i + 1] = ray.y; dir[3 * i + 2] = ray.z;
+  }
+  scene_free(&R.scene);
+  return DT_OK;
+}
+
+/* ======================================================================= */
+/* test-only entry points to the geometry statics above (tests/test_oracle_geom.py compares them with
+ * the reference's geometry.cpp, oracle/ref/geom_harness.cpp). Each wraps a static; none restates one.
+ * A shape is (d, si): shapes[si] of a dt_scene_desc, with d->holes for a RectPrismWithCylinder.      */
+/* ======================================================================= */
+static void geom_ctx(Scene* s, Ctx* c, const dt_scene_desc* d, dt_stats* st)
+{
+  memset(s, 0, sizeof(*s));
+  s->d = d;
+  s->root = -1;
+  memset(c, 0, sizeof(*c));
+  c->s = s;
+  c->shift = 0.0f;
+  if (st) memset(st, 0, sizeof(*st));
+  c->st = st;
+}
+
+static void v3out(V3 a, double* o) { o[0] = a.x; o[1] = a.y; o[2] = a.z; }
+
+/* GeoPrimitive::intersect. *t and *inside keep the caller's values where the shape does not write them;
+ * *hole: the RectPrismWithCylinder hole whose body is the hit (-1: none) */
+int or_shape_intersect(const dt_scene_desc* d, int si, const double ray[3], const double start[3], float* t,
+                       int* inside, int* hole)
+{
+  Scene s; Ctx c;
+  geom_ctx(&s, &c, d, NULL);
+  V3 hc;
+  int h = -1;
+  int r = shape_intersect(&c, si, v3a(ray), v3a(start), t, inside, &hc, &h);
+  if (hole) *hole = h;
+  return r;
+}
+
+/* the colour the reference's intersect() leaves in shape->color (Checkerboard square, hit hole) */
+int or_shape_color_after_hit(const dt_scene_desc* d, int si, const double ray[3], const double start[3],
+                             double color[3])
+{
+  Scene s; Ctx c;
+  geom_ctx(&s, &c, d, NULL);
+  V3 hc;
+  float t = 0;
+  int inside = 0, h = -1;
+  int r = shape_intersect(&c, si, v3a(ray), v3a(start), &t, &inside, &hc, &h);
+  v3out(hc, color);
+  return r;
+}
+
+int or_shape_shadow(const dt_scene_desc* d, int si, const double ray[3], const double start[3], float t_max)
+{
+  Scene s; Ctx c;
+  geom_ctx(&s, &c, d, NULL);
+  return shape_shadow(&c, si, v3a(ray), v3a(start), t_max);
+}
+
+/* Cylinder::intersectCap of a CYLINDER / CHECKER_CYLINDER record */
+int or_shape_intersect_cap(const dt_scene_desc* d, int si, const double ray[3], const double start[3], float* t,
+                           int* inside)
+{
+  return cyl_intersect_cap(&d->shapes[si], v3a(ray), v3a(start), t, inside);
+}
+
+/* GeoPrimitive::getNorm; hole as or_shape_intersect reported it. Returns the number of fallbacks taken
+ * (RectPrismV2 off-surface print path, RectPrismWithCylinder's throw) */
+int or_shape_norm(const dt_scene_desc* d, int si, const double p[3], int hole, double out[3])
+{
+  Scene s; Ctx c;
+  dt_stats st;
+  geom_ctx(&s, &c, d, &st);
+  v3out(shape_norm(&c, si, v3a(p), hole), out);
+  return (int)st.prism_norm_fallback;
+}
+
+/* GeoPrimitive::getUV: returns valid (0, 1, 2) */
+int or_shape_uv(const dt_scene_desc* d, int si, const double p[3], double uv[2])
+{
+  Scene s; Ctx c;
+  dt_stats st;
+  geom_ctx(&s, &c, d, &st);
+  return shape_uv(&c, si, v3a(p), &uv[0], &uv[1]);
+}
+
+void or_shape_bounds(const dt_scene_desc* d, int si, double lb[3], double ub[3])
+{
+  V3 l, u;
+  shape_bounds(&d->shapes[si], &l, &u);
+  v3out(l, lb);
+  v3out(u, ub);
+}
+
+/* CheckerCylinder::objM (buildCOB + constructor), row-major */
+void or_checker_cyl_objM(const dt_scene_desc* d, int si, double out[16])
+{
+  double M[4][4];
+  checker_cyl_objM(&d->shapes[si], M);
+  memcpy(out, M, sizeof(M));
+}
+
+/* BoundingVolume over the one shape si (constructor + setBounds, as generateBVH pushes it) and, with
+ * ray != NULL, BoundingVolume::intersect; lb / ub (optional) receive the padded bounds */
+int or_box_intersect(const dt_scene_desc* d, int si, int leaf, const double ray[3], const double inv_ray[3],
+                     const double start[3], double lb[3], double ub[3])
+{
+  Scene s; Ctx c;
+  geom_ctx(&s, &c, d, NULL);
+  int node = bvh_push_node(&s, leaf, &si, 1);
+  const BNode* b = &s.nodes[node];
+  if (lb) v3out(b->lb, lb);
+  if (ub) v3out(b->ub, ub);
+  int r = ray ? box_intersect(b, 0.0f, v3a(ray), v3a(inv_ray), v3a(start)) : b->leaf;
+  scene_free(&s);
+  return r;
+}
+
+void or_fix_norm(const double ray[3], const double nrm[3], double out[3])
+{
+  v3out(fix_norm(v3a(ray), v3a(nrm)), out);
+}
+
+void or_barycentric3d(const double p[3], const double A[3], const double B[3], const double C[3], double out[3])
+{
+  v3out(barycentric3d(v3a(p), v3a(A), v3a(B), v3a(C)), out);
+}
+
+int or_segment_intersect(const double A[3], const double B[3], const double ray[3], const double origin[3])
+{
+  return segment_intersect(v3a(A), v3a(B), v3a(ray), v3a(origin));
 }
 
 int or_render_work(const dt_scene_desc* d, const dt_globals* g, int frame, const dt_tiles* tiles, float* out,

@@ -10,9 +10,19 @@
  *   - value noise (noise.h:25-136) is pinned bit-for-bit against the reference's own
  *     noise.h compiled as-is (oracle/ref/noise_harness.cpp -> oracle/_ref/libref_noise.so)
  *     and against the hand-derived anchors of SURVEY §8c.
- *   - everything else (render_final_project.cpp, geometry.cpp, helpers.h) needs Eigen,
- *     which is absent from the image: the reference is unbuildable here, so those
- *     functions are "parity unpinned" beyond analytic anchors (tests/test_oracle_*.py).
+ *   - geometry.cpp, as far as this file restates it (intersect / intersectShadow / intersectCap /
+ *     getNorm / getBounds / getUV of the classes behind dt_shape_type, fixNorm, getBarycentricCoords3D,
+ *     segmentIntersect's verdict, CheckerCylinder's objM, BoundingVolume), is pinned bit-for-bit against
+ *     the reference's own geometry.cpp,
+ *     compiled unmodified against the Eigen-API shim oracle/ref/eigen_shim
+ *     (oracle/ref/geom_harness.cpp -> oracle/_ref/libref_geom.so -> tests/golden/geom_ref.npz,
+ *     tests/test_oracle_geom.py). The shim and this file share their Eigen conventions (dot's summation
+ *     order, normalized() of a zero vector): the program logic is pinned, Eigen's internals are not.
+ *     Not compared (no restatement here, or no reference answer): intersectMax, buildCOB on its own,
+ *     shortestLine's coefficients, lineIntersect, RectPrism / RectPrismWithHoles, and
+ *     RectPrismWithCylinder::getNorm where the reference throws or answers from a stale lastHit.
+ *   - render_final_project.cpp and helpers.h (shading, refraction, BVH build) drag in the skeleton code
+ *     and ~60 globals: "parity unpinned" beyond analytic anchors (tests/test_oracle_*.py).
  *
  * RNG: the reference draws from random_device-seeded mt19937 (F7) and cannot be
  * reproduced; oracle and device share the counter-based stream documented in
@@ -64,6 +74,30 @@ int or_render_work(const dt_scene_desc* d, const dt_globals* g, int frame, const
 /* the intersection micro-benchmark's closest hits (include/dt.h dt_intersect_primary numbering) */
 int or_primary_hit(const dt_scene_desc* d, const dt_globals* g, int frame, long long first, long long n,
                    int* shape, float* t, int nthreads);
+
+/* the start and direction (n x 3 doubles each) of the rays or_primary_hit and dt_intersect_primary trace */
+int or_primary_ray(const dt_globals* g, int frame, long long first, long long n, double* start, double* dir);
+
+/* Test-only entry points to the geometry.cpp restatement (tests/test_oracle_geom.py). A shape is
+ * (d, si): d->shapes[si], with d->holes for a RectPrismWithCylinder. They wrap the static functions
+ * the render loop calls. *t / *inside keep the caller's value where the reference's method leaves its
+ * reference parameter unwritten. */
+int  or_shape_intersect(const dt_scene_desc* d, int si, const double ray[3], const double start[3], float* t,
+                        int* inside, int* hole);
+int  or_shape_color_after_hit(const dt_scene_desc* d, int si, const double ray[3], const double start[3],
+                              double color[3]);
+int  or_shape_shadow(const dt_scene_desc* d, int si, const double ray[3], const double start[3], float t_max);
+int  or_shape_intersect_cap(const dt_scene_desc* d, int si, const double ray[3], const double start[3], float* t,
+                            int* inside);
+int  or_shape_norm(const dt_scene_desc* d, int si, const double p[3], int hole, double out[3]);
+int  or_shape_uv(const dt_scene_desc* d, int si, const double p[3], double uv[2]);
+void or_shape_bounds(const dt_scene_desc* d, int si, double lb[3], double ub[3]);
+void or_checker_cyl_objM(const dt_scene_desc* d, int si, double out[16]);
+int  or_box_intersect(const dt_scene_desc* d, int si, int leaf, const double ray[3], const double inv_ray[3],
+                      const double start[3], double lb[3], double ub[3]);
+void or_fix_norm(const double ray[3], const double nrm[3], double out[3]);
+void or_barycentric3d(const double p[3], const double A[3], const double B[3], const double C[3], double out[3]);
+int  or_segment_intersect(const double A[3], const double B[3], const double ray[3], const double origin[3]);
 
 /* one rayColor call tree for a single pixel-sample (debug / unit tests) */
 int or_sample_color(const dt_scene_desc* d, const dt_globals* g, int frame, int x, int y,
