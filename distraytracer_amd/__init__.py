@@ -23,7 +23,7 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "accel_info", "DT_KERNEL_AUTO", "DT_KERNEL_PRODUCT", "DT_KERNEL_DONATE",
            "accum_doubles", "window_check", "render_window", "render_window_async", "resolve", "Progressive",
            "mean_abs_change", "adapt_converged", "render_window_adaptive", "resolve_adaptive", "adapt_select_ms",
-           "AdaptiveProgressive"]
+           "AdaptiveProgressive", "render_features", "feature_images", "FEATURE_PLANES"]
 
 
 def globals_default():
@@ -193,6 +193,67 @@ def intersect_primary(scene, g, frame, first_ray, hit_shape, hit_t, stream=None)
     return ms.value
 
 
+FEATURE_PLANES = ("albedo", "normal", "depth", "coverage", "shape")
+
+
+def render_features(scene, g, frame, n_samples=None, tile=None, stream=None, planes=FEATURE_PLANES, out=None,
+                    stats=None):
+    """First-hit feature buffers of the leading n_samples samples (None: spp) of every owned pixel
+    (include/dt.h dt_render_features): a dict plane name -> tensor. albedo and normal hold
+    accum_doubles(g, tile) float32 elements, indexed like render's output; depth and coverage
+    (float32) and shape (int32) a third of that, entry q for the pixel at floats 3q..3q+2. `out`: a
+    dict of planes to write into, all CUDA torch tensors or all host arrays (numpy, CPU tensors),
+    where only owned pixels are written; without it, new CUDA tensors (zeros, shape -1). stats: a Stats
+    to fill with the call's counts."""
+    n3 = accum_doubles(g, tile)
+    n = _spp(g) if n_samples is None else int(n_samples)
+    if out is None:
+        import torch
+        for name in planes:
+            if name not in FEATURE_PLANES:
+                raise DTError("render_features: unknown plane %r" % (name,))
+        out = {name: (torch.full((n3 // 3,), -1, dtype=torch.int32, device="cuda") if name == "shape" else
+                      torch.zeros(n3 if name in ("albedo", "normal") else n3 // 3, dtype=torch.float32, device="cuda"))
+               for name in planes}
+    from ._lib import Features
+    f = Features()
+    side = None
+    for name, a in out.items():
+        if name not in FEATURE_PLANES:
+            raise DTError("render_features: unknown plane %r" % (name,))
+        p, dev = _ptr_typed(a, "torch.int32", "int32") if name == "shape" else _ptr(a)
+        need = n3 if name in ("albedo", "normal") else n3 // 3
+        have = a.numel() if hasattr(a, "numel") else a.size
+        if have != need:
+            raise DTError("render_features: plane %s holds %d elements, (g, tile) need %d" % (name, have, need))
+        if side is not None and dev != side:
+            raise DTError("render_features: the planes must all be on the same side")
+        side = dev
+        setattr(f, name, p)
+    st = stats if stats is not None else Stats()
+    check(lib.dt_render_features(scene.handle, ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None, n,
+                                 ctypes.byref(f), side or 0, ctypes.c_void_p(stream) if stream else None,
+                                 ctypes.byref(st)), "dt_render_features")
+    return out
+
+
+def feature_images(g, feats):
+    """The four 8-bit feature images as `dtrender --features` writes them, from full-frame image-layout
+    planes (numpy float32): {"albedo": albedo*255, "normal": (normal*0.5 + 0.5*coverage)*255,
+    "depth": depth / the frame's largest depth * 255 (grey), "coverage": coverage*255 (grey)}, each
+    3 floats per pixel for write_png, clamped to 0..255. float32 arithmetic in this order."""
+    import numpy as np
+    f32 = np.float32
+    cov = np.ascontiguousarray(feats["coverage"], dtype=f32)
+    dep = np.ascontiguousarray(feats["depth"], dtype=f32)
+    dmax = dep.max() if dep.size else f32(0)
+    grey_d = (dep / dmax if dmax > 0 else np.zeros_like(dep)) * f32(255)
+    img = {"albedo": np.ascontiguousarray(feats["albedo"], dtype=f32) * f32(255),
+           "normal": (np.ascontiguousarray(feats["normal"], dtype=f32) * f32(0.5) + np.repeat(f32(0.5) * cov, 3)) * f32(255),
+           "depth": np.repeat(grey_d, 3), "coverage": np.repeat(cov * f32(255), 3)}
+    return {k: np.clip(v, f32(0), f32(255)) for k, v in img.items()}
+
+
 def render_sky(g, frame, out, tile=None, stream=None):
     """renderImageCloud's pixel loop (sky only) into `out`."""
     st = Stats()
@@ -335,6 +396,14 @@ class Progressive:
             out = torch.empty(self.accum.numel(), dtype=torch.float32, device="cuda")
         self.nan_pixels = resolve(self.g, self.accum, self.samples_done, out, self.tile)
         return out
+
+    def features(self, planes=FEATURE_PLANES):
+        """The first-hit feature buffers of the samples rendered so far (render_features of the leading
+        samples_done samples of every owned pixel, in the accumulator's layout; with adaptive sampling
+        of every pixel alike, whether or not it has stopped)."""
+        if self.samples_done < 1:
+            raise DTError("Progressive.features: no window rendered yet")
+        return render_features(self.scene, self.g, self.frame, self.samples_done, self.tile, planes=planes)
 
     def run(self, until=None, n_chunks=1):
         """step() until done, or until until(self) returns true after a step."""
@@ -545,14 +614,17 @@ def write_png(filename, g, values):
     check(lib.dt_write_png(filename.encode(), g.xRes, g.yRes, ctypes.c_void_p(v.ctypes.data)), "dt_write_png")
 
 
-def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progressive=None, adaptive=None):
+def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progressive=None, adaptive=None,
+                features=None):
     """render_final_project.cpp:965: build (sceneBuilder names a scene.h builder), render the
     frame on the current GPU, write the PPM. Returns (image, stats). progressive=callback renders in
     one-chunk sample windows (Progressive) and calls callback(image, samples_done) with the resolved
     preview (numpy) after every window; the image returned is the same bits, stats the last window's.
     adaptive=tol renders with adaptive sampling (AdaptiveProgressive at that tolerance, in grey levels):
     converged pixels stop between windows, every pixel is the mean of its own samples; a progressive
-    callback is called after every window as well."""
+    callback is called after every window as well. features=prefix also writes the first-hit feature images
+    of all spp samples, prefix.albedo.png, prefix.normal.png, prefix.depth.png and prefix.coverage.png
+    (feature_images), as `dtrender --features` does."""
     import numpy as np
     g = g if g is not None else globals_default()
     built = build_scene(sceneBuilder, frame if builder_frame is None else builder_frame, g)
@@ -575,6 +647,10 @@ def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progr
         st = render(scene, g, frame, img)
     if filename:
         (write_png if filename.endswith(".png") else write_ppm)(filename, g, img)
+    if features:
+        planes = render_features(scene, g, frame, planes=("albedo", "normal", "depth", "coverage"))
+        for name, v in feature_images(g, {k: t.cpu().numpy() for k, t in planes.items()}).items():
+            write_png("%s.%s.png" % (features, name), g, v)
     scene.close()
     return img, st
 

@@ -93,6 +93,12 @@ class Stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Features(ctypes.Structure):
+    """dt_features: the planes of dt_render_features (a null pointer: not wanted)"""
+    _fields_ = [("albedo", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("depth", ctypes.c_void_p),
+                ("coverage", ctypes.c_void_p), ("shape", ctypes.c_void_p)]
+
+
 class BVHNode(ctypes.Structure):
     _fields_ = [("first_child", c_int32), ("n_children", c_int32), ("first_index", c_int32),
                 ("n_indices", c_int32), ("leaf", c_int32), ("depth", c_int32), ("lbound", D3), ("ubound", D3)]
@@ -123,7 +129,7 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_debug_load_obj",
            "dt_accum_doubles", "dt_window_check", "dt_render_window", "dt_render_window_async", "dt_resolve",
            "dt_adapt_converged", "dt_render_window_adaptive", "dt_render_window_adaptive_async",
-           "dt_resolve_adaptive", "dt_adapt_select_ms"]
+           "dt_resolve_adaptive", "dt_adapt_select_ms", "dt_render_features"]
 
 
 class DTError(RuntimeError):
@@ -201,6 +207,8 @@ def _load():
                                     P(Stats)]),
         "dt_intersect_primary": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, c_int64, c_int64, ctypes.c_void_p,
                                            ctypes.c_void_p, c_int32, ctypes.c_void_p, P(c_float)]),
+        "dt_render_features": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, P(Features), c_int32,
+                                         ctypes.c_void_p, P(Stats)]),
         "dt_unpack_slabs": (c_int32, [P(Globals), P(Tiles), c_int32, ctypes.c_void_p, ctypes.c_void_p, c_int32,
                                       ctypes.c_void_p]),
         "dt_build_scene": (c_int32, [ctypes.c_char_p, c_float, P(Globals), ctypes.c_char_p, P(P(SceneDesc))]),

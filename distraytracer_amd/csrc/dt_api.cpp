@@ -87,6 +87,9 @@ extern "C" hipError_t dt_launch_adapt_select(const void* dev_launch, int64_t n_i
 extern "C" hipError_t dt_launch_isect(const void* dev_launch, int64_t first, int64_t n, int32_t* hit_shape, float* hit_t,
                                       int grid, hipStream_t stream);
 extern "C" const void* dt_isect_kernel_ptr(void);
+extern "C" hipError_t dt_launch_features(const void* dev_launch, int n_samples, float* albedo, float* normal, float* depth,
+                                         float* coverage, int32_t* shape, int grid, hipStream_t stream);
+extern "C" const void* dt_features_kernel_ptr(void);
 
 namespace {
 
@@ -1664,6 +1667,108 @@ int dt_intersect_primary(const dt_scene* sc_c, const dt_globals* g, int32_t fram
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
     *kernel_ms = ms;
+  }
+  return DT_OK;
+}
+
+// First-hit feature buffers: dt_features_kernel over the samples 0 .. n_samples-1 of every owned pixel.
+// Synchronous; like dt_intersect_primary its launch record, counters and events are its own and it
+// shares only the scene's primary-ray lists. Every argument check comes before the scene is looked at.
+int dt_render_features(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                       int32_t n_samples, const dt_features* out, int32_t out_on_device, void* stream, dt_stats* stats)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  if (!sc) return fail(DT_E_INVALID, "dt_render_features: null scene");
+  if (!g) return fail(DT_E_INVALID, "dt_render_features: null globals");
+  if (!out) return fail(DT_E_INVALID, "dt_render_features: null planes");
+  if (!out->albedo && !out->normal && !out->depth && !out->coverage && !out->shape)
+    return fail(DT_E_INVALID, "dt_render_features: no plane wanted (every pointer is null)");
+  if (int rc = dt_window_check(g, 0, n_samples)) return rc;
+  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_render_features: scenes with a RectPrismWithCylinder");
+  hipStream_t st = (hipStream_t)stream;
+  dtd::DParams P;
+  std::vector<float> zs;
+  int rc = prepare_render(sc, g, frame, tiles, P, zs);
+  if (rc) return rc;
+  if ((rc = scene_upload(sc)) || (rc = update_primary_lists(sc, P, true))) return rc;
+  // the planes' lengths (dt_accum_doubles) and the pixels the launch produces: the owned tiles' pixels
+  // inside the window (pixel_of's `valid`)
+  const int64_t n3 = P.layout == DT_OUT_SLAB ? P.n_owned_tiles * P.tw * P.th * 3 : (int64_t)3 * P.xRes * P.yRes;
+  const int64_t n1 = n3 / 3;
+  uint64_t pixels = 0;
+  for (int64_t slot = 0; slot < P.n_owned_tiles; ++slot) {
+    const int64_t t = dtd::tile_of(slot, P.rank, P.world);
+    if (t >= P.n_tiles) continue;
+    const int ty = (int)(t / P.tiles_x), tx = (int)(t - (int64_t)ty * P.tiles_x);
+    const int xa = P.x0 + tx * P.tw, ya = P.y0 + ty * P.th;
+    const int xb = xa + P.tw < P.x1 ? xa + P.tw : P.x1, yb = ya + P.th < P.y1 ? ya + P.th : P.y1;
+    if (xb > xa && yb > ya) pixels += (uint64_t)(xb - xa) * (uint64_t)(yb - ya);
+  }
+  struct Tmp {   // released on every return path, after the stream's work that may use them
+    hipStream_t st = nullptr;
+    void *launch = nullptr, *stats = nullptr, *plane[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Tmp()
+    {
+      if (launch) (void)hipStreamSynchronize(st);
+      for (void* b : {launch, stats, plane[0], plane[1], plane[2], plane[3], plane[4]})
+        if (b) (void)hipFree(b);
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+    }
+  } tmp;
+  tmp.st = st;
+  const size_t n_stats = sizeof(unsigned long long) * (ST_N + 1);
+  HIPCHK(hipMalloc(&tmp.launch, dt_launch_size()));
+  HIPCHK(hipMalloc(&tmp.stats, n_stats));
+  HIPCHK(hipMemsetAsync(tmp.stats, 0, n_stats, st));
+  HScene hs;
+  fill_hscene(sc, hs);
+  hs.stats = (unsigned long long*)tmp.stats;
+  hs.queue = hs.stats + ST_N;
+  std::vector<uint8_t> L(dt_launch_size(), 0);
+  memcpy(L.data() + dt_scene_struct_offset(), &hs, sizeof(hs));
+  memcpy(L.data() + dt_params_struct_offset(), &P, sizeof(P));
+  HIPCHK(hipMemcpyAsync(tmp.launch, L.data(), L.size(), hipMemcpyHostToDevice, st));
+  // host planes are staged through device copies of the caller's arrays: the entries of pixels this
+  // rank does not own go back as they came
+  void* host[5] = {out->albedo, out->normal, out->depth, out->coverage, out->shape};
+  void* dev[5] = {out->albedo, out->normal, out->depth, out->coverage, out->shape};
+  const size_t bytes[5] = {(size_t)n3 * sizeof(float), (size_t)n3 * sizeof(float), (size_t)n1 * sizeof(float),
+                           (size_t)n1 * sizeof(float), (size_t)n1 * sizeof(int32_t)};
+  if (!out_on_device)
+    for (int k = 0; k < 5; ++k)
+      if (host[k]) {
+        HIPCHK(hipMalloc(&tmp.plane[k], bytes[k]));
+        HIPCHK(hipMemcpyAsync(tmp.plane[k], host[k], bytes[k], hipMemcpyHostToDevice, st));
+        dev[k] = tmp.plane[k];
+      }
+  static int resident = 0;
+  if (!resident) resident = max_resident_waves(dt_features_kernel_ptr(), 64);
+  const int grid = (int)(P.n_items < resident ? P.n_items : resident);
+  HIPCHK(hipEventCreate(&tmp.e0));
+  HIPCHK(hipEventCreate(&tmp.e1));
+  HIPCHK(hipEventRecord(tmp.e0, st));
+  HIPCHK(dt_launch_features(tmp.launch, n_samples, (float*)dev[0], (float*)dev[1], (float*)dev[2], (float*)dev[3],
+                            (int32_t*)dev[4], grid > 0 ? grid : 1, st));
+  HIPCHK(hipEventRecord(tmp.e1, st));
+  if (!out_on_device)
+    for (int k = 0; k < 5; ++k)
+      if (host[k]) HIPCHK(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, st));
+  unsigned long long h[ST_N + 1];
+  HIPCHK(hipMemcpyAsync(h, tmp.stats, n_stats, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
+    stats->pixels = pixels;
+    stats->samples = pixels * (uint64_t)n_samples;
+    stats->rays = stats->samples;
+    stats->tex_fetches = h[ST_TEX];
+    stats->uv_out_of_range = h[ST_UV];
+    stats->prism_norm_fallback = h[ST_PRISM];
+    stats->kernel_ms = ms;
   }
   return DT_OK;
 }

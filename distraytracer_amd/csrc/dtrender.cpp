@@ -20,6 +20,11 @@
 //                     whose mean has a standard error of at most TOL grey levels stop. --min-samples N:
 //                     no pixel stops with fewer (default 64). --counts FILE: samples taken / spp per
 //                     pixel as a grey PNG. Prints the share of pixels * spp that was taken.
+//   --features PREFIX after the frame, the first-hit feature buffers of all spp samples (dt_render_features)
+//                     as 8-bit PNGs: PREFIX.albedo.png (albedo*255), PREFIX.normal.png ((normal*0.5 +
+//                     0.5*coverage)*255), PREFIX.depth.png (depth / the frame's largest depth, grey) and
+//                     PREFIX.coverage.png (grey), each clamped to 0..255. The frame file is the same bytes
+//                     as without the flag.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -48,7 +53,7 @@ int main(int argc, char** argv)
   std::string data_dir = DT_DATA_DIR;
   int spp = -1, depth = -1, W = -1, H = -1, progressive = 0, min_samples = 64;
   double adaptive = -1.0;
-  std::string counts_file;
+  std::string counts_file, features_prefix;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     if (a == "--out" && i + 1 < argc) out = argv[++i];
@@ -61,6 +66,7 @@ int main(int argc, char** argv)
     else if (a == "--adaptive" && i + 1 < argc) adaptive = atof(argv[++i]);
     else if (a == "--min-samples" && i + 1 < argc) min_samples = atoi(argv[++i]);
     else if (a == "--counts" && i + 1 < argc) counts_file = argv[++i];
+    else if (a == "--features" && i + 1 < argc) features_prefix = argv[++i];
   }
   std::string scene = "final";
   float build_frame = 0;
@@ -212,6 +218,36 @@ int main(int argc, char** argv)
     if (rc) return die("dt_render", rc);
     rc = png ? dt_write_png(fn.c_str(), g.xRes, g.yRes, img.data()) : dt_write_ppm(fn.c_str(), g.xRes, g.yRes, img.data());
     if (rc) return die("dt_write_ppm/png", rc);
+  }
+  if (!features_prefix.empty()) {
+    const int n = (int)sqrt((double)g.antialias_samples);
+    const size_t n_px = (size_t)g.xRes * g.yRes;
+    std::vector<float> alb(3 * n_px, 0.0f), nrm(3 * n_px, 0.0f), dep(n_px, 0.0f), cov(n_px, 0.0f), pix(3 * n_px);
+    dt_features f;
+    memset(&f, 0, sizeof f);
+    f.albedo = alb.data(); f.normal = nrm.data(); f.depth = dep.data(); f.coverage = cov.data();
+    dt_stats fst;
+    rc = dt_render_features(s, &g, frame, nullptr, n * n, &f, 0, nullptr, &fst);
+    if (rc) return die("dt_render_features", rc);
+    float dmax = 0.0f;
+    for (size_t q = 0; q < n_px; ++q) dmax = dep[q] > dmax ? dep[q] : dmax;
+    for (int plane = 0; plane < 4; ++plane) {
+      static const char* const names[4] = {"albedo", "normal", "depth", "coverage"};
+      for (size_t q = 0; q < n_px; ++q)
+        for (int k = 0; k < 3; ++k) {
+          float v;
+          if (plane == 0) v = alb[3 * q + k] * 255.0f;
+          else if (plane == 1) v = (nrm[3 * q + k] * 0.5f + 0.5f * cov[q]) * 255.0f;
+          else if (plane == 2) v = (dmax > 0.0f ? dep[q] / dmax : 0.0f) * 255.0f;
+          else v = cov[q] * 255.0f;
+          pix[3 * q + k] = v < 0.0f ? 0.0f : v > 255.0f ? 255.0f : v;   // (the PNG writer truncates to a byte)
+        }
+      const std::string pf = features_prefix + "." + names[plane] + ".png";
+      rc = dt_write_png(pf.c_str(), g.xRes, g.yRes, pix.data());
+      if (rc) return die("dt_write_png (features)", rc);
+    }
+    printf("features: %llu pixels in %.3f ms (kernel) -> %s.{albedo,normal,depth,coverage}.png\n",
+           (unsigned long long)fst.pixels, fst.kernel_ms, features_prefix.c_str());
   }
   double msps = st.samples / (st.kernel_ms * 1e-3) / 1e6;
   printf("Rendered %s frame %d: %dx%d, %d spp, depth %d in %.2f ms (kernel, %.1f Mpixel-samples/s) -> %s\n",

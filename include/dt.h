@@ -49,6 +49,8 @@ extern "C" {
  *    dt_render_window_async, dt_resolve -- progressive rendering) */
 /* (still 8, new exports only, no struct changed: dt_adapt_converged, dt_render_window_adaptive,
  *    dt_render_window_adaptive_async, dt_resolve_adaptive, dt_adapt_select_ms -- adaptive sampling) */
+/* (still 8, new exports only, no struct changed: dt_render_features and its dt_features argument --
+ *    first-hit feature buffers) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -451,6 +453,47 @@ int dt_debug_normalize(const double* in, double* out, int64_t n);
 int dt_intersect_primary(const dt_scene* s, const dt_globals* g, int32_t frame, int64_t first_ray,
                          int64_t n_rays, int32_t* hit_shape, float* hit_t, int32_t out_on_device,
                          void* stream, float* kernel_ms);
+
+/* First-hit feature buffers ("AOVs": the per-pixel companions of the colour image a denoiser, a
+ * compositor or an object picker reads). No reference counterpart. For the samples 0 .. n_samples-1 of
+ * every owned pixel (n_samples as dt_window_check(g, 0, n_samples): whole 64-sample chunks or spp; with
+ * spp < 64, spp) the render's own primary ray is traced to its closest hit, exactly as dt_render's
+ * root ray: RNG pixel y*xRes+x, sample i, key (seed, frame); in dt_intersect_primary's numbering ray
+ * ((i/8)*W*H + y*W + x)*8 + i%8. A miss adds nothing; a hit on shape h at t along the unnormalised ray:
+ *   p      = eye_sample + (double)t * ray
+ *   normal = fixNorm(normalized(ray), getNorm(p))              world space
+ *   colour = the colour intersect() leaves in the shape (a Checkerboard's square, else the shape's);
+ *            for a DT_F_TEXTURE shape, by getUV(p): type 1 with a texture the texel / 255.0 (the light
+ *            loop's index arithmetic and clamp; counted in tex_fetches), type 2 bordercolor, type 0
+ *            unchanged; a uv outside [0,1] (types 1, 2) counts uv_out_of_range
+ *   d      = (double)t * |ray|
+ * All sums are f64, left to right in ascending sample order. With A, N, D the sums over the H hitting
+ * samples of n = n_samples:
+ *   albedo[3q+k] = (float)(A[k] / n)      normal[3q+k] = (float)(N[k] / n)      (premultiplied by
+ *   coverage[q]  = (float)(H / n)         depth[q] = H ? (float)(D / H) : 0      coverage, no clamp,
+ *   shape[q]     = the shape sample 0 hit (-1: none)                             not renormalised)
+ * q is the pixel's slot in the output layout: its colour occupies floats 3q..3q+2 of dt_render's output
+ * (DT_OUT_IMAGE and DT_OUT_SLAB alike; the entry of dt_render_window_adaptive's count). Planes hold
+ * dt_accum_doubles(g, tiles) (albedo, normal) or a third of that (depth, coverage, shape) elements, all
+ * host (out_on_device=0) or all device (1); a NULL plane is not wanted. Only owned pixels are written.
+ * On frames >= frame_prism the planes describe the unshifted hit, not the motion-blur re-traces.
+ * Synchronous. stats (optional): pixels produced, samples = rays = pixels * n, tex_fetches,
+ * uv_out_of_range, prism_norm_fallback, kernel_ms; everything else 0. Like dt_intersect_primary it has
+ * a launch record, counters and events of its own and shares only the scene's primary-ray lists: a
+ * render of the scene afterwards is unaffected. A null scene, globals or out, an out with every plane
+ * NULL or a bad n_samples: DT_E_INVALID; a scene with a RectPrismWithCylinder: DT_E_UNSUPPORTED; both
+ * before any device work. */
+typedef struct dt_features {      /* each plane optional (NULL: not wanted); all on one side */
+  float*   albedo;    /* 3 per pixel, indexed exactly like dt_render's output (element 3q+k) */
+  float*   normal;    /* 3 per pixel, same indexing; world space */
+  float*   depth;     /* 1 per pixel, entry q */
+  float*   coverage;  /* 1 per pixel, entry q */
+  int32_t* shape;     /* 1 per pixel, entry q */
+} dt_features;
+
+int dt_render_features(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                       int32_t n_samples, const dt_features* out, int32_t out_on_device,
+                       void* stream, dt_stats* stats);
 
 /* renderImageCloud (render_final_project.cpp:1224-1279). Sets eye/up/lookingAt as the
  * reference does (1227-1229) on a local copy; g is not modified. */
