@@ -14,7 +14,7 @@ an error (there is no CPU path in this package).
 """
 import ctypes
 
-from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT, DT_OUT_IMAGE, DT_OUT_SLAB, AccelInfo, BVHNode, DTError, Globals, SceneDesc,
+from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT, DT_OUT_IMAGE, DT_OUT_SLAB, AccelInfo, BVHNode, DenoiseParams, DTError, Globals, SceneDesc,
                    Stats, Tiles, check, lib)
 
 __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_scene", "Scene",
@@ -23,7 +23,8 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "accel_info", "DT_KERNEL_AUTO", "DT_KERNEL_PRODUCT", "DT_KERNEL_DONATE",
            "accum_doubles", "window_check", "render_window", "render_window_async", "resolve", "Progressive",
            "mean_abs_change", "adapt_converged", "render_window_adaptive", "resolve_adaptive", "adapt_select_ms",
-           "AdaptiveProgressive", "render_features", "feature_images", "FEATURE_PLANES"]
+           "AdaptiveProgressive", "render_features", "feature_images", "FEATURE_PLANES",
+           "DenoiseParams", "denoise_params_default", "denoise", "denoised_filename"]
 
 
 def globals_default():
@@ -254,6 +255,81 @@ def feature_images(g, feats):
     return {k: np.clip(v, f32(0), f32(255)) for k, v in img.items()}
 
 
+def denoise_params_default():
+    """dt_denoise_params_default: levels 5, demodulate 1 and the sigmas chosen in BASELINE.md."""
+    from ._lib import DenoiseParams
+    p = DenoiseParams()
+    lib.dt_denoise_params_default(ctypes.byref(p))
+    return p
+
+
+_denoise_work = {}   # side (0 host, 1 + device index) -> the workspace last allocated there
+
+
+def _denoise_workspace(n, dev, like):
+    key = 0 if not dev else 1 + like.device.index
+    w = _denoise_work.get(key)
+    if w is None or (w.numel() if dev else w.size) < n:
+        if dev:
+            import torch
+            w = torch.empty(n, dtype=torch.float32, device=like.device)
+        else:
+            import numpy as np
+            w = np.empty(n, np.float32)
+        _denoise_work[key] = w
+    return w
+
+
+def denoise(g, colour, feats, params=None, out=None, stream=None):
+    """The edge-avoiding a-trous filter of include/dt.h dt_denoise on a whole frame of g.xRes x g.yRes:
+    colour (3 floats per pixel, as render / Progressive.image give it) and feats, a dict with the albedo,
+    normal and depth planes of render_features (other planes are ignored), all numpy float32 arrays (the
+    host loop) or all CUDA float32 tensors (the kernels, enqueued on `stream`). A tile share or a slab
+    lacks its neighbours: gather the frame first. params: a DenoiseParams (None: denoise_params_default()).
+    Returns out (a new array or tensor unless given). The workspace is allocated once per side and kept;
+    calls on one side must not overlap."""
+    n_px = int(g.xRes) * int(g.yRes)
+    cp, side = _ptr(colour)
+    from ._lib import Features
+    f = Features()
+    for name, need in (("albedo", 3 * n_px), ("normal", 3 * n_px), ("depth", n_px)):
+        if name not in feats:
+            raise DTError("denoise: the %s plane is missing" % name)
+        a = feats[name]
+        p, dev = _ptr(a)
+        have = a.numel() if hasattr(a, "numel") else a.size
+        if have != need:
+            raise DTError("denoise: plane %s holds %d elements, %dx%d needs %d" % (name, have, g.xRes, g.yRes, need))
+        if dev != side:
+            raise DTError("denoise: colour and the planes must all be on the same side")
+        setattr(f, name, p)
+    have = colour.numel() if hasattr(colour, "numel") else colour.size
+    if have != 3 * n_px:
+        raise DTError("denoise: colour holds %d elements, %dx%d needs %d" % (have, g.xRes, g.yRes, 3 * n_px))
+    if out is None:
+        if side:
+            import torch
+            out = torch.empty_like(colour)
+        else:
+            import numpy as np
+            out = np.empty(3 * n_px, np.float32)
+    op, odev = _ptr(out)
+    if odev != side or (out.numel() if hasattr(out, "numel") else out.size) != 3 * n_px:
+        raise DTError("denoise: out must hold %d elements on the side of colour" % (3 * n_px))
+    params = params if params is not None else denoise_params_default()
+    n_work = int(lib.dt_denoise_workspace_floats(g.xRes, g.yRes, ctypes.byref(params)))
+    if n_work < 0:
+        check(n_work, "dt_denoise_workspace_floats")
+    work = _denoise_workspace(n_work, side, colour)
+    wp, _ = _ptr(work)
+    check(lib.dt_denoise(g.xRes, g.yRes, cp, ctypes.byref(f), ctypes.byref(params), op, wp, side,
+                         ctypes.c_void_p(stream) if stream else None, None), "dt_denoise")
+    return out
+
+
+_denoise = denoise   # (renderImage's denoise argument hides the name)
+
+
 def render_sky(g, frame, out, tile=None, stream=None):
     """renderImageCloud's pixel loop (sky only) into `out`."""
     st = Stats()
@@ -404,6 +480,16 @@ class Progressive:
         if self.samples_done < 1:
             raise DTError("Progressive.features: no window rendered yet")
         return render_features(self.scene, self.g, self.frame, self.samples_done, self.tile, planes=planes)
+
+    def denoised(self, params=None, out=None):
+        """The denoised preview: image() and features() of the samples so far through denoise(), on the
+        device (a CUDA float32 tensor like image()). Whole frames only: a tile share or a slab lacks the
+        neighbours the filter reads. The accumulator is not touched."""
+        t = self.tile
+        if t.layout != DT_OUT_IMAGE or t.world != 1 or t.x0 != 0 or t.y0 != 0 \
+                or (t.x1 > 0 and t.x1 < self.g.xRes) or (t.y1 > 0 and t.y1 < self.g.yRes):
+            raise DTError("Progressive.denoised: needs the whole frame (DT_OUT_IMAGE, world 1, no window)")
+        return denoise(self.g, self.image(), self.features(planes=("albedo", "normal", "depth")), params, out)
 
     def run(self, until=None, n_chunks=1):
         """step() until done, or until until(self) returns true after a step."""
@@ -614,8 +700,15 @@ def write_png(filename, g, values):
     check(lib.dt_write_png(filename.encode(), g.xRes, g.yRes, ctypes.c_void_p(v.ctypes.data)), "dt_write_png")
 
 
+def denoised_filename(filename):
+    """<stem>.denoised.<ext> beside the frame file (as `dtrender --denoise` names it)"""
+    import os
+    stem, ext = os.path.splitext(filename)
+    return stem + ".denoised" + ext
+
+
 def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progressive=None, adaptive=None,
-                features=None):
+                features=None, denoise=None):
     """render_final_project.cpp:965: build (sceneBuilder names a scene.h builder), render the
     frame on the current GPU, write the PPM. Returns (image, stats). progressive=callback renders in
     one-chunk sample windows (Progressive) and calls callback(image, samples_done) with the resolved
@@ -624,7 +717,10 @@ def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progr
     converged pixels stop between windows, every pixel is the mean of its own samples; a progressive
     callback is called after every window as well. features=prefix also writes the first-hit feature images
     of all spp samples, prefix.albedo.png, prefix.normal.png, prefix.depth.png and prefix.coverage.png
-    (feature_images), as `dtrender --features` does."""
+    (feature_images), as `dtrender --features` does. denoise=True or a DenoiseParams also writes the
+    denoised frame (denoise() of the image and the feature planes of the samples taken) to
+    denoised_filename(filename), as `dtrender --denoise` does; the frame file's bytes are unchanged. A
+    scene with a RectPrismWithCylinder has no feature planes: DTError (DT_E_UNSUPPORTED)."""
     import numpy as np
     g = g if g is not None else globals_default()
     built = build_scene(sceneBuilder, frame if builder_frame is None else builder_frame, g)
@@ -651,6 +747,13 @@ def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progr
         planes = render_features(scene, g, frame, planes=("albedo", "normal", "depth", "coverage"))
         for name, v in feature_images(g, {k: t.cpu().numpy() for k, t in planes.items()}).items():
             write_png("%s.%s.png" % (features, name), g, v)
+    if denoise and filename:
+        import torch
+        n = p.samples_done if adaptive is not None else None
+        planes = render_features(scene, g, frame, n, planes=("albedo", "normal", "depth"))
+        clean = _denoise(g, torch.from_numpy(img).to("cuda"), planes, None if denoise is True else denoise)
+        dn = denoised_filename(filename)
+        (write_png if dn.endswith(".png") else write_ppm)(dn, g, clean.cpu().numpy())
     scene.close()
     return img, st
 

@@ -99,6 +99,12 @@ class Features(ctypes.Structure):
                 ("coverage", ctypes.c_void_p), ("shape", ctypes.c_void_p)]
 
 
+class DenoiseParams(ctypes.Structure):
+    """dt_denoise_params: levels 1..6, demodulate 0/1, the four edge-stopping widths (> 0, inf: term off)"""
+    _fields_ = [("levels", c_int32), ("demodulate", c_int32), ("sigma_normal", c_float), ("sigma_depth", c_float),
+                ("sigma_colour", c_float), ("sigma_albedo", c_float)]
+
+
 class BVHNode(ctypes.Structure):
     _fields_ = [("first_child", c_int32), ("n_children", c_int32), ("first_index", c_int32),
                 ("n_indices", c_int32), ("leaf", c_int32), ("depth", c_int32), ("lbound", D3), ("ubound", D3)]
@@ -129,7 +135,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_debug_load_obj",
            "dt_accum_doubles", "dt_window_check", "dt_render_window", "dt_render_window_async", "dt_resolve",
            "dt_adapt_converged", "dt_render_window_adaptive", "dt_render_window_adaptive_async",
-           "dt_resolve_adaptive", "dt_adapt_select_ms", "dt_render_features"]
+           "dt_resolve_adaptive", "dt_adapt_select_ms", "dt_render_features",
+           "dt_denoise_params_default", "dt_denoise_workspace_floats", "dt_denoise"]
 
 
 class DTError(RuntimeError):
@@ -209,6 +216,10 @@ def _load():
                                            ctypes.c_void_p, c_int32, ctypes.c_void_p, P(c_float)]),
         "dt_render_features": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, P(Features), c_int32,
                                          ctypes.c_void_p, P(Stats)]),
+        "dt_denoise_params_default": (None, [P(DenoiseParams)]),
+        "dt_denoise_workspace_floats": (c_int64, [c_int32, c_int32, P(DenoiseParams)]),
+        "dt_denoise": (c_int32, [c_int32, c_int32, ctypes.c_void_p, P(Features), P(DenoiseParams), ctypes.c_void_p,
+                                 ctypes.c_void_p, c_int32, ctypes.c_void_p, P(c_float)]),
         "dt_unpack_slabs": (c_int32, [P(Globals), P(Tiles), c_int32, ctypes.c_void_p, ctypes.c_void_p, c_int32,
                                       ctypes.c_void_p]),
         "dt_build_scene": (c_int32, [ctypes.c_char_p, c_float, P(Globals), ctypes.c_char_p, P(P(SceneDesc))]),

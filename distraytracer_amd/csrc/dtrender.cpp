@@ -25,6 +25,11 @@
 //                     0.5*coverage)*255), PREFIX.depth.png (depth / the frame's largest depth, grey) and
 //                     PREFIX.coverage.png (grey), each clamped to 0..255. The frame file is the same bytes
 //                     as without the flag.
+//   --denoise         also write the denoised frame (dt_denoise with the default parameters on the frame
+//                     and the albedo, normal and depth planes of the samples taken, on the device) to
+//                     <stem>.denoised.<ext> beside the frame; with --progressive or --adaptive that file is
+//                     overwritten after every window as well. --denoise-levels N: a-trous levels (1..6,
+//                     default 5). The frame file is the same bytes as without the flag.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -42,6 +47,44 @@ static int die(const char* what, int rc)
   return 1;
 }
 
+// --denoise: `img` (host, the frame or a preview of the first n_samples samples of every pixel) and the
+// feature planes of those samples through dt_denoise on the device, written to `fn`
+static int write_denoised(const dt_scene* s, const dt_globals& g, int frame, int n_samples, int levels,
+                          const std::vector<float>& img, const std::string& fn, bool png)
+{
+  const size_t n_px = (size_t)g.xRes * g.yRes;
+  dt_denoise_params dp;
+  dt_denoise_params_default(&dp);
+  if (levels > 0) dp.levels = levels;
+  const int64_t n_work = dt_denoise_workspace_floats(g.xRes, g.yRes, &dp);
+  if (n_work < 0) return die("dt_denoise_workspace_floats", (int)n_work);
+  // colour, albedo, normal (3 per pixel), depth (1), out (3), then the workspace
+  float* d = nullptr;
+  if (hipMalloc((void**)&d, (13 * n_px + (size_t)n_work) * sizeof(float)) != hipSuccess ||
+      hipMemset(d, 0, 13 * n_px * sizeof(float)) != hipSuccess ||
+      hipMemcpy(d, img.data(), 3 * n_px * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+    fprintf(stderr, "denoise buffers: hipMalloc failed\n");
+    return 1;
+  }
+  dt_features f;
+  memset(&f, 0, sizeof f);
+  f.albedo = d + 3 * n_px; f.normal = d + 6 * n_px; f.depth = d + 9 * n_px;
+  float* out = d + 10 * n_px;
+  int rc = dt_render_features(s, &g, frame, nullptr, n_samples, &f, 1, nullptr, nullptr);
+  if (rc) return die("dt_render_features", rc);
+  rc = dt_denoise(g.xRes, g.yRes, d, &f, &dp, out, d + 13 * n_px, 1, nullptr, nullptr);
+  if (rc) return die("dt_denoise", rc);
+  std::vector<float> clean(3 * n_px);
+  if (hipMemcpy(clean.data(), out, 3 * n_px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+    fprintf(stderr, "denoise: hipMemcpy failed\n");
+    return 1;
+  }
+  (void)hipFree(d);
+  rc = png ? dt_write_png(fn.c_str(), g.xRes, g.yRes, clean.data()) : dt_write_ppm(fn.c_str(), g.xRes, g.yRes, clean.data());
+  if (rc) return die("dt_write_ppm/png (denoised)", rc);
+  return 0;
+}
+
 int main(int argc, char** argv)
 {
   dt_globals g;
@@ -51,7 +94,7 @@ int main(int argc, char** argv)
   int arg = (argc > 2 && argv[2][0] != '-') ? atoi(argv[2]) : 0;
   std::string out;
   std::string data_dir = DT_DATA_DIR;
-  int spp = -1, depth = -1, W = -1, H = -1, progressive = 0, min_samples = 64;
+  int spp = -1, depth = -1, W = -1, H = -1, progressive = 0, min_samples = 64, denoise = 0, denoise_levels = 0;
   double adaptive = -1.0;
   std::string counts_file, features_prefix;
   for (int i = 2; i < argc; ++i) {
@@ -67,6 +110,8 @@ int main(int argc, char** argv)
     else if (a == "--min-samples" && i + 1 < argc) min_samples = atoi(argv[++i]);
     else if (a == "--counts" && i + 1 < argc) counts_file = argv[++i];
     else if (a == "--features" && i + 1 < argc) features_prefix = argv[++i];
+    else if (a == "--denoise") denoise = 1;
+    else if (a == "--denoise-levels" && i + 1 < argc) denoise_levels = atoi(argv[++i]);
   }
   std::string scene = "final";
   float build_frame = 0;
@@ -126,6 +171,12 @@ int main(int argc, char** argv)
   dt_stats st;
   std::string fn = out.empty() ? std::string(buf) : out;
   const bool png = fn.size() > 4 && fn.compare(fn.size() - 4, 4, ".png") == 0;
+  // <stem>.denoised.<ext> beside the frame
+  const size_t slash = fn.find_last_of('/'), dot = fn.find_last_of('.');
+  const bool has_ext = dot != std::string::npos && dot > (slash == std::string::npos ? 0 : slash + 1);
+  const std::string dn_fn = has_ext ? fn.substr(0, dot) + ".denoised" + fn.substr(dot) : fn + ".denoised";
+  int samples_taken = (int)sqrt((double)g.antialias_samples);
+  samples_taken *= samples_taken;
   if (adaptive >= 0.0) {
     // one-chunk windows over the live, unconverged pixels until a window traces none or all samples
     // are rendered; every pixel resolved with its own count
@@ -152,6 +203,16 @@ int main(int argc, char** argv)
       printf("%d/%d: %llu pixels\n", end, total, (unsigned long long)st.pixels);
       fflush(stdout);
       begin = end;
+      samples_taken = end;
+      if (denoise) {
+        rc = dt_resolve_adaptive(&g, nullptr, acc, cnt, dimg, 1, nullptr, nullptr);
+        if (rc) return die("dt_resolve_adaptive", rc);
+        if (hipMemcpy(img.data(), dimg, n_acc * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+          fprintf(stderr, "preview: hipMemcpy failed\n");
+          return 1;
+        }
+        if (write_denoised(s, g, frame, end, denoise_levels, img, dn_fn, png)) return 1;
+      }
       if (st.pixels == 0) break;
     }
     rc = dt_resolve_adaptive(&g, nullptr, acc, cnt, dimg, 1, nullptr, nullptr);
@@ -206,6 +267,7 @@ int main(int argc, char** argv)
       }
       rc = png ? dt_write_png(fn.c_str(), g.xRes, g.yRes, img.data()) : dt_write_ppm(fn.c_str(), g.xRes, g.yRes, img.data());
       if (rc) return die("dt_write_ppm/png", rc);
+      if (denoise && write_denoised(s, g, frame, end, denoise_levels, img, dn_fn, png)) return 1;
       printf("%d/%d\n", end, total);
       fflush(stdout);
       begin = end;
@@ -218,6 +280,7 @@ int main(int argc, char** argv)
     if (rc) return die("dt_render", rc);
     rc = png ? dt_write_png(fn.c_str(), g.xRes, g.yRes, img.data()) : dt_write_ppm(fn.c_str(), g.xRes, g.yRes, img.data());
     if (rc) return die("dt_write_ppm/png", rc);
+    if (denoise && write_denoised(s, g, frame, samples_taken, denoise_levels, img, dn_fn, png)) return 1;
   }
   if (!features_prefix.empty()) {
     const int n = (int)sqrt((double)g.antialias_samples);

@@ -51,6 +51,8 @@ extern "C" {
  *    dt_render_window_adaptive_async, dt_resolve_adaptive, dt_adapt_select_ms -- adaptive sampling) */
 /* (still 8, new exports only, no struct changed: dt_render_features and its dt_features argument --
  *    first-hit feature buffers) */
+/* (still 8, new exports and one new struct, no struct changed: dt_denoise_params_default,
+ *    dt_denoise_workspace_floats, dt_denoise and its dt_denoise_params -- preview denoising) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -494,6 +496,67 @@ typedef struct dt_features {      /* each plane optional (NULL: not wanted); all
 int dt_render_features(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
                        int32_t n_samples, const dt_features* out, int32_t out_on_device,
                        void* stream, dt_stats* stats);
+
+/* ---- feature-guided denoising of previews: an edge-avoiding a-trous filter ----
+ * No reference counterpart. The consumer of the feature buffers: (preview, albedo, normal, depth) ->
+ * a clean preview, by the edge-avoiding a-trous wavelet filter of Dammertz et al. 2010, demodulated by
+ * the first-hit albedo. Whole frames only, DT_OUT_IMAGE indexing, W = xRes, H = yRes: pixel slot
+ * q = r*W + x with r the buffer row (a tile share or a slab lacks its neighbours and is not accepted:
+ * gather the frame first). colour C[3q+k] is what dt_render / dt_resolve give (0..255); A, N (3 per
+ * pixel) and Z (1 per pixel) are the albedo, normal and depth planes of dt_render_features. Coverage is
+ * not read: A and N are premultiplied by it, which is what separates silhouette pixels.
+ *
+ * All arithmetic is IEEE f32, every operation below one rounded operation (no contraction), the same
+ * on the host and on the device. Constants, computed on the host:
+ *   isn = 1.0f/(sn*sn)   isa = 1.0f/(sa*sa)           sn, sz, sc, sa: sigma_normal, _depth, _colour, _albedo
+ *   isc_l = 1.0f/((sc*2^-l)*(sc*2^-l))                the colour width halves per level
+ *   isz_l = 1.0f/((sz*2^l)*(sz*2^l))                  the depth width grows with the step
+ * Prepare, per pixel p:
+ *   d[k] = demodulate ? fmaxf(A_p[k], 0.0625f) : 1.0f     E0_p[k] = C_p[k] / d[k]
+ *   rz_p = 1.0f / (Z_p*Z_p + 1e-6f)
+ * Level l = 0 .. levels-1, step s = 1 << l, pixel p = (r, x): taps j = -2..2 (outer), i = -2..2 (inner),
+ * q = (r + j*s, x + i*s); a tap outside the image is skipped (no clamping, no mirroring):
+ *   h  = K[|i|] * K[|j|]                     K = {0.375, 0.25, 0.0625}
+ *   dn = N_p - N_q ; xn = ((dn0*dn0 + dn1*dn1) + dn2*dn2) * isn
+ *   da = A_p - A_q ; xa = (same shape) * isa
+ *   de = E_p - E_q ; xc = (same shape) * isc_l          (E: this level's input)
+ *   dz = Z_p - Z_q ; xz = ((dz*dz) * rz_p) * isz_l
+ *   R(x) = t*t with t = fmaxf(0.0f, 1.0f - x)           (fmaxf drops a NaN: weight 0)
+ *   w  = (h * (R(xn) * R(xz))) * (R(xa) * R(xc))
+ *   if (w > 0) { S[k] = S[k] + w * E_q[k] (k = 0,1,2) ; Wt = Wt + w }       S, Wt from 0
+ *   E'_p[k] = Wt > 0 ? S[k] / Wt : E_p[k]
+ * Finish: out[3p+k] = fminf(fmaxf(E_L[k] * d[k], 0.0f), 255.0f). A pixel whose input colour has a NaN
+ * channel is copied to out unchanged (all three channels); by R it never contributes to a neighbour.
+ * The edge-stopping function is a compact polynomial, not exp: no libm on either side, so the output
+ * is specified bit for bit. Limits: first-hit guides only (a mirror's or a glass pane's reflection is
+ * filtered by the colour term alone); no variance guidance.
+ *
+ * levels: 1..6. Each sigma > 0; +inf disables its term. dt_denoise_params_default: levels 5,
+ * demodulate 1 and the sigmas chosen in BASELINE.md. */
+typedef struct dt_denoise_params {
+  int32_t levels;        /* 1..6 */
+  int32_t demodulate;    /* 0 or 1 */
+  float   sigma_normal;  /* edge-stopping width on the normal */
+  float   sigma_depth;   /* ... on the relative depth */
+  float   sigma_colour;  /* ... on the (demodulated) colour */
+  float   sigma_albedo;  /* ... on the albedo */
+} dt_denoise_params;
+
+void    dt_denoise_params_default(dt_denoise_params* p);
+/* the floats of scratch dt_denoise needs for an xRes x yRes frame (the ping-pong buffers of E and the
+ * packed guides; the layout is the implementation's). < 0: xRes or yRes < 1, or p given and invalid. */
+int64_t dt_denoise_workspace_floats(int32_t xRes, int32_t yRes, const dt_denoise_params* p);
+/* feat needs albedo, normal and depth; its other planes are ignored. colour, the planes, out and work
+ * all on one side: host (on_device=0: a plain loop) or device (1: kernels on `stream`, enqueue only;
+ * with kernel_ms they are timed with HIP events and the call synchronises). out: 3*xRes*yRes floats,
+ * not aliasing colour or work; nothing outside them is written. work: caller-owned,
+ * dt_denoise_workspace_floats floats; nothing in it survives a call. No scene, globals or tiles: any
+ * whole-frame image, a frame gathered from several ranks included. DT_E_INVALID before any device work,
+ * with a dt_last_error naming the argument: a null argument or a missing plane, xRes or yRes < 1, levels
+ * outside 1..6, demodulate not 0 or 1, a sigma that is <= 0 or NaN, aliasing. */
+int     dt_denoise(int32_t xRes, int32_t yRes, const float* colour, const dt_features* feat,
+                   const dt_denoise_params* p, float* out, float* work, int32_t on_device,
+                   void* stream, float* kernel_ms);
 
 /* renderImageCloud (render_final_project.cpp:1224-1279). Sets eye/up/lookingAt as the
  * reference does (1227-1229) on a local copy; g is not modified. */
