@@ -14,7 +14,7 @@ an error (there is no CPU path in this package).
 """
 import ctypes
 
-from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT, DT_OUT_IMAGE, DT_OUT_SLAB, AccelInfo, BVHNode, DenoiseParams, DTError, Globals, SceneDesc,
+from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT, DT_OUT_IMAGE, DT_OUT_SLAB, AccelInfo, BVHNode, DenoiseParams, DenoiseVarParams, DTError, Globals, SceneDesc,
                    Stats, Tiles, check, lib)
 
 __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_scene", "Scene",
@@ -24,7 +24,8 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "accum_doubles", "window_check", "render_window", "render_window_async", "resolve", "Progressive",
            "mean_abs_change", "adapt_converged", "render_window_adaptive", "resolve_adaptive", "adapt_select_ms",
            "AdaptiveProgressive", "render_features", "feature_images", "FEATURE_PLANES",
-           "DenoiseParams", "denoise_params_default", "denoise", "denoised_filename"]
+           "DenoiseParams", "denoise_params_default", "denoise", "denoised_filename",
+           "DenoiseVarParams", "denoise_var_params_default", "variance"]
 
 
 def globals_default():
@@ -263,6 +264,13 @@ def denoise_params_default():
     return p
 
 
+def denoise_var_params_default():
+    """dt_denoise_var_params_default: levels 5, demodulate 1 and the values chosen in BASELINE.md."""
+    p = DenoiseVarParams()
+    lib.dt_denoise_var_params_default(ctypes.byref(p))
+    return p
+
+
 _denoise_work = {}   # side (0 host, 1 + device index) -> the workspace last allocated there
 
 
@@ -280,16 +288,30 @@ def _denoise_workspace(n, dev, like):
     return w
 
 
-def denoise(g, colour, feats, params=None, out=None, stream=None):
+def denoise(g, colour, feats, params=None, out=None, stream=None, variance=None):
     """The edge-avoiding a-trous filter of include/dt.h dt_denoise on a whole frame of g.xRes x g.yRes:
     colour (3 floats per pixel, as render / Progressive.image give it) and feats, a dict with the albedo,
     normal and depth planes of render_features (other planes are ignored), all numpy float32 arrays (the
     host loop) or all CUDA float32 tensors (the kernels, enqueued on `stream`). A tile share or a slab
     lacks its neighbours: gather the frame first. params: a DenoiseParams (None: denoise_params_default()).
+    With variance, the plane variance() gives (3 floats per pixel, on the side of colour), the filter is
+    dt_denoise_var, whose colour width follows every pixel's own noise, and params is a DenoiseVarParams
+    (None: denoise_var_params_default()).
     Returns out (a new array or tensor unless given). The workspace is allocated once per side and kept;
     calls on one side must not overlap."""
     n_px = int(g.xRes) * int(g.yRes)
     cp, side = _ptr(colour)
+    if variance is not None:
+        if params is not None and not isinstance(params, DenoiseVarParams):
+            raise DTError("denoise: with a variance plane params must be a DenoiseVarParams")
+        vp, vdev = _ptr(variance)
+        have = variance.numel() if hasattr(variance, "numel") else variance.size
+        if have != 3 * n_px:
+            raise DTError("denoise: variance holds %d elements, %dx%d needs %d" % (have, g.xRes, g.yRes, 3 * n_px))
+        if vdev != side:
+            raise DTError("denoise: colour and the variance plane must be on the same side")
+    elif isinstance(params, DenoiseVarParams):
+        raise DTError("denoise: a DenoiseVarParams needs a variance plane")
     from ._lib import Features
     f = Features()
     for name, need in (("albedo", 3 * n_px), ("normal", 3 * n_px), ("depth", n_px)):
@@ -316,6 +338,16 @@ def denoise(g, colour, feats, params=None, out=None, stream=None):
     op, odev = _ptr(out)
     if odev != side or (out.numel() if hasattr(out, "numel") else out.size) != 3 * n_px:
         raise DTError("denoise: out must hold %d elements on the side of colour" % (3 * n_px))
+    st = ctypes.c_void_p(stream) if stream else None
+    if variance is not None:
+        params = params if params is not None else denoise_var_params_default()
+        n_work = int(lib.dt_denoise_var_workspace_floats(g.xRes, g.yRes, ctypes.byref(params)))
+        if n_work < 0:
+            check(n_work, "dt_denoise_var_workspace_floats")
+        wp, _ = _ptr(_denoise_workspace(n_work, side, colour))
+        check(lib.dt_denoise_var(g.xRes, g.yRes, cp, vp, ctypes.byref(f), ctypes.byref(params), op, wp, side, st, None),
+              "dt_denoise_var")
+        return out
     params = params if params is not None else denoise_params_default()
     n_work = int(lib.dt_denoise_workspace_floats(g.xRes, g.yRes, ctypes.byref(params)))
     if n_work < 0:
@@ -481,15 +513,23 @@ class Progressive:
             raise DTError("Progressive.features: no window rendered yet")
         return render_features(self.scene, self.g, self.frame, self.samples_done, self.tile, planes=planes)
 
-    def denoised(self, params=None, out=None):
+    def _variance_plane(self):
+        raise DTError("Progressive.denoised(variance=True): the sums of squares live in AdaptiveProgressive; "
+                      "with min_samples >= spp it never stops a pixel and renders this frame's bits")
+
+    def denoised(self, params=None, out=None, variance=False):
         """The denoised preview: image() and features() of the samples so far through denoise(), on the
         device (a CUDA float32 tensor like image()). Whole frames only: a tile share or a slab lacks the
-        neighbours the filter reads. The accumulator is not touched."""
+        neighbours the filter reads. The accumulator is not touched. variance=True (AdaptiveProgressive
+        only: it keeps the sums of squares) filters with the per-pixel colour width of dt_denoise_var on
+        variance(); params is then a DenoiseVarParams or None."""
+        vplane = self._variance_plane() if variance else None
         t = self.tile
         if t.layout != DT_OUT_IMAGE or t.world != 1 or t.x0 != 0 or t.y0 != 0 \
                 or (t.x1 > 0 and t.x1 < self.g.xRes) or (t.y1 > 0 and t.y1 < self.g.yRes):
             raise DTError("Progressive.denoised: needs the whole frame (DT_OUT_IMAGE, world 1, no window)")
-        return denoise(self.g, self.image(), self.features(planes=("albedo", "normal", "depth")), params, out)
+        return denoise(self.g, self.image(), self.features(planes=("albedo", "normal", "depth")), params, out,
+                       variance=vplane)
 
     def run(self, until=None, n_chunks=1):
         """step() until done, or until until(self) returns true after a step."""
@@ -598,6 +638,40 @@ def resolve_adaptive(g, accum, count, out, tile=None, stream=None):
     return nan.value
 
 
+def variance(g, accum, accum2, count, out=None, tile=None, stream=None):
+    """The variance of the mean of every channel's sample colours, in grey levels squared of the 0..255
+    output (dt_variance): 0 where a pixel has fewer than two samples. accum, accum2 (float64) and count
+    (int32 for torch, uint32 / int32 for numpy) as render_window_adaptive keeps them, all numpy arrays (a
+    loop) or all CUDA tensors (a kernel, enqueued on `stream`). Returns out (float32, indexed like the
+    accumulator and the colour image; a new array or tensor unless given)."""
+    ap, adev = _ptr_typed(accum, "torch.float64", "float64")
+    bp, bdev = _ptr_typed(accum2, "torch.float64", "float64")
+    if hasattr(count, "data_ptr"):
+        cp, cdev = _ptr_typed(count, "torch.int32", "int32")
+    else:
+        cp, cdev = _ptr_typed(count, "", "int32" if str(count.dtype) == "int32" else "uint32")
+    need = accum_doubles(g, tile)
+    if out is None:
+        if adev:
+            import torch
+            out = torch.empty(max(need, 1), dtype=torch.float32, device=accum.device)
+        else:
+            import numpy as np
+            out = np.empty(need, np.float32)
+    op, odev = _ptr(out)
+    if not adev == bdev == cdev == odev:
+        raise DTError("variance: accum, accum2, count and out must be on the same side")
+    for a, k in ((accum, 1), (accum2, 1), (out, 1), (count, 3)):
+        if k * (a.numel() if hasattr(a, "numel") else a.size) < need:
+            raise DTError("variance: (g, tile) need %d elements" % (need // k))
+    check(lib.dt_variance(ctypes.byref(g), ctypes.byref(tile) if tile else None, ap, bp, cp, op, adev,
+                          ctypes.c_void_p(stream) if stream else None), "dt_variance")
+    return out
+
+
+_variance = variance   # (denoised's variance argument hides the name)
+
+
 class AdaptiveProgressive(Progressive):
     """Progressive with adaptive sampling: between windows, pixels whose mean has converged stop.
 
@@ -659,6 +733,16 @@ class AdaptiveProgressive(Progressive):
         self.nan_pixels = resolve_adaptive(self.g, self.accum, self.count, out, self.tile)
         return out
 
+    def variance(self, out=None):
+        """The variance of the mean of every pixel's samples so far, per channel, in grey levels squared
+        (variance(): a CUDA float32 tensor indexed like image(); 0 where a pixel has fewer than two samples)."""
+        if self.samples_done < 1:
+            raise DTError("AdaptiveProgressive.variance: no window rendered yet")
+        return _variance(self.g, self.accum, self.accum2, self.count, out, self.tile)
+
+    def _variance_plane(self):
+        return self.variance()
+
     def state(self):
         d = super().state()
         d.update({"accum2": self.accum2.cpu().numpy().copy(), "count": self.count.cpu().numpy().copy(),
@@ -719,9 +803,14 @@ def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progr
     of all spp samples, prefix.albedo.png, prefix.normal.png, prefix.depth.png and prefix.coverage.png
     (feature_images), as `dtrender --features` does. denoise=True or a DenoiseParams also writes the
     denoised frame (denoise() of the image and the feature planes of the samples taken) to
-    denoised_filename(filename), as `dtrender --denoise` does; the frame file's bytes are unchanged. A
+    denoised_filename(filename), as `dtrender --denoise` does; the frame file's bytes are unchanged.
+    denoise="variance" or a DenoiseVarParams filters with the per-pixel colour width of dt_denoise_var on the
+    adaptive sampler's variance, as `dtrender --denoise-variance` does; it needs adaptive (DTError without). A
     scene with a RectPrismWithCylinder has no feature planes: DTError (DT_E_UNSUPPORTED)."""
     import numpy as np
+    by_variance = isinstance(denoise, DenoiseVarParams) or (isinstance(denoise, str) and denoise == "variance")
+    if by_variance and adaptive is None:
+        raise DTError("renderImage: denoise by variance needs adaptive=tol (the sums of squares are adaptive sampling's)")
     g = g if g is not None else globals_default()
     built = build_scene(sceneBuilder, frame if builder_frame is None else builder_frame, g)
     scene = Scene(built, g)
@@ -751,7 +840,11 @@ def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progr
         import torch
         n = p.samples_done if adaptive is not None else None
         planes = render_features(scene, g, frame, n, planes=("albedo", "normal", "depth"))
-        clean = _denoise(g, torch.from_numpy(img).to("cuda"), planes, None if denoise is True else denoise)
+        if by_variance:
+            clean = _denoise(g, torch.from_numpy(img).to("cuda"), planes, None if denoise == "variance" else denoise,
+                             variance=p.variance())
+        else:
+            clean = _denoise(g, torch.from_numpy(img).to("cuda"), planes, None if denoise is True else denoise)
         dn = denoised_filename(filename)
         (write_png if dn.endswith(".png") else write_ppm)(dn, g, clean.cpu().numpy())
     scene.close()

@@ -105,6 +105,13 @@ class DenoiseParams(ctypes.Structure):
                 ("sigma_colour", c_float), ("sigma_albedo", c_float)]
 
 
+class DenoiseVarParams(ctypes.Structure):
+    """dt_denoise_var_params: levels 1..6, demodulate 0/1, the guide widths of DenoiseParams, sigma_variance (the
+    colour width in standard deviations of the pixel's own noise; > 0, inf: term off), variance_floor (finite, > 0)"""
+    _fields_ = [("levels", c_int32), ("demodulate", c_int32), ("sigma_normal", c_float), ("sigma_depth", c_float),
+                ("sigma_albedo", c_float), ("sigma_variance", c_float), ("variance_floor", c_float), ("_pad", c_float)]
+
+
 class BVHNode(ctypes.Structure):
     _fields_ = [("first_child", c_int32), ("n_children", c_int32), ("first_index", c_int32),
                 ("n_indices", c_int32), ("leaf", c_int32), ("depth", c_int32), ("lbound", D3), ("ubound", D3)]
@@ -136,7 +143,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_accum_doubles", "dt_window_check", "dt_render_window", "dt_render_window_async", "dt_resolve",
            "dt_adapt_converged", "dt_render_window_adaptive", "dt_render_window_adaptive_async",
            "dt_resolve_adaptive", "dt_adapt_select_ms", "dt_render_features",
-           "dt_denoise_params_default", "dt_denoise_workspace_floats", "dt_denoise"]
+           "dt_denoise_params_default", "dt_denoise_workspace_floats", "dt_denoise",
+           "dt_variance", "dt_denoise_var_params_default", "dt_denoise_var_workspace_floats", "dt_denoise_var"]
 
 
 class DTError(RuntimeError):
@@ -220,6 +228,12 @@ def _load():
         "dt_denoise_workspace_floats": (c_int64, [c_int32, c_int32, P(DenoiseParams)]),
         "dt_denoise": (c_int32, [c_int32, c_int32, ctypes.c_void_p, P(Features), P(DenoiseParams), ctypes.c_void_p,
                                  ctypes.c_void_p, c_int32, ctypes.c_void_p, P(c_float)]),
+        "dt_variance": (c_int32, [P(Globals), P(Tiles), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                  c_int32, ctypes.c_void_p]),
+        "dt_denoise_var_params_default": (None, [P(DenoiseVarParams)]),
+        "dt_denoise_var_workspace_floats": (c_int64, [c_int32, c_int32, P(DenoiseVarParams)]),
+        "dt_denoise_var": (c_int32, [c_int32, c_int32, ctypes.c_void_p, ctypes.c_void_p, P(Features), P(DenoiseVarParams),
+                                     ctypes.c_void_p, ctypes.c_void_p, c_int32, ctypes.c_void_p, P(c_float)]),
         "dt_unpack_slabs": (c_int32, [P(Globals), P(Tiles), c_int32, ctypes.c_void_p, ctypes.c_void_p, c_int32,
                                       ctypes.c_void_p]),
         "dt_build_scene": (c_int32, [ctypes.c_char_p, c_float, P(Globals), ctypes.c_char_p, P(P(SceneDesc))]),

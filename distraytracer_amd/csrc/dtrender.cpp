@@ -30,6 +30,9 @@
 //                     <stem>.denoised.<ext> beside the frame; with --progressive or --adaptive that file is
 //                     overwritten after every window as well. --denoise-levels N: a-trous levels (1..6,
 //                     default 5). The frame file is the same bytes as without the flag.
+//   --denoise-variance  as --denoise, with the variance-guided filter: dt_variance of the adaptive sampler's
+//                     sums, then dt_denoise_var with the default parameters (--denoise-levels applies).
+//                     Needs --adaptive: a usage error and exit status 2 without it, before any rendering.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -47,18 +50,30 @@ static int die(const char* what, int rc)
   return 1;
 }
 
+// the adaptive sampler's device buffers (--denoise-variance filters by them; all null: --denoise)
+struct adaptive_sums {
+  const double *acc, *acc2;
+  const uint32_t* cnt;
+};
+
 // --denoise: `img` (host, the frame or a preview of the first n_samples samples of every pixel) and the
-// feature planes of those samples through dt_denoise on the device, written to `fn`
+// feature planes of those samples through dt_denoise on the device, written to `fn`; with sums, through
+// dt_variance and dt_denoise_var
 static int write_denoised(const dt_scene* s, const dt_globals& g, int frame, int n_samples, int levels,
-                          const std::vector<float>& img, const std::string& fn, bool png)
+                          const std::vector<float>& img, const std::string& fn, bool png,
+                          const adaptive_sums* sums = nullptr)
 {
   const size_t n_px = (size_t)g.xRes * g.yRes;
   dt_denoise_params dp;
   dt_denoise_params_default(&dp);
   if (levels > 0) dp.levels = levels;
-  const int64_t n_work = dt_denoise_workspace_floats(g.xRes, g.yRes, &dp);
+  dt_denoise_var_params vp;
+  dt_denoise_var_params_default(&vp);
+  if (levels > 0) vp.levels = levels;
+  const int64_t n_work = sums ? dt_denoise_var_workspace_floats(g.xRes, g.yRes, &vp) + 3 * (int64_t)n_px
+                              : dt_denoise_workspace_floats(g.xRes, g.yRes, &dp);
   if (n_work < 0) return die("dt_denoise_workspace_floats", (int)n_work);
-  // colour, albedo, normal (3 per pixel), depth (1), out (3), then the workspace
+  // colour, albedo, normal (3 per pixel), depth (1), out (3), then (the variance plane, 3, and) the workspace
   float* d = nullptr;
   if (hipMalloc((void**)&d, (13 * n_px + (size_t)n_work) * sizeof(float)) != hipSuccess ||
       hipMemset(d, 0, 13 * n_px * sizeof(float)) != hipSuccess ||
@@ -72,8 +87,16 @@ static int write_denoised(const dt_scene* s, const dt_globals& g, int frame, int
   float* out = d + 10 * n_px;
   int rc = dt_render_features(s, &g, frame, nullptr, n_samples, &f, 1, nullptr, nullptr);
   if (rc) return die("dt_render_features", rc);
-  rc = dt_denoise(g.xRes, g.yRes, d, &f, &dp, out, d + 13 * n_px, 1, nullptr, nullptr);
-  if (rc) return die("dt_denoise", rc);
+  if (sums) {
+    float* var = d + 13 * n_px;
+    rc = dt_variance(&g, nullptr, sums->acc, sums->acc2, sums->cnt, var, 1, nullptr);
+    if (rc) return die("dt_variance", rc);
+    rc = dt_denoise_var(g.xRes, g.yRes, d, var, &f, &vp, out, d + 16 * n_px, 1, nullptr, nullptr);
+    if (rc) return die("dt_denoise_var", rc);
+  } else {
+    rc = dt_denoise(g.xRes, g.yRes, d, &f, &dp, out, d + 13 * n_px, 1, nullptr, nullptr);
+    if (rc) return die("dt_denoise", rc);
+  }
   std::vector<float> clean(3 * n_px);
   if (hipMemcpy(clean.data(), out, 3 * n_px * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
     fprintf(stderr, "denoise: hipMemcpy failed\n");
@@ -94,7 +117,7 @@ int main(int argc, char** argv)
   int arg = (argc > 2 && argv[2][0] != '-') ? atoi(argv[2]) : 0;
   std::string out;
   std::string data_dir = DT_DATA_DIR;
-  int spp = -1, depth = -1, W = -1, H = -1, progressive = 0, min_samples = 64, denoise = 0, denoise_levels = 0;
+  int spp = -1, depth = -1, W = -1, H = -1, progressive = 0, min_samples = 64, denoise = 0, denoise_levels = 0, denoise_variance = 0;
   double adaptive = -1.0;
   std::string counts_file, features_prefix;
   for (int i = 2; i < argc; ++i) {
@@ -111,8 +134,14 @@ int main(int argc, char** argv)
     else if (a == "--counts" && i + 1 < argc) counts_file = argv[++i];
     else if (a == "--features" && i + 1 < argc) features_prefix = argv[++i];
     else if (a == "--denoise") denoise = 1;
+    else if (a == "--denoise-variance") denoise_variance = 1;
     else if (a == "--denoise-levels" && i + 1 < argc) denoise_levels = atoi(argv[++i]);
   }
+  if (denoise_variance && adaptive < 0.0) {
+    fprintf(stderr, "usage: --denoise-variance needs --adaptive TOL (the variance comes from the adaptive sampler's sums)\n");
+    return 2;
+  }
+  if (denoise_variance) denoise = 1;
   std::string scene = "final";
   float build_frame = 0;
   int frame = 0;
@@ -211,7 +240,8 @@ int main(int argc, char** argv)
           fprintf(stderr, "preview: hipMemcpy failed\n");
           return 1;
         }
-        if (write_denoised(s, g, frame, end, denoise_levels, img, dn_fn, png)) return 1;
+        const adaptive_sums sums = {acc, acc2, cnt};
+        if (write_denoised(s, g, frame, end, denoise_levels, img, dn_fn, png, denoise_variance ? &sums : nullptr)) return 1;
       }
       if (st.pixels == 0) break;
     }

@@ -53,6 +53,9 @@ extern "C" {
  *    first-hit feature buffers) */
 /* (still 8, new exports and one new struct, no struct changed: dt_denoise_params_default,
  *    dt_denoise_workspace_floats, dt_denoise and its dt_denoise_params -- preview denoising) */
+/* (still 8, new exports and one new struct, no struct changed: dt_variance, dt_denoise_var_params_default,
+ *    dt_denoise_var_workspace_floats, dt_denoise_var and its dt_denoise_var_params -- variance-guided
+ *    preview denoising) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -529,7 +532,8 @@ int dt_render_features(const dt_scene* s, const dt_globals* g, int32_t frame, co
  * channel is copied to out unchanged (all three channels); by R it never contributes to a neighbour.
  * The edge-stopping function is a compact polynomial, not exp: no libm on either side, so the output
  * is specified bit for bit. Limits: first-hit guides only (a mirror's or a glass pane's reflection is
- * filtered by the colour term alone); no variance guidance.
+ * filtered by the colour term alone); one colour width for every pixel (dt_denoise_var below takes the
+ * width per pixel from the adaptive sampler's variance).
  *
  * levels: 1..6. Each sigma > 0; +inf disables its term. dt_denoise_params_default: levels 5,
  * demodulate 1 and the sigmas chosen in BASELINE.md. */
@@ -557,6 +561,74 @@ int64_t dt_denoise_workspace_floats(int32_t xRes, int32_t yRes, const dt_denoise
 int     dt_denoise(int32_t xRes, int32_t yRes, const float* colour, const dt_features* feat,
                    const dt_denoise_params* p, float* out, float* work, int32_t on_device,
                    void* stream, float* kernel_ms);
+
+/* ---- variance-guided preview denoising: the colour width from the adaptive sampler's sums ----
+ * No reference counterpart. dt_variance turns the three buffers of dt_render_window_adaptive into a
+ * plane: the variance of the mean of every channel's unclamped sample colours, in grey levels squared of
+ * the 0..255 output. variance holds dt_accum_doubles(g, tiles) floats and is indexed like the
+ * accumulator, so like the colour image, for DT_OUT_IMAGE and DT_OUT_SLAB alike (dt_unpack_slabs gathers
+ * the planes of several ranks as it gathers their colours). Element i = 3q+k, n = (double)count[q], f64:
+ *   n < 2 : variance[i] = 0.0f                              (no estimate: unowned pixel, 1-sample frame)
+ *   else  : d = accum2[i] - (accum[i] * accum[i]) / n       (dt_adapt_converged's d, the same order)
+ *           v = fmax(d, 0.0) / (n * (n - 1.0))              (fmax drops a NaN: 0)
+ *           variance[i] = (float)(v * 65025.0)
+ * One function on both sides, no contraction: host loop and kernel give the same bits. All four buffers
+ * on one side: host (on_device=0) or device (1: one kernel on `stream`, enqueue only). A null pointer or
+ * invalid g / tiles: DT_E_INVALID with a dt_last_error message, before any device work. */
+int dt_variance(const dt_globals* g, const dt_tiles* tiles, const double* accum, const double* accum2,
+                const uint32_t* count, float* variance, int32_t on_device, void* stream);
+
+/* dt_denoise_var: dt_denoise's filter with the colour width of every pixel scaled by the standard
+ * deviation of its own noise, and that variance filtered along with the colour (the scheme of SVGF,
+ * Schied et al. 2017). Whole frames, DT_OUT_IMAGE indexing, C, A, N, Z as for dt_denoise; Vc[3q+k] is the
+ * variance plane dt_variance gives. All arithmetic is IEEE f32, every operation below one rounded
+ * operation (no contraction, no libm), the same on the host and on the device. Everything not restated
+ * here is dt_denoise's. Constants, computed on the host:
+ *   isn, isa, isz_l as in dt_denoise      sv2 = sv*sv, sv = sigma_variance      vf = variance_floor
+ *   (the colour width does not halve per level: the variance it scales with shrinks as the filter proceeds)
+ * Prepare, per pixel p: d[k], E0_p, rz_p as in dt_denoise, and one scalar, the variance of the
+ * demodulated colour vector:
+ *   x = ((Vc_p[0]/(d[0]*d[0])) + (Vc_p[1]/(d[1]*d[1]))) + (Vc_p[2]/(d[2]*d[2]))
+ *   V0_p = fminf(fmaxf(x, 0.0f), 1e12f)        (a NaN or negative x: 0; the cap keeps w*w*V finite)
+ * Level l, pixel p = (r, x), before the taps: the 3x3 prefiltered variance, step 1 at every level:
+ *   sg = 0, gw = 0;  for b = -1..1 (outer, rows), a = -1..1 (inner), q = (r+b, x+a), a q outside the
+ *   image skipped:   g = G[|a|] * G[|b|], G = {0.5, 0.25};   sg = sg + g * V_q;   gw = gw + g
+ *   vbar_p = sg / gw          cv_p = 1.0f / (sv2 * (vbar_p + vf))
+ * Taps: dt_denoise's 25 taps, order and skip rule; xn, xa, xz unchanged;
+ *   xc = ((de0*de0 + de1*de1) + de2*de2) * cv_p
+ *   w  = (h * (R(xn) * R(xz))) * (R(xa) * R(xc))
+ *   if (w > 0) { S[k] = S[k] + w * E_q[k] ; Wt = Wt + w ; SV = SV + (w*w) * V_q }      S, Wt, SV from 0
+ *   Wt > 0:  E'_p = S / Wt,  V'_p = SV / (Wt*Wt);     otherwise E'_p = E_p, V'_p = V_p
+ * Finish and the NaN-colour pass-through: dt_denoise's. Two consequences: with sigma_variance = +inf,
+ * cv = 0 and R(xc) = 1, and the output is dt_denoise's with sigma_colour = +inf and the same other
+ * parameters, bit for bit; where cv_p * |E_p - E_q|^2 >= 1 the tap's weight is exactly 0.
+ * Limits: first-hit guides only, as dt_denoise; the variance is the sampler's estimate from the samples
+ * taken so far (0 below two samples, where only variance_floor sets the width); no temporal reuse.
+ *
+ * levels: 1..6. Each sigma > 0; +inf disables its term. variance_floor: finite, > 0.
+ * dt_denoise_var_params_default: levels 5, demodulate 1 and the values chosen in BASELINE.md. */
+typedef struct dt_denoise_var_params {
+  int32_t levels;          /* 1..6 */
+  int32_t demodulate;      /* 0 or 1 */
+  float   sigma_normal;    /* edge-stopping widths on the guides, as dt_denoise_params */
+  float   sigma_depth;
+  float   sigma_albedo;
+  float   sigma_variance;  /* colour width in standard deviations of the pixel's own noise; > 0, +inf disables */
+  float   variance_floor;  /* added to the variance, demodulated grey levels squared; finite, > 0 */
+  float   _pad;
+} dt_denoise_var_params;
+
+void    dt_denoise_var_params_default(dt_denoise_var_params* p);
+/* as dt_denoise_workspace_floats (the same size: the variance travels in the fourth float of E's records) */
+int64_t dt_denoise_var_workspace_floats(int32_t xRes, int32_t yRes, const dt_denoise_var_params* p);
+/* dt_denoise's contract throughout: sides, workspace, kernel_ms, enqueue only on the device; out must not
+ * alias colour, variance or work. variance: 3*xRes*yRes floats on the side of colour. DT_E_INVALID before
+ * any device work, with a dt_last_error starting "dt_denoise_var: " and naming the argument: a null
+ * argument or a missing plane, xRes or yRes < 1, levels outside 1..6, demodulate not 0 or 1, a sigma that
+ * is <= 0 or NaN, a variance_floor that is <= 0, infinite or NaN, aliasing. */
+int     dt_denoise_var(int32_t xRes, int32_t yRes, const float* colour, const float* variance,
+                       const dt_features* feat, const dt_denoise_var_params* p, float* out, float* work,
+                       int32_t on_device, void* stream, float* kernel_ms);
 
 /* renderImageCloud (render_final_project.cpp:1224-1279). Sets eye/up/lookingAt as the
  * reference does (1227-1229) on a local copy; g is not modified. */
