@@ -306,17 +306,74 @@ bool build_shadow_grid(const std::vector<dtd::DNodeDev>& nodes, const FlatScene&
   //    (at most max(4, 10%)) whose removal shrinks the union at least 4x (the room; with
   //    thousands of small mesh triangles the first term alone would shrink onto the meshes),
   // within the root box. Points outside the grid walk the tree.
+  //
+  // The reference's leaf boxes never end below 0.01: the running maximum of its bounds starts at
+  // FLT_MIN, not at -inf (scene.h, reproduced by host_bvh.cpp). On an axis where every shape lies
+  // below zero every leaf therefore reaches up to 0.01 however far away the scene is (a room at
+  // y = -2048 has leaves 2048 tall), and a grid box made from them is one useless slab. On such an
+  // axis, and only there, the grid box takes each leaf's upper end from its shapes: their own
+  // largest coordinate plus the reference's 1e-2 padding. Shading points lie on the shapes, and
+  // points outside the grid walk the tree; the lists are still made from the reference's boxes.
+  std::vector<double> leaf_hi[3];
+  {
+    std::vector<P3> pts;
+    auto shape_hi = [&](int sid, double hi[3]) {   // false: a shape without bounds here
+      const dtd::DShapeHdr& hd = fs.hdr[sid];
+      const double* gp = fs.geom.data() + hd.off;
+      if (hd.type == DT_SHAPE_SPHERE) {
+        const double r = std::sqrt(gp[dtd::SP_R2]);
+        for (int a = 0; a < 3; ++a) hi[a] = gp[dtd::SP_C + a] + r;
+      } else if (hd.type == DT_SHAPE_CYLINDER || hd.type == DT_SHAPE_CHECKER_CYLINDER) {
+        const double r = std::sqrt(gp[dtd::CY_R2]);
+        for (int a = 0; a < 3; ++a) hi[a] = std::max(gp[dtd::CY_C1 + a], gp[dtd::CY_C2 + a]) + r;
+      } else {
+        pts.clear();
+        if (!shape_hull_points(hd, gp, 0.0, pts) || pts.empty()) return false;
+        for (int a = 0; a < 3; ++a) {
+          hi[a] = -INFINITY;
+          for (const P3& q : pts) hi[a] = std::max(hi[a], q[a]);
+        }
+      }
+      return true;
+    };
+    std::vector<std::array<double, 3>> lhi(leaves.size());
+    bool known = true;
+    double all_hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (size_t i = 0; i < leaves.size() && known; ++i) {
+      const dtd::DNodeDev& nd = nodes[leaves[i]];
+      lhi[i] = {-INFINITY, -INFINITY, -INFINITY};
+      const int64_t cnt = (nd.meta & dtd::DN_SINGLE) ? 1 : (int64_t)nd.aux;
+      for (int64_t q = 0; q < cnt && known; ++q) {
+        const int sid = (nd.meta & dtd::DN_SINGLE) ? (int)nd.first : fs.bvh.leaf_idx[nd.first + q];
+        double hi[3];
+        if (sid < 0 || sid >= (int)fs.hdr.size() || !shape_hi(sid, hi)) { known = false; break; }
+        for (int a = 0; a < 3; ++a) { lhi[i][a] = std::max(lhi[i][a], hi[a]); all_hi[a] = std::max(all_hi[a], hi[a]); }
+      }
+    }
+    for (int a = 0; a < 3; ++a) {
+      if (!known || !(all_hi[a] < -2e-2)) continue;   // some shape reaches zero: the leaf boxes are the shapes'
+      leaf_hi[a].assign(nodes.size(), 0.0);
+      for (size_t i = 0; i < leaves.size(); ++i)
+        leaf_hi[a][leaves[i]] = std::min((double)nodes[leaves[i]].ub[a], lhi[i][a] + 1e-2 * (1 + 1e-6) + 1e-6 * std::fabs(lhi[i][a]));
+    }
+  }
   double lo[3], ext[3], vol = 1;
   for (int a = 0; a < 3; ++a) {
+    auto ub_of = [&](int l) { return leaf_hi[a].empty() ? (double)nodes[l].ub[a] : leaf_hi[a][l]; };
+    double root_ub = nodes[0].ub[a];
+    if (!leaf_hi[a].empty()) {
+      root_ub = -INFINITY;
+      for (int l : leaves) root_ub = std::max(root_ub, ub_of(l));
+    }
     std::vector<std::pair<double, int>> byext;
-    for (int l : leaves) byext.push_back({nodes[l].ub[a] - nodes[l].lb[a], l});
+    for (int l : leaves) byext.push_back({ub_of(l) - nodes[l].lb[a], l});
     std::sort(byext.begin(), byext.end());
     const size_t n = byext.size();
     // plo/phi[k]: union of the k shortest leaf intervals
     std::vector<double> plo(n + 1, INFINITY), phi(n + 1, -INFINITY);
     for (size_t k = 0; k < n; ++k) {
       plo[k + 1] = std::min(plo[k], nodes[byext[k].second].lb[a]);
-      phi[k + 1] = std::max(phi[k], nodes[byext[k].second].ub[a]);
+      phi[k + 1] = std::max(phi[k], ub_of(byext[k].second));
     }
     const size_t k90 = std::max((size_t)1, std::min(n, (size_t)(0.9 * (double)n) + 1));
     double c0 = plo[k90], c1 = phi[k90];
@@ -328,7 +385,7 @@ bool build_shadow_grid(const std::vector<dtd::DNodeDev>& nodes, const FlatScene&
     for (size_t k = n - 1; k >= 1 && n - k <= max_drop; --k)
       if (phi[n] - plo[n] > 4.0 * (phi[k] - plo[k])) { keep = k; break; }
     c0 = std::max(std::min(c0, plo[keep]), nodes[0].lb[a]);
-    c1 = std::min(std::max(c1, phi[keep]), nodes[0].ub[a]);
+    c1 = std::min(std::max(c1, phi[keep]), root_ub);
     if (!(c1 > c0)) return false;
     lo[a] = c0;
     ext[a] = std::max(c1 - c0, 1e-3);
@@ -349,8 +406,15 @@ bool build_shadow_grid(const std::vector<dtd::DNodeDev>& nodes, const FlatScene&
   // segment ends 1e-3 past the light sample (m2)
   double scale = 0;
   for (int a = 0; a < 3; ++a) scale = std::max({scale, std::fabs(lo[a]), std::fabs(lo[a] + ext[a])});
-  const double m1 = (reach + 0.05) * std::max({hh[0], hh[1], hh[2]}) + 1e-4 * (1 + scale);
-  const double m2 = 2e-3 + 1e-4 * (1 + scale);
+  // The slack covers the f32 cell coordinates of the device (dt_kernels.hip sg_coords: (float)p, the
+  // f32 grid origin and 1 / h, together below 3e-7 scale in world units). 1e-4 (1 + scale) is ample
+  // at room scale but grows to 0.8 for a room at 8192 and is 4 cells for a room 0.04 across at 32,
+  // where it swallows the umbra and plane margins: it is capped at 5% of a cell, never below
+  // 1e-6 (1 + scale). At room scale (cells of 0.1 and more, scale in the tens) the cap is not reached.
+  const double hmax_ = std::max({hh[0], hh[1], hh[2]});
+  const double slack = std::min(1e-4 * (1 + scale), std::max(1e-6 * (1 + scale), 0.05 * hmax_));
+  const double m1 = (reach + 0.05) * hmax_ + slack;
+  const double m2 = 2e-3 + slack;
   const double mplane = 1e-3 + 1e-6 * (1 + scale);
   // leaf boxes, padded in y by where the blur passes can hit their shapes (blur_leaf_pad)
   std::vector<std::array<double, 6>> lbox(nodes.size());

@@ -1,0 +1,224 @@
+"""Deterministic synthetic scenes under a similarity transform, built through the ABI's descriptor
+structs as a caller of dt_scene_create would (a plain helper module, imported by the tests).
+
+Every scene is written in unit coordinates and takes a scale s and an offset t; x -> s*x + t is
+applied to everything that carries a position (vertices, centres, light frames, holes, eye,
+lookingAt, cap_center) and s alone to everything that carries a length (radius, S, borderwidth,
+length, width, focal_length, aperture, near_plane, far_dist, move_per_frame, tot_move, accel_t).
+Colours, directions (up, baxis), fov and the sample counts are untouched. With a power of two for
+s the scene's own proportions survive exactly. Each function returns (desc, g, keepalive).
+
+The culling structures (host_shadowgrid.cpp, host_primlists.cpp, host_fasttree.cpp) hold absolute
+margins chosen at room scale, as do the reference's own constants (shadow rays start 1e-3 along the
+ray); CASES are the transforms that move a scene away from that scale: tests/test_scale_host.py,
+tests/test_gpu_scale.py.
+"""
+import math
+
+import distraytracer_amd as dt
+from distraytracer_amd import _lib
+
+F_LIGHT, F_MOTION, F_GLOSSY, F_NAMED_RECT = 1, 2, 8, 16   # include/dt.h DT_F_*
+SPHERE, CYLINDER, TRIANGLE, RECTANGLE, PRISM_V2, CHECKER, CHECKER_HOLE = 1, 2, 3, 4, 5, 6, 7
+PHONG, OREN_NAYAR, COOK_TORRANCE, RAW = 0, 1, 2, 3
+GLASS, STEEL, LINOLEUM = 1, 2, 5
+POINT_LIGHT, SPHERE_LIGHT, RECT_LIGHT = 1, 2, 3
+
+# name -> (s, t): powers of two, so that s*x + t is exact for the scenes' short coordinates
+CASES = {
+    "unit": (1.0, (0.0, 0.0, 0.0)),
+    "tiny": (2.0 ** -8, (0.0, 0.0, 0.0)),
+    "tiny-shifted": (2.0 ** -8, (16.0, -8.0, 32.0)),
+    "shifted": (1.0, (4096.0, -2048.0, 8192.0)),
+    "huge": (2.0 ** 8, (0.0, 0.0, 0.0)),
+}
+
+_POSITIONS = ("center", "A", "B", "D")            # light fields; shapes: v and center
+_LENGTHS = ("radius", "S", "borderwidth", "length", "width")
+
+
+class _Builder:
+    """Collects shape, hole and light records in unit coordinates and writes them transformed."""
+
+    def __init__(self, s, t):
+        self.s, self.t = float(s), tuple(float(v) for v in t)
+        self.shapes, self.lights = [], []
+
+    def pos(self, p):
+        return tuple(self.s * float(p[a]) + self.t[a] for a in range(3))
+
+    def shape(self, t, **kw):
+        """A shape record; v and center are positions, _LENGTHS lengths, everything else as given."""
+        r = _lib.ShapeDesc()
+        r.type = t
+        r.tex_frame = -1
+        for k, v in kw.items():
+            if k == "v":
+                for i, p in enumerate(v):
+                    q = self.pos(p)
+                    for a in range(3):
+                        r.v[i][a] = q[a]
+            elif k == "center":
+                q = self.pos(v)
+                for a in range(3):
+                    r.center[a] = q[a]
+            elif k in _LENGTHS:
+                setattr(r, k, self.s * v)
+            elif isinstance(v, (list, tuple)):
+                for a in range(len(v)):
+                    getattr(r, k)[a] = v[a]
+            else:
+                setattr(r, k, v)
+        self.shapes.append(r)
+        return len(self.shapes) - 1
+
+    def light(self, t, shape_index=-1, radius=0.0, **kw):
+        r = _lib.LightDesc()
+        r.type, r.shape_index, r.radius = t, shape_index, self.s * radius
+        for k, v in kw.items():
+            q = self.pos(v) if k in _POSITIONS else v
+            for a in range(3):
+                getattr(r, k)[a] = q[a]
+        self.lights.append(r)
+        return len(self.lights) - 1
+
+    def globals(self, eye, looking_at, aperture, focal_length):
+        g = dt.globals_default()
+        g.use_model = 0
+        e, l, c = self.pos(eye), self.pos(looking_at), self.pos(tuple(g.cap_center))
+        for a in range(3):
+            g.eye[a], g.lookingAt[a], g.cap_center[a] = e[a], l[a], c[a]
+        g.aperture, g.focal_length = self.s * aperture, self.s * focal_length
+        for k in ("near_plane", "far_dist", "move_per_frame", "tot_move", "accel_t"):
+            setattr(g, k, self.s * getattr(g, k))
+        return g
+
+    def desc(self):
+        arr = (_lib.ShapeDesc * len(self.shapes))(*self.shapes)
+        lights = (_lib.LightDesc * len(self.lights))(*self.lights)
+        return _lib.SceneDesc(len(self.shapes), len(self.lights), 0, 0, arr, lights, None), (arr, lights)
+
+
+def features(s=1.0, t=(0.0, 0.0, 0.0)):
+    """A synthetic scene for the shading paths the shipped builders never use: a glass sphere
+    (refraction + Fresnel, Q5), a steel mirror sphere, an Oren-Nayar sphere, a raw triangle, a
+    plain Checkerboard floor (geometry.cpp:2248-2341), a sphere light with a bounding axis
+    (rejection sampling, Q11), a rectangle light and a point light."""
+    b = _Builder(s, t)
+    A, B, C, D = (-5, 0, 5), (5, 0, 5), (5, 0, -5), (-5, 0, -5)
+    b.shape(CHECKER, v=[A, B, C, D], color=(0.5, 0.5, 0.5), color1=(0.9, 0.9, 0.9), color2=(0.1, 0.1, 0.3), S=1.0,
+            length=10.0, width=10.0, center=(0, 0, 0))
+    b.shape(SPHERE, v=[(0.5, 1.0, 0.0)], radius=0.6, color=(0.9, 0.9, 1.0), material=GLASS, center=(0.5, 1.0, 0.0))
+    b.shape(SPHERE, v=[(-1.2, 0.7, 0.5)], radius=0.5, color=(0.8, 0.8, 0.8), material=STEEL, center=(-1.2, 0.7, 0.5))
+    b.shape(SPHERE, v=[(1.8, 0.5, -0.8)], radius=0.5, color=(0.9, 0.4, 0.2), model=OREN_NAYAR, roughness=0.3,
+            center=(1.8, 0.5, -0.8))
+    b.shape(TRIANGLE, v=[(-2, 0, -2), (-1, 2, -2), (0, 0, -2)], color=(0.2, 0.8, 0.3), model=RAW,
+            center=(-1, 2 / 3, -2))
+    sl = b.shape(SPHERE, v=[(0, 3.5, 1)], radius=0.3, color=(1, 1, 0.9), emit=1, flags=F_LIGHT, center=(0, 3.5, 1))
+    ra, rb, rc, rd = (-1, 4, -1), (1, 4, -1), (1, 4, 1), (-1, 4, 1)
+    rl = b.shape(RECTANGLE, v=[ra, rb, rc, rd], color=(0.8, 0.8, 0.8), emit=2, flags=F_LIGHT, length=1.0, width=1.0,
+                 center=(0, 4, 0))
+    b.light(SPHERE_LIGHT, sl, 0.3, center=(0, 3.5, 1), color=(1, 1, 0.9), baxis=(0, -1, 0))
+    b.light(RECT_LIGHT, rl, center=(0, 4, 0), color=(0.8, 0.8, 0.8), A=ra, B=rb, D=rd)
+    b.light(POINT_LIGHT, center=(3, 3, 3), color=(0.6, 0.6, 0.6))
+    g = b.globals((-4.0, 2.5, 4.0), (0.3, 0.8, -0.2), 0.1, 6.0)
+    g.xRes, g.yRes, g.antialias_samples, g.max_depth, g.brdf_samples = 160, 120, 9, 5, 2
+    desc, keep = b.desc()
+    return desc, g, keep
+
+
+def _rect(b, A, B, C, D, color, flags=F_NAMED_RECT, **kw):
+    """Rectangle(a, b, c, d) as the builders make it: float length |B-A| and width |D-A|, the centre the
+    corners' mean, named "rectangle" (it shifts in the motion-blur passes) unless flags says otherwise"""
+    cen = tuple((A[a] + B[a] + C[a] + D[a]) / 4 for a in range(3))
+    return b.shape(RECTANGLE, v=[A, B, C, D], color=color, flags=flags, length=math.dist(A, B), width=math.dist(A, D),
+                   center=cen, **kw)
+
+
+def _cylinder(b, c1, c2, radius, color, **kw):
+    cen = tuple((c1[a] + c2[a]) / 2 for a in range(3))
+    return b.shape(CYLINDER, v=[c1, c2], radius=radius, color=color, center=cen, **kw)
+
+
+# The plate of the room family: 6 x 6 at y = 2 under the point light at (0, 3.5, 0). The umbra proof of
+# host_shadowgrid.cpp wants every crossing point mu >= 3e-3 inside the face and the cells mud >= 2e-3 below
+# it, absolute lengths: at s = 2^-8 the plate is 0.023 wide and 0.0078 above the floor, and whole 8 x 4
+# blocks of grid cells under it still pass (a 3 x 3 plate at y = 1.5 left none there). Its shadow covers
+# the floor and ends on the walls at y = 1.5.
+PLATE = ((-3, 2, 3), (3, 2, 3), (3, 2, -3), (-3, 2, -3))
+
+
+def room(s=1.0, t=(0.0, 0.0, 0.0), plate=True, motion=None):
+    """Shapes, lights and materials of the room builds only (DT_ROOM_FEATURES: dt_trace_kernel below 64
+    spp, dt_trace_kernel_w5 from 64): a glossy linoleum checkerboard floor (with a small hole in a back
+    corner: the plain Checkerboard is not a room feature, nor is a sphere, so the round shapes are
+    cylinders), a back and a side wall, a Phong and a Cook-Torrance cylinder standing on the floor, a
+    steel one lying on it, a RectPrismV2, and a plain rectangle plate hovering over most of the
+    floor under a point light, so that whole blocks of grid cells lie in that light's umbra; a second
+    point light low at the side (it lights the room under the plate) and a rectangle light with its emitter at the ceiling.
+    plate=False leaves the plate out (what its shadow changes: tests/test_scale_host.py).
+    motion=(move_per_frame, accel_t), in unit lengths: the motion family -- the lying cylinder, the prism
+    and a "rectangle" panel are DT_F_MOTION, so samples that hit them re-trace with every "rectangle"
+    shifted in y and the leaf boxes bumped (cpp:1095-1210); render at a frame >= frame_blur."""
+    b = _Builder(s, t)
+    mv = F_MOTION if motion else 0
+    b.shape(CHECKER_HOLE, v=[(-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4),
+                             (2.5, 0, -2.5), (3.5, 0, -2.5), (3.5, 0, -3.5), (2.5, 0, -3.5)],
+            color=(0.58, 0.82, 1.0), color1=(0.58, 0.82, 1.0), color2=(1.0, 0.416, 0.835), S=1.0, length=8.0,
+            width=8.0, center=(0, 0, 0), material=LINOLEUM, flags=F_GLOSSY, roughness=0.6, refr=(1.543, 0.0))
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 4, -4), (-4, 4, -4), (0.0, 0.81, 0.99))          # back wall
+    _rect(b, (4, 0, -4), (4, 0, 4), (4, 4, 4), (4, 4, -4), (0.9, 0.8, 0.3))                # side wall
+    _cylinder(b, (-2.5, 0, -1.5), (-2.5, 1.5, -1.5), 0.5, (0.9, 0.3, 0.2))
+    _cylinder(b, (2.25, 0, 0.5), (2.25, 1.0, 0.5), 0.5, (0.95, 0.64, 0.54), model=COOK_TORRANCE, roughness=0.4,
+              refr=(2.75, 3.79))
+    _cylinder(b, (-1.5, 0.375, 2.0), (-0.5, 0.375, 2.5), 0.375, (0.8, 0.8, 0.8), material=STEEL, flags=mv)
+    pa, pb, pc, pd = (0.5, 0, -2), (1.5, 0, -2), (1.5, 0, -3), (0.5, 0, -3)
+    up = lambda p: (p[0], p[1] + 0.75, p[2])
+    b.shape(PRISM_V2, v=[pa, pb, pc, pd, up(pa), up(pb), up(pc), up(pd)], color=(0.3, 0.9, 0.4), length=1.0, width=1.0,
+            center=(1.0, 0.375, -2.5), flags=mv)
+    if plate:
+        _rect(b, *PLATE, (0.7, 0.7, 0.75), flags=0)
+    if motion:
+        _rect(b, (-3.5, 0.25, 1.0), (-2.5, 0.25, 1.0), (-2.5, 1.5, 1.0), (-3.5, 1.5, 1.0), (0.9, 0.9, 0.2),
+              flags=F_NAMED_RECT | F_MOTION)
+    ra, rb, rc, rd = (1.5, 3.75, -1.5), (2.5, 3.75, -1.5), (2.5, 3.75, -2.5), (1.5, 3.75, -2.5)
+    rl = b.shape(RECTANGLE, v=[ra, rb, rc, rd], color=(0.8, 0.8, 0.8), emit=2, flags=F_LIGHT, length=1.0, width=1.0,
+                 center=(2.0, 3.75, -2.0))
+    b.light(POINT_LIGHT, center=(0, 3.5, 0), color=(0.9, 0.9, 0.9))
+    b.light(POINT_LIGHT, center=(-3.5, 1.0, 3.0), color=(0.5, 0.5, 0.5))
+    b.light(RECT_LIGHT, rl, center=(2.0, 3.75, -2.0), color=(0.7, 0.7, 0.7), A=ra, B=rb, D=rd)
+    g = b.globals((0.5, 1.25, 6.5), (0.0, 0.75, 0.0), 0.0625, 6.0)
+    if motion:
+        g.move_per_frame, g.accel_t = s * motion[0], s * motion[1]
+    g.xRes, g.yRes, g.antialias_samples, g.max_depth, g.brdf_samples = 96, 64, 4, 4, 2
+    desc, keep = b.desc()
+    return desc, g, keep
+
+
+# the motion family's shifts val = move_per_frame d + accel_t d^3, d in [0, frame_range = 1], in unit lengths:
+# small against the 8-unit room, and up to 3.5 units, about half of it (bumped leaf boxes outgrow their
+# parents: the bump tree's ancestor-chain test; padded lists overflow: the pass-0 grid)
+MOTION_SHIFTS = {"small": (2.0 ** -6, 2.0 ** -7), "large": (0.5, 3.0)}
+
+
+def motion(s=1.0, t=(0.0, 0.0, 0.0), shift="small"):
+    """room() with shapes in motion; returns (desc, g, keepalive) for a render at MOTION_FRAME"""
+    return room(s, t, motion=MOTION_SHIFTS[shift])
+
+
+MOTION_FRAME = 1600   # the default frame_blur: val takes the cubic term as well (Q19)
+
+FAMILIES = {
+    "room": (room, 0),
+    "features": (features, 0),
+    "motion-small": (lambda s, t: motion(s, t, "small"), MOTION_FRAME),
+    "motion-large": (lambda s, t: motion(s, t, "large"), MOTION_FRAME),
+}
+
+
+def build(family, case):
+    """(desc, g, keepalive, frame) of a family under a case's transform"""
+    fn, frame = FAMILIES[family]
+    s, t = CASES[case]
+    desc, g, keep = fn(s, t)
+    return desc, g, keep, frame

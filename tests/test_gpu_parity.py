@@ -404,68 +404,7 @@ def test_bump_tree_matches_reference_walks(cuda, monkeypatch, n):
         log_equal("bump tree frame %d %s vs reference-tree walks" % (n * 8, env), img, ref_img)
 
 
-def _feature_scene():
-    """A synthetic scene for the shading paths the shipped builders never use: a glass sphere
-    (refraction + Fresnel, Q5), a steel mirror sphere, an Oren-Nayar sphere, a raw triangle, a
-    plain Checkerboard floor (geometry.cpp:2248-2341), a sphere light with a bounding axis
-    (rejection sampling, Q11), a rectangle light and a point light. Built through the ABI's
-    descriptor structs, as a caller of dt_scene_create would."""
-    import ctypes
-    from distraytracer_amd import _lib
-    shapes = []
-
-    def shape(t, **kw):
-        s = _lib.ShapeDesc()
-        s.type = t
-        s.tex_frame = -1
-        for k, v in kw.items():
-            if k == "v":
-                for i, p in enumerate(v):
-                    for a in range(3):
-                        s.v[i][a] = p[a]
-            elif isinstance(v, (list, tuple)):
-                for a in range(len(v)):
-                    getattr(s, k)[a] = v[a]
-            else:
-                setattr(s, k, v)
-        shapes.append(s)
-        return len(shapes) - 1
-
-    A, B, C, D = (-5, 0, 5), (5, 0, 5), (5, 0, -5), (-5, 0, -5)
-    shape(6, v=[A, B, C, D], color=(0.5, 0.5, 0.5), color1=(0.9, 0.9, 0.9), color2=(0.1, 0.1, 0.3), S=1.0,
-          length=10.0, width=10.0, center=(0, 0, 0))
-    shape(1, v=[(0.5, 1.0, 0.0)], radius=0.6, color=(0.9, 0.9, 1.0), material=1, center=(0.5, 1.0, 0.0))
-    shape(1, v=[(-1.2, 0.7, 0.5)], radius=0.5, color=(0.8, 0.8, 0.8), material=2, center=(-1.2, 0.7, 0.5))
-    shape(1, v=[(1.8, 0.5, -0.8)], radius=0.5, color=(0.9, 0.4, 0.2), model=1, roughness=0.3,
-          center=(1.8, 0.5, -0.8))
-    shape(3, v=[(-2, 0, -2), (-1, 2, -2), (0, 0, -2)], color=(0.2, 0.8, 0.3), model=3, center=(-1, 2 / 3, -2))
-    sl = shape(1, v=[(0, 3.5, 1)], radius=0.3, color=(1, 1, 0.9), emit=1, flags=1, center=(0, 3.5, 1))
-    ra, rb, rc, rd = (-1, 4, -1), (1, 4, -1), (1, 4, 1), (-1, 4, 1)
-    rl = shape(4, v=[ra, rb, rc, rd], color=(0.8, 0.8, 0.8), emit=2, flags=1, length=1.0, width=1.0,
-               center=(0, 4, 0))
-    lights = (_lib.LightDesc * 3)()
-    lights[0].type, lights[0].shape_index, lights[0].radius = 2, sl, 0.3
-    for a in range(3):
-        lights[0].center[a] = (0, 3.5, 1)[a]
-        lights[0].color[a] = (1, 1, 0.9)[a]
-        lights[0].baxis[a] = (0, -1, 0)[a]
-        lights[1].center[a] = (0, 4, 0)[a]
-        lights[1].color[a] = 0.8
-        lights[1].A[a], lights[1].B[a], lights[1].D[a] = ra[a], rb[a], rd[a]
-        lights[2].center[a] = (3, 3, 3)[a]
-        lights[2].color[a] = 0.6
-    lights[1].type, lights[1].shape_index = 3, rl
-    lights[2].type, lights[2].shape_index = 1, -1
-    arr = (_lib.ShapeDesc * len(shapes))(*shapes)
-    desc = _lib.SceneDesc(len(shapes), 3, 0, 0, arr, lights, None)
-    g = dt.globals_default()
-    g.use_model = 0
-    g.eye[0], g.eye[1], g.eye[2] = -4.0, 2.5, 4.0
-    g.lookingAt[0], g.lookingAt[1], g.lookingAt[2] = 0.3, 0.8, -0.2
-    g.xRes, g.yRes, g.antialias_samples, g.max_depth, g.brdf_samples = 160, 120, 9, 5, 2
-    g.aperture, g.focal_length = 0.1, 6.0
-    keep = (arr, lights)
-    return desc, g, keep
+from scene_gen import features as _feature_scene   # (the synthetic ABI scene, at s = 1, t = 0)
 
 
 def test_feature_scene_glass_spherelight_checkerboard(cuda):
