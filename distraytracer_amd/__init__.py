@@ -14,8 +14,8 @@ an error (there is no CPU path in this package).
 """
 import ctypes
 
-from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT, DT_OUT_IMAGE, DT_OUT_SLAB, AccelInfo, BVHNode, DenoiseParams, DenoiseVarParams, DTError, Globals, SceneDesc,
-                   Stats, Tiles, check, lib)
+from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT, DT_OUT_IMAGE, DT_OUT_SLAB, AccelInfo, BVHNode, Camera, DenoiseParams, DenoiseVarParams, DTError, Globals, SceneDesc,
+                   Stats, TemporalParams, Tiles, check, lib)
 
 __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_scene", "Scene",
            "render", "render_sky", "renderImage", "renderImageCloud", "write_ppm", "DATA_DIR",
@@ -25,7 +25,8 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "mean_abs_change", "adapt_converged", "render_window_adaptive", "resolve_adaptive", "adapt_select_ms",
            "AdaptiveProgressive", "render_features", "feature_images", "FEATURE_PLANES",
            "DenoiseParams", "denoise_params_default", "denoise", "denoised_filename",
-           "DenoiseVarParams", "denoise_var_params_default", "variance"]
+           "DenoiseVarParams", "denoise_var_params_default", "variance",
+           "Camera", "camera", "TemporalParams", "temporal_params_default", "reproject", "TemporalAccumulator"]
 
 
 def globals_default():
@@ -360,6 +361,149 @@ def denoise(g, colour, feats, params=None, out=None, stream=None, variance=None)
 
 
 _denoise = denoise   # (renderImage's denoise argument hides the name)
+
+
+def camera(g):
+    """dt_camera_get: the camera the renders of g use, as a Camera record (host only)."""
+    c = Camera()
+    check(lib.dt_camera_get(ctypes.byref(g), ctypes.byref(c)), "dt_camera_get")
+    return c
+
+
+def temporal_params_default():
+    """dt_temporal_params_default: demodulate 1 and the values chosen in BASELINE.md."""
+    p = TemporalParams()
+    lib.dt_temporal_params_default(ctypes.byref(p))
+    return p
+
+
+def _numel(a):
+    return a.numel() if hasattr(a, "numel") else a.size
+
+
+def _new_like(like, n, side):
+    if side:
+        import torch
+        return torch.empty(n, dtype=torch.float32, device=like.device)
+    import numpy as np
+    return np.empty(n, np.float32)
+
+
+def reproject(cur_cam, colour, feats, prev_cam, prev_feats, history, params=None, variance=None, stream=None,
+              out=None, out_history=None, out_var=None, timed=False):
+    """include/dt.h dt_reproject, one call per frame: the current frame (its Camera, colour, the albedo, normal
+    and depth planes of render_features in the dict feats, optionally shape, optionally the variance plane) is
+    blended with the history found by reprojecting every pixel into the previous frame (prev_cam, the dict
+    prev_feats with albedo, normal, depth and optionally shape, and the dict `history` with colour, len and, iff
+    variance is given, var: what the previous call returned). prev_cam, prev_feats and history all None: the
+    first frame of a sequence. Whole frames; all numpy float32 arrays (the host loop) or all CUDA float32
+    tensors (the kernel, enqueued on `stream`). Returns (out, history', out_var): out_var is None without
+    variance. out, out_history, out_var: buffers to write into (new ones otherwise); nothing may alias an
+    input. timed: the kernel is timed with events, the call synchronises and returns a fourth value, its ms."""
+    from ._lib import Features, History
+    W, H = int(cur_cam.xRes), int(cur_cam.yRes)
+    n_px = W * H
+    cp, side = _ptr(colour)
+
+    def plane(a, need, what, shape=False):
+        p, dev = _ptr_typed(a, "torch.int32", "int32") if shape else _ptr(a)
+        if _numel(a) != need:
+            raise DTError("reproject: %s holds %d elements, %dx%d needs %d" % (what, _numel(a), W, H, need))
+        if dev != side:
+            raise DTError("reproject: colour and %s must be on the same side" % what)
+        return p
+
+    plane(colour, 3 * n_px, "colour")
+    vp = plane(variance, 3 * n_px, "variance") if variance is not None else None
+
+    def features(d, names, what):
+        f = Features()
+        for name in names:
+            if name not in d:
+                raise DTError("reproject: %s lacks the %s plane" % (what, name))
+            setattr(f, name, plane(d[name], n_px if name == "depth" else 3 * n_px, "%s[%s]" % (what, name)))
+        if d.get("shape") is not None:
+            f.shape = plane(d["shape"], n_px, "%s[shape]" % what, shape=True)
+        return f
+
+    def record(d, what):
+        h = History()
+        for name in ("colour", "len") + (("var",) if variance is not None else ()):
+            if d.get(name) is None:
+                raise DTError("reproject: %s lacks the %s plane" % (what, name))
+            setattr(h, name, plane(d[name], n_px if name == "len" else 3 * n_px, "%s[%s]" % (what, name)))
+        return h
+
+    f = features(feats, ("albedo", "normal", "depth"), "feats")
+    given = [prev_cam is not None, prev_feats is not None, history is not None]
+    if any(given) and not all(given):
+        raise DTError("reproject: prev_cam, prev_feats and history go together (all None: the first frame)")
+    pf = features(prev_feats, ("albedo", "normal", "depth"), "prev_feats") if given[0] else None
+    hin = record(history, "history") if given[0] else None
+    if out is None:
+        out = _new_like(colour, 3 * n_px, side)
+    if out_history is None:
+        out_history = {"colour": _new_like(colour, 3 * n_px, side), "len": _new_like(colour, n_px, side)}
+        if variance is not None:
+            out_history["var"] = _new_like(colour, 3 * n_px, side)
+    if variance is not None and out_var is None:
+        out_var = _new_like(colour, 3 * n_px, side)
+    op = plane(out, 3 * n_px, "out")
+    ovp = plane(out_var, 3 * n_px, "out_var") if variance is not None else None
+    hout = record(out_history, "out_history")
+    params = params if params is not None else temporal_params_default()
+    ms = ctypes.c_float(0)
+    check(lib.dt_reproject(ctypes.byref(cur_cam), cp, vp, ctypes.byref(f),
+                           ctypes.byref(prev_cam) if given[0] else None, ctypes.byref(pf) if given[0] else None,
+                           ctypes.byref(hin) if given[0] else None, ctypes.byref(params), op, ovp, ctypes.byref(hout),
+                           side, ctypes.c_void_p(stream) if stream else None, ctypes.byref(ms) if timed else None),
+          "dt_reproject")
+    res = (out, out_history, out_var if variance is not None else None)
+    return res + (ms.value,) if timed else res
+
+
+class TemporalAccumulator:
+    """Carries the history of dt_reproject from frame to frame: the two ping-ponged history records, the
+    previous frame's camera and its albedo, normal, depth and shape planes (copies: the caller may reuse its buffers).
+
+        acc = TemporalAccumulator()
+        for each frame, in order:  out = acc.push(g, prog.image(), prog.features())
+                                   clean = denoise(g, out, feats)
+
+    push(g, colour, feats, variance=None) returns the accumulated frame (a new array or tensor), or
+    (out, out_var) with a variance plane; the first push, a push after reset(), one at another resolution, on
+    the other side or with / without variance where the last one differed starts a new sequence.
+    history_length(): the float plane of frames accumulated per pixel (None before the first push)."""
+
+    def __init__(self, params=None):
+        self.params = params if params is not None else temporal_params_default()
+        self.reset()
+
+    def reset(self):
+        self._cam = self._feats = self._hist = self._spare = None
+
+    def history_length(self):
+        return None if self._hist is None else self._hist["len"]
+
+    @staticmethod
+    def _copy(a):
+        return a.clone() if hasattr(a, "clone") else a.copy()
+
+    def push(self, g, colour, feats, variance=None, stream=None):
+        cam = camera(g)
+        side = 1 if getattr(colour, "is_cuda", False) else 0
+        key = (cam.xRes, cam.yRes, side, variance is not None)
+        if self._cam is not None and self._key != key:
+            self.reset()
+        self._key = key
+        if self._spare is not None and ("var" in self._spare) != (variance is not None):
+            self._spare = None
+        out, hist, out_var = reproject(cam, colour, feats, self._cam, self._feats, self._hist, self.params,
+                                       variance=variance, stream=stream, out_history=self._spare)
+        self._spare, self._hist = self._hist, hist
+        self._cam = cam
+        self._feats = {k: self._copy(feats[k]) for k in ("albedo", "normal", "depth", "shape") if feats.get(k) is not None}
+        return (out, out_var) if variance is not None else out
 
 
 def render_sky(g, frame, out, tile=None, stream=None):

@@ -112,6 +112,25 @@ class DenoiseVarParams(ctypes.Structure):
                 ("sigma_albedo", c_float), ("sigma_variance", c_float), ("variance_floor", c_float), ("_pad", c_float)]
 
 
+class Camera(ctypes.Structure):
+    """dt_camera: the render's camera as dt_camera_get gives it (eye, the right / up / backward unit vectors, the
+    near-plane window, the resolution)"""
+    _fields_ = [("eye", D3), ("X", D3), ("Y", D3), ("Z", D3), ("l", c_float), ("r", c_float), ("b", c_float),
+                ("t", c_float), ("near_plane", c_float), ("focal_length", c_float), ("xRes", c_int32), ("yRes", c_int32)]
+
+
+class TemporalParams(ctypes.Structure):
+    """dt_temporal_params: demodulate 0/1, alpha_min in (0, 1], max_history >= 1, the depth, normal and albedo
+    tolerances (>= 0, inf: test off)"""
+    _fields_ = [("demodulate", c_int32), ("alpha_min", c_float), ("max_history", c_float), ("depth_tol", c_float),
+                ("normal_tol", c_float), ("albedo_tol", c_float)]
+
+
+class History(ctypes.Structure):
+    """dt_history: the planes of one history record of dt_reproject (var: a null pointer without variance)"""
+    _fields_ = [("colour", ctypes.c_void_p), ("var", ctypes.c_void_p), ("len", ctypes.c_void_p)]
+
+
 class BVHNode(ctypes.Structure):
     _fields_ = [("first_child", c_int32), ("n_children", c_int32), ("first_index", c_int32),
                 ("n_indices", c_int32), ("leaf", c_int32), ("depth", c_int32), ("lbound", D3), ("ubound", D3)]
@@ -144,7 +163,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_adapt_converged", "dt_render_window_adaptive", "dt_render_window_adaptive_async",
            "dt_resolve_adaptive", "dt_adapt_select_ms", "dt_render_features",
            "dt_denoise_params_default", "dt_denoise_workspace_floats", "dt_denoise",
-           "dt_variance", "dt_denoise_var_params_default", "dt_denoise_var_workspace_floats", "dt_denoise_var"]
+           "dt_variance", "dt_denoise_var_params_default", "dt_denoise_var_workspace_floats", "dt_denoise_var",
+           "dt_camera_get", "dt_temporal_params_default", "dt_reproject"]
 
 
 class DTError(RuntimeError):
@@ -234,6 +254,11 @@ def _load():
         "dt_denoise_var_workspace_floats": (c_int64, [c_int32, c_int32, P(DenoiseVarParams)]),
         "dt_denoise_var": (c_int32, [c_int32, c_int32, ctypes.c_void_p, ctypes.c_void_p, P(Features), P(DenoiseVarParams),
                                      ctypes.c_void_p, ctypes.c_void_p, c_int32, ctypes.c_void_p, P(c_float)]),
+        "dt_camera_get": (c_int32, [P(Globals), P(Camera)]),
+        "dt_temporal_params_default": (None, [P(TemporalParams)]),
+        "dt_reproject": (c_int32, [P(Camera), ctypes.c_void_p, ctypes.c_void_p, P(Features), P(Camera), P(Features),
+                                   P(History), P(TemporalParams), ctypes.c_void_p, ctypes.c_void_p, P(History), c_int32,
+                                   ctypes.c_void_p, P(c_float)]),
         "dt_unpack_slabs": (c_int32, [P(Globals), P(Tiles), c_int32, ctypes.c_void_p, ctypes.c_void_p, c_int32,
                                       ctypes.c_void_p]),
         "dt_build_scene": (c_int32, [ctypes.c_char_p, c_float, P(Globals), ctypes.c_char_p, P(P(SceneDesc))]),

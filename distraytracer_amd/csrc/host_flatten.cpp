@@ -521,4 +521,37 @@ int fill_sky_params(const dt_globals& g0, float frame, const dt_tiles* tiles, DP
   return DT_OK;
 }
 
+// dt_camera_get (include/dt.h): the camera fill_params gives the device, from the same two functions
+int camera_record(const dt_globals& g, dt_camera& out, std::string& err)
+{
+  if (g.xRes <= 0 || g.yRes <= 0) {
+    err = "invalid globals";
+    return DT_E_INVALID;
+  }
+  V3 X, Y, Z;
+  bool degenerate;
+  camera(v3a(g.eye), v3a(g.lookingAt), v3a(g.up), X, Y, Z, degenerate);
+  if (degenerate) {
+    err = "Gaze direction can't be equal to up vector";   // cpp:993-996
+    return DT_E_INVALID;
+  }
+  DParams P;
+  near_plane(g, P);
+  for (int k = 0; k < 3; ++k) {
+    out.eye[k] = g.eye[k];
+    out.X[k] = (&X.x)[k];
+    out.Y[k] = (&Y.x)[k];
+    out.Z[k] = (&Z.x)[k];
+  }
+  out.l = P.l;
+  out.r = P.r;
+  out.b = P.b;
+  out.t = P.t;
+  out.near_plane = g.near_plane;
+  out.focal_length = g.focal_length;
+  out.xRes = g.xRes;
+  out.yRes = g.yRes;
+  return DT_OK;
+}
+
 }  // namespace dth

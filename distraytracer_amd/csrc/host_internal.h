@@ -159,6 +159,7 @@ bool build_primary_lists(const std::vector<dtd::DNodeDev>& fnodes, int n_fnodes,
 int fill_params(const dt_globals& g, int frame, const dt_tiles* tiles, dtd::DParams& P, std::string& err);
 int fill_sky_params(const dt_globals& g, float frame, const dt_tiles* tiles, dtd::DParams& P, std::string& err);
 std::vector<float> cloud_z_steps(const dt_globals& g);
+int camera_record(const dt_globals& g, dt_camera& out, std::string& err);   // dt_camera_get
 
 void set_error(const std::string& e);
 

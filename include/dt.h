@@ -56,6 +56,9 @@ extern "C" {
 /* (still 8, new exports and one new struct, no struct changed: dt_variance, dt_denoise_var_params_default,
  *    dt_denoise_var_workspace_floats, dt_denoise_var and its dt_denoise_var_params -- variance-guided
  *    preview denoising) */
+/* (still 8, new exports and new structs, no struct changed: dt_camera_get and its dt_camera,
+ *    dt_temporal_params_default, dt_reproject and its dt_temporal_params and dt_history -- temporal reuse
+ *    for animation previews) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -603,7 +606,8 @@ int dt_variance(const dt_globals* g, const dt_tiles* tiles, const double* accum,
  * cv = 0 and R(xc) = 1, and the output is dt_denoise's with sigma_colour = +inf and the same other
  * parameters, bit for bit; where cv_p * |E_p - E_q|^2 >= 1 the tap's weight is exactly 0.
  * Limits: first-hit guides only, as dt_denoise; the variance is the sampler's estimate from the samples
- * taken so far (0 below two samples, where only variance_floor sets the width); no temporal reuse.
+ * taken so far (0 below two samples, where only variance_floor sets the width); one frame alone (dt_reproject
+ * below carries the samples of earlier frames over, and its out_var is a variance plane this filter takes).
  *
  * levels: 1..6. Each sigma > 0; +inf disables its term. variance_floor: finite, > 0.
  * dt_denoise_var_params_default: levels 5, demodulate 1 and the values chosen in BASELINE.md. */
@@ -629,6 +633,119 @@ int64_t dt_denoise_var_workspace_floats(int32_t xRes, int32_t yRes, const dt_den
 int     dt_denoise_var(int32_t xRes, int32_t yRes, const float* colour, const float* variance,
                        const dt_features* feat, const dt_denoise_var_params* p, float* out, float* work,
                        int32_t on_device, void* stream, float* kernel_ms);
+
+/* ---- temporal reuse for animation previews: reproject and accumulate frames ----
+ * No reference counterpart. The third leg of the SVGF scheme (Schied et al. 2017) beside dt_denoise_var: the
+ * previous frames' samples of the same surfaces, found by reprojecting every pixel's first hit into the
+ * previous frame's camera, are blended with the current preview.
+ *
+ * dt_camera: the render's camera as a record. dt_camera_get fills it with exactly the values the renders
+ * take from g (the functions of host_flatten.cpp that fill the device parameters: camera() for X, Y, Z from
+ * eye, lookingAt and up, near_plane() for l, r, b, t from fov, aspect and near_plane). Host only; no scene,
+ * no device. A null argument, xRes or yRes < 1: DT_E_INVALID; a degenerate gaze: DT_E_INVALID with the
+ * renders' message ("Gaze direction can't be equal to up vector"). */
+typedef struct dt_camera {
+  double  eye[3], X[3], Y[3], Z[3];              /* the eye and the camera's right, up and backward unit vectors */
+  float   l, r, b, t, near_plane, focal_length;  /* the near-plane window; rays are focal_length * dir (below) */
+  int32_t xRes, yRes;
+} dt_camera;
+
+int dt_camera_get(const dt_globals* g, dt_camera* out);
+
+/* dt_reproject: one call per frame. Whole frames only, DT_OUT_IMAGE indexing, W = xRes, H = yRes of both
+ * cameras: render pixel (x, y) has slot q = (H-1-y)*W + x. Current frame: camera cur, colour C (3 per pixel,
+ * 0..255, what dt_render / dt_resolve give), feat with the planes A (albedo), N (normal), Z (depth) of
+ * dt_render_features and optionally shape; optionally the variance plane Vc (3 per pixel, dt_variance's).
+ * Previous frame: camera prev, prev_feat with its A', N', Z' and optionally shape' (coverage is not
+ * read), and the history record hist_in that the previous call wrote. A history record is three
+ * caller-owned planes: colour (3 per pixel, demodulated), var (3 per pixel, present iff Vc is) and len (1 per
+ * pixel: the number of frames in the pixel's history, a float). Outputs: out (3 per pixel: the accumulated
+ * colour, remodulated and clamped to 0..255), the new history record hist_out, and out_var (3 per pixel,
+ * present iff Vc is: the variance of out in dt_variance's units, a plane dt_denoise_var takes unchanged).
+ * prev == NULL with prev_feat == NULL and hist_in == NULL: there is no history (the first frame of a
+ * sequence, step 8 for every pixel). No output may alias an input or another output: the call gathers from
+ * neighbours, and the caller ping-pongs two history records.
+ *
+ * All arithmetic is IEEE f32, every operation below one rounded operation (no contraction; sqrtf and /
+ * correctly rounded; floorf exact; no other libm), the same on the host and on the device;
+ * tests/temporal_ref.py restates it in numpy. dot(u, v) = (u0*v0 + u1*v1) + u2*v2. The cameras' eye, X, Y, Z
+ * are converted to f32 once, on the host, before any pixel; primed names are prev's. Host constants:
+ * nt2 = normal_tol * normal_tol, at2 = albedo_tol * albedo_tol. Per pixel p = (x, y), slot q:
+ *  1 demodulate   d[k] = demodulate ? fmaxf(A_p[k], 0.0625f) : 1.0f      E_p[k] = C_p[k] / d[k]
+ *                 Ve_p[k] = Vc_p[k] / (d[k]*d[k])
+ *  2 direction    camera_ray's, from the pixel's corner:  a = l + ((r-l) * (float)x) / (float)W
+ *                 b = b_ + ((t-b_) * (float)y) / (float)H  (b_: the record's b)
+ *                 dir[k] = (a*X[k] + b*Y[k]) - near_plane*Z[k]
+ *  3 world point  Z_p > 0:  s = Z_p / sqrtf(dot(dir, dir))   Pw[k] = eye[k] + s*dir[k]   v[k] = Pw[k] - eye'[k]
+ *                           dq = sqrtf(dot(v, v))      (the depth plane is the mean distance from the lens,
+ *                           whose samples are symmetric about eye: the pinhole point through its centre)
+ *                 otherwise (sky, nothing hit; a NaN depth too):  v = dir, the pixel is a sky pixel
+ *  4 project      zc = -dot(v, Z')       a' = (near_plane' * dot(v, X')) / zc      b' likewise with Y'
+ *                 fx = ((a' - l') * (float)W) / (r' - l')      fy = ((b' - b_') * (float)H) / (t' - b_')
+ *                 (an integer fx is a pixel: rays leave pixel corners). History is sought iff
+ *                 zc > 0 and -1 < fx and fx < (float)W and -1 < fy and fy < (float)H   (false for a NaN;
+ *                 decided before any conversion to int)
+ *  5 taps         x0 = floorf(fx), tx = fx - x0, y0 = floorf(fy), ty = fy - y0; four taps in the order
+ *                 (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) with the weights
+ *                 (1-tx)*(1-ty), tx*(1-ty), (1-tx)*ty, tx*ty. Tap (u, w_) has slot q' = (H-1-w_)*W + u in the
+ *                 previous frame's planes. It is valid iff its weight w > 0, it lies inside the image,
+ *                 hist_len[q'] > 0, no channel of hist_colour[q'] is a NaN,
+ *                   depth:  fabsf(Z'[q'] - dq) <= depth_tol * dq;  for a sky pixel Z'[q'] == 0 instead
+ *                   normal: dot(n, n) <= nt2 with n = N_p - N'[q']  (the premultiplied world-space normals
+ *                           compare across cameras)
+ *                   albedo: dot(m, m) <= at2 with m = A_p - A'[q']  (demodulation cannot carry a history across
+ *                           an albedo edge where the colour is clamped at 255, the albedo is below the 0.0625
+ *                           floor, or the surface is an emitter or a mirror; depth, normal and shape do
+ *                           not see a texture's edge, or an emitter's edge under depth of field)
+ *                   shape:  shape[q] == shape'[q'], when both shape planes are given
+ *                 (a NaN guide fails its comparison: such a tap is not valid)
+ *  6 gather       over the valid taps in tap order, all sums from 0:  Wt = Wt + w   S[k] = S[k] + w*hist_colour[k]
+ *                 SL = SL + w*hist_len   SV[k] = SV[k] + w*hist_var[k];  with Wt > 0:
+ *                 E_h = S / Wt   len_h = SL / Wt   V_h = SV / Wt    (the conservative form: interpolated
+ *                 taps are not independent, so the variance is interpolated, not reduced)
+ *  7 blend        n = fminf(len_h + 1.0f, max_history)      alpha = fmaxf(alpha_min, 1.0f / n)
+ *                 E_out = E_h + alpha*(E_p - E_h)           u = 1.0f - alpha
+ *                 V_out = (u*u)*V_h + (alpha*alpha)*Ve_p    len_out = n
+ *                 out = fminf(fmaxf(E_out*d, 0.0f), 255.0f)  out_var = V_out*(d*d)
+ *  8 no history   (no prev, history not sought, or Wt == 0): out = C_p bit for bit, E_out = E_p,
+ *                 V_out = Ve_p, out_var = Vc_p bit for bit, len_out = 1
+ *  9 NaN colour   a pixel whose C_p has a NaN channel is copied through as in 8 with len_out = 0: by the
+ *                 rule on hist_len it is never anybody's history (dt_denoise's rule for such pixels)
+ * hist_out holds E_out, V_out and len_out. With +inf a tolerance switches its test off for every tap whose
+ * guides are numbers. Limits: a static world is assumed (there are no per-object motion vectors: a moving
+ * shape is handled only by the rejection tests); first-hit guides, so a reflection is reprojected as if it
+ * were painted on the mirror; the world point is the pinhole point, also under depth of field; whole
+ * frames only (a tile share lacks the pixels its taps land on).
+ *
+ * dt_temporal_params_default: demodulate 1 and the values chosen in BASELINE.md. */
+typedef struct dt_temporal_params {
+  int32_t demodulate;    /* 0 or 1 */
+  float   alpha_min;     /* the least weight of the current frame, in (0, 1] */
+  float   max_history;   /* the cap on the history length, >= 1 */
+  float   depth_tol;     /* relative depth difference a tap may have; >= 0, +inf: no depth test */
+  float   normal_tol;    /* length of the normal difference a tap may have; >= 0, +inf: no normal test */
+  float   albedo_tol;    /* length of the albedo difference a tap may have; >= 0, +inf: no albedo test */
+} dt_temporal_params;
+
+typedef struct dt_history {   /* caller-owned planes, all on the side of the call */
+  float* colour;   /* 3 per pixel: the accumulated colour, demodulated */
+  float* var;      /* 3 per pixel: its variance; present iff the call has a variance plane */
+  float* len;      /* 1 per pixel: frames accumulated (0: a NaN-colour pixel) */
+} dt_history;
+
+void dt_temporal_params_default(dt_temporal_params* p);
+/* Every plane on one side: host (on_device=0: a plain loop) or device (1: one kernel on `stream`, enqueue
+ * only; with kernel_ms it is timed with HIP events and the call synchronises). Nothing outside the outputs
+ * is written. DT_E_INVALID before any device work, with a dt_last_error starting "dt_reproject: " and naming
+ * the argument: a null argument or a missing plane (feat's albedo, normal, depth; prev_feat's albedo, normal, depth;
+ * a history record's colour and len, and its var iff variance is given; out_var iff variance is given),
+ * prev, prev_feat and hist_in not all given or all NULL, a camera of another size than cur, xRes or
+ * yRes < 1, demodulate not 0 or 1, alpha_min outside (0, 1], max_history < 1 or NaN, a tolerance that
+ * is < 0 or NaN, aliasing. */
+int dt_reproject(const dt_camera* cur, const float* colour, const float* variance, const dt_features* feat,
+                 const dt_camera* prev, const dt_features* prev_feat, const dt_history* hist_in,
+                 const dt_temporal_params* p, float* out, float* out_var, const dt_history* hist_out,
+                 int32_t on_device, void* stream, float* kernel_ms);
 
 /* renderImageCloud (render_final_project.cpp:1224-1279). Sets eye/up/lookingAt as the
  * reference does (1227-1229) on a local copy; g is not modified. */
