@@ -26,7 +26,8 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "AdaptiveProgressive", "render_features", "feature_images", "FEATURE_PLANES",
            "DenoiseParams", "denoise_params_default", "denoise", "denoised_filename",
            "DenoiseVarParams", "denoise_var_params_default", "variance",
-           "Camera", "camera", "TemporalParams", "temporal_params_default", "reproject", "TemporalAccumulator"]
+           "Camera", "camera", "TemporalParams", "temporal_params_default", "reproject", "TemporalAccumulator",
+           "trace_rays", "rays_occluded", "RAY_PLANES"]
 
 
 def globals_default():
@@ -238,6 +239,92 @@ def render_features(scene, g, frame, n_samples=None, tile=None, stream=None, pla
                                  ctypes.byref(f), side or 0, ctypes.c_void_p(stream) if stream else None,
                                  ctypes.byref(st)), "dt_render_features")
     return out
+
+
+RAY_PLANES = ("shape", "t", "point", "normal", "albedo")
+# plane -> (torch dtype, numpy dtype, values per ray)
+_RAY_PLANE_TYPES = {"shape": ("torch.int32", "int32", 1), "t": ("torch.float32", "float32", 1),
+                    "point": ("torch.float64", "float64", 3), "normal": ("torch.float64", "float64", 3),
+                    "albedo": ("torch.float64", "float64", 3)}
+_NO_RAYS = (ctypes.c_double * 3)()   # stands in for the null data pointer of an empty array (n = 0 reads nothing)
+
+
+def _numel_any(a):
+    return a.numel() if hasattr(a, "numel") else a.size
+
+
+def _ray_arrays(what, start, dir):
+    """(n, start pointer, dir pointer, on_device) of two float64 arrays shaped (n, 3) or flat, on one side"""
+    sp, sdev = _ptr_typed(start, "torch.float64", "float64")
+    dp, ddev = _ptr_typed(dir, "torch.float64", "float64")
+    ns, nd = _numel_any(start), _numel_any(dir)
+    if ns % 3 or ns != nd or sdev != ddev:
+        raise DTError("%s: start and dir hold 3 doubles per ray, the same number of rays, on the same side" % what)
+    none = ctypes.cast(_NO_RAYS, ctypes.c_void_p)
+    return ns // 3, sp if sp.value else none, dp if dp.value else none, sdev
+
+
+def _ray_new(like, shape, torch_dtype, np_dtype):
+    """a new array on the side of `like` (a CUDA or CPU tensor, or a numpy array)"""
+    if hasattr(like, "data_ptr"):
+        import torch
+        return torch.zeros(shape, dtype=getattr(torch, torch_dtype.split(".")[1]), device=like.device)
+    import numpy as np
+    return np.zeros(shape, dtype=np_dtype)
+
+
+def _ray_out(what, name, a, n, per, torch_dtype, np_dtype, side):
+    p, dev = _ptr_typed(a, torch_dtype, np_dtype)
+    if _numel_any(a) != n * per:
+        raise DTError("%s: %s holds %d elements, %d rays need %d" % (what, name, _numel_any(a), n, n * per))
+    if dev != side:
+        raise DTError("%s: %s must be on the side of start" % (what, name))
+    return p if p.value else ctypes.cast(_NO_RAYS, ctypes.c_void_p)
+
+
+def trace_rays(scene, g, start, dir, planes=RAY_PLANES, out=None, stream=None):
+    """Closest hits of caller-supplied rays (include/dt.h dt_trace_rays): start and dir are float64, shaped
+    (n, 3) or flat, numpy arrays or torch tensors, both on one side. Returns (hits, stats): hits is a dict
+    plane name -> array on the side of start for the planes asked for: shape (int32, -1: none), t (float32
+    along the unnormalised dir, FLT_MAX: none), point, normal and albedo (float64, (n, 3); zeros on a miss).
+    `out`: a dict of planes to write into instead (it decides the planes). 64 consecutive rays share a
+    wave: keep neighbours in the arrays neighbours in space. g: the globals of the scene's renders."""
+    n, sp, dp, side = _ray_arrays("trace_rays", start, dir)
+    if out is None:
+        for name in planes:
+            if name not in RAY_PLANES:
+                raise DTError("trace_rays: unknown plane %r" % (name,))
+        out = {name: _ray_new(start, (n,) if _RAY_PLANE_TYPES[name][2] == 1 else (n, 3), *_RAY_PLANE_TYPES[name][:2])
+               for name in planes}
+    from ._lib import RayHits
+    h = RayHits()
+    for name, a in out.items():
+        if name not in RAY_PLANES:
+            raise DTError("trace_rays: unknown plane %r" % (name,))
+        tt, nt, per = _RAY_PLANE_TYPES[name]
+        setattr(h, name, _ray_out("trace_rays", name, a, n, per, tt, nt, side))
+    st = Stats()
+    check(lib.dt_trace_rays(scene.handle, ctypes.byref(g), n, sp, dp, ctypes.byref(h), side,
+                            ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)), "dt_trace_rays")
+    return out, st
+
+
+def rays_occluded(scene, g, start, dir, skip_shape=None, out=None, stream=None):
+    """Is start + dir hidden from start (include/dt.h dt_rays_occluded)? start and dir as for trace_rays;
+    skip_shape: optional int32 per ray on the same side, the shape the test leaves out (-1: none), such as
+    the shape a light is. Returns (occluded, stats): uint8 per ray (1 or 0) on the side of start, or `out`.
+    A wave is served in groups of equal skip_shape: group the rays by it where it varies."""
+    n, sp, dp, side = _ray_arrays("rays_occluded", start, dir)
+    kp = None
+    if skip_shape is not None:
+        kp = _ray_out("rays_occluded", "skip_shape", skip_shape, n, 1, "torch.int32", "int32", side)
+    if out is None:
+        out = _ray_new(start, (n,), "torch.uint8", "uint8")
+    op = _ray_out("rays_occluded", "out", out, n, 1, "torch.uint8", "uint8", side)
+    st = Stats()
+    check(lib.dt_rays_occluded(scene.handle, ctypes.byref(g), n, sp, dp, kp, op, side,
+                               ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)), "dt_rays_occluded")
+    return out, st
 
 
 def feature_images(g, feats):

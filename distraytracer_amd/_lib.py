@@ -99,6 +99,12 @@ class Features(ctypes.Structure):
                 ("coverage", ctypes.c_void_p), ("shape", ctypes.c_void_p)]
 
 
+class RayHits(ctypes.Structure):
+    """dt_ray_hits: the planes of dt_trace_rays (a null pointer: not wanted)"""
+    _fields_ = [("shape", ctypes.c_void_p), ("t", ctypes.c_void_p), ("point", ctypes.c_void_p),
+                ("normal", ctypes.c_void_p), ("albedo", ctypes.c_void_p)]
+
+
 class DenoiseParams(ctypes.Structure):
     """dt_denoise_params: levels 1..6, demodulate 0/1, the four edge-stopping widths (> 0, inf: term off)"""
     _fields_ = [("levels", c_int32), ("demodulate", c_int32), ("sigma_normal", c_float), ("sigma_depth", c_float),
@@ -164,7 +170,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_resolve_adaptive", "dt_adapt_select_ms", "dt_render_features",
            "dt_denoise_params_default", "dt_denoise_workspace_floats", "dt_denoise",
            "dt_variance", "dt_denoise_var_params_default", "dt_denoise_var_workspace_floats", "dt_denoise_var",
-           "dt_camera_get", "dt_temporal_params_default", "dt_reproject"]
+           "dt_camera_get", "dt_temporal_params_default", "dt_reproject",
+           "dt_trace_rays", "dt_rays_occluded"]
 
 
 class DTError(RuntimeError):
@@ -244,6 +251,10 @@ def _load():
                                            ctypes.c_void_p, c_int32, ctypes.c_void_p, P(c_float)]),
         "dt_render_features": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, P(Features), c_int32,
                                          ctypes.c_void_p, P(Stats)]),
+        "dt_trace_rays": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p, P(RayHits),
+                                    c_int32, ctypes.c_void_p, P(Stats)]),
+        "dt_rays_occluded": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_denoise_params_default": (None, [P(DenoiseParams)]),
         "dt_denoise_workspace_floats": (c_int64, [c_int32, c_int32, P(DenoiseParams)]),
         "dt_denoise": (c_int32, [c_int32, c_int32, ctypes.c_void_p, P(Features), P(DenoiseParams), ctypes.c_void_p,

@@ -90,6 +90,13 @@ extern "C" const void* dt_isect_kernel_ptr(void);
 extern "C" hipError_t dt_launch_features(const void* dev_launch, int n_samples, float* albedo, float* normal, float* depth,
                                          float* coverage, int32_t* shape, int grid, hipStream_t stream);
 extern "C" const void* dt_features_kernel_ptr(void);
+extern "C" hipError_t dt_launch_rayq(const void* dev_launch, int64_t n, const double* start, const double* dir,
+                                     int32_t* shape, float* t, double* point, double* normal, double* albedo, int grid,
+                                     hipStream_t stream);
+extern "C" hipError_t dt_launch_rayq_occl(const void* dev_launch, int64_t n, const double* start, const double* dir,
+                                          const int32_t* skip_shape, uint8_t* occluded, int grid, hipStream_t stream);
+extern "C" const void* dt_rayq_kernel_ptr(void);
+extern "C" const void* dt_rayq_occl_kernel_ptr(void);
 
 namespace {
 
@@ -1768,6 +1775,183 @@ int dt_render_features(const dt_scene* sc_c, const dt_globals* g, int32_t frame,
     stats->tex_fetches = h[ST_TEX];
     stats->uv_out_of_range = h[ST_UV];
     stats->prism_norm_fallback = h[ST_PRISM];
+    stats->kernel_ms = ms;
+  }
+  return DT_OK;
+}
+
+// Ray queries (dt_trace_rays, dt_rays_occluded): dt_rayq_kernel / dt_rayq_occl_kernel over rays the caller
+// hands over. Synchronous. A query has a launch record, counters and events of its own and takes only
+// the traversal parameters from g (prepare_render; the camera it fills in is not read): it neither
+// reads nor rebuilds the scene's primary-ray lists, and a render afterwards finds the scene as it was.
+struct RayqTmp {   // released on every return path, after the stream's work that may use them
+  hipStream_t st = nullptr;
+  void *launch = nullptr, *stats = nullptr;
+  std::vector<void*> bufs;
+  std::vector<uint8_t> record;   // the launch record's host bytes
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~RayqTmp()
+  {
+    if (launch) (void)hipStreamSynchronize(st);
+    for (void* b : bufs)
+      if (b) (void)hipFree(b);
+    if (launch) (void)hipFree(launch);
+    if (stats) (void)hipFree(stats);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  // a device buffer of `bytes`, holding host's bytes when host is given
+  int stage(const void* host, size_t bytes, void** dev)
+  {
+    HIPCHK(hipMalloc(dev, bytes));
+    bufs.push_back(*dev);
+    if (host) HIPCHK(hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, st));
+    return DT_OK;
+  }
+};
+
+// the query's launch record and zeroed counters on the device, and its two events
+static int rayq_begin(dt_scene* sc, const dt_globals* g, RayqTmp& tmp)
+{
+  dtd::DParams P;
+  std::vector<float> zs;
+  dt_tiles whole;
+  memset(&whole, 0, sizeof(whole));
+  whole.world = 1;
+  int rc = prepare_render(sc, g, 0, &whole, P, zs);
+  if (rc) return rc;
+  if ((rc = scene_upload(sc))) return rc;
+  P.pl_block = P.pl_nbx = P.pl_nby = P.pl_bump = 0;   // no primary lists: the rays are not the camera's
+  const size_t n_stats = sizeof(unsigned long long) * (ST_N + 1);
+  HIPCHK(hipMalloc(&tmp.launch, dt_launch_size()));
+  HIPCHK(hipMalloc(&tmp.stats, n_stats));
+  HIPCHK(hipMemsetAsync(tmp.stats, 0, n_stats, tmp.st));
+  HScene hs;
+  fill_hscene(sc, hs);
+  hs.pl_cells = hs.pl_list = nullptr;
+  hs.stats = (unsigned long long*)tmp.stats;
+  hs.queue = hs.stats + ST_N;
+  std::vector<uint8_t>& L = tmp.record;   // (lives until the stream has drained)
+  L.assign(dt_launch_size(), 0);
+  memcpy(L.data() + dt_scene_struct_offset(), &hs, sizeof(hs));
+  memcpy(L.data() + dt_params_struct_offset(), &P, sizeof(P));
+  HIPCHK(hipMemcpyAsync(tmp.launch, L.data(), L.size(), hipMemcpyHostToDevice, tmp.st));
+  HIPCHK(hipEventCreate(&tmp.e0));
+  HIPCHK(hipEventCreate(&tmp.e1));
+  return DT_OK;
+}
+
+static int rayq_grid(const void* kernel_fn, int64_t n_rays, int& resident)
+{
+  if (!resident) resident = max_resident_waves(kernel_fn, 64);
+  const int64_t waves = (n_rays + 63) / 64;
+  const int grid = (int)(waves < resident ? waves : resident);
+  return grid > 0 ? grid : 1;
+}
+
+int dt_trace_rays(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
+                  const dt_ray_hits* out, int32_t on_device, void* stream, dt_stats* stats)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  if (!sc) return fail(DT_E_INVALID, "dt_trace_rays: null scene");
+  if (!g) return fail(DT_E_INVALID, "dt_trace_rays: null globals");
+  if (!start) return fail(DT_E_INVALID, "dt_trace_rays: null start");
+  if (!dir) return fail(DT_E_INVALID, "dt_trace_rays: null dir");
+  if (!out) return fail(DT_E_INVALID, "dt_trace_rays: null out");
+  if (!out->shape && !out->t && !out->point && !out->normal && !out->albedo)
+    return fail(DT_E_INVALID, "dt_trace_rays: out wants no plane (every pointer is null)");
+  if (n_rays < 0) return fail(DT_E_INVALID, "dt_trace_rays: n_rays < 0");
+  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_trace_rays: scenes with a RectPrismWithCylinder");
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n_rays == 0) return DT_OK;
+  RayqTmp tmp;
+  tmp.st = (hipStream_t)stream;
+  if (int rc = rayq_begin(sc, g, tmp)) return rc;
+  const size_t n = (size_t)n_rays;
+  const void *dstart = start, *ddir = dir;
+  void* host[5] = {out->shape, out->t, out->point, out->normal, out->albedo};
+  void* dev[5] = {out->shape, out->t, out->point, out->normal, out->albedo};
+  const size_t bytes[5] = {n * sizeof(int32_t), n * sizeof(float), 3 * n * sizeof(double), 3 * n * sizeof(double),
+                           3 * n * sizeof(double)};
+  if (!on_device) {
+    void* d = nullptr;
+    if (int rc = tmp.stage(start, 3 * n * sizeof(double), &d)) return rc;
+    dstart = d;
+    if (int rc = tmp.stage(dir, 3 * n * sizeof(double), &d)) return rc;
+    ddir = d;
+    for (int k = 0; k < 5; ++k)
+      if (host[k])
+        if (int rc = tmp.stage(nullptr, bytes[k], &dev[k])) return rc;
+  }
+  static int resident = 0;
+  const int grid = rayq_grid(dt_rayq_kernel_ptr(), n_rays, resident);
+  HIPCHK(hipEventRecord(tmp.e0, tmp.st));
+  HIPCHK(dt_launch_rayq(tmp.launch, n_rays, (const double*)dstart, (const double*)ddir, (int32_t*)dev[0], (float*)dev[1],
+                        (double*)dev[2], (double*)dev[3], (double*)dev[4], grid, tmp.st));
+  HIPCHK(hipEventRecord(tmp.e1, tmp.st));
+  if (!on_device)
+    for (int k = 0; k < 5; ++k)
+      if (host[k]) HIPCHK(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, tmp.st));
+  unsigned long long h[ST_N + 1];
+  HIPCHK(hipMemcpyAsync(h, tmp.stats, sizeof(h), hipMemcpyDeviceToHost, tmp.st));
+  HIPCHK(hipStreamSynchronize(tmp.st));
+  if (stats) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
+    stats->rays = h[ST_RAYS];
+    stats->tex_fetches = h[ST_TEX];
+    stats->uv_out_of_range = h[ST_UV];
+    stats->prism_norm_fallback = h[ST_PRISM];
+    stats->kernel_ms = ms;
+  }
+  return DT_OK;
+}
+
+int dt_rays_occluded(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
+                     const int32_t* skip_shape, uint8_t* occluded, int32_t on_device, void* stream, dt_stats* stats)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  if (!sc) return fail(DT_E_INVALID, "dt_rays_occluded: null scene");
+  if (!g) return fail(DT_E_INVALID, "dt_rays_occluded: null globals");
+  if (!start) return fail(DT_E_INVALID, "dt_rays_occluded: null start");
+  if (!dir) return fail(DT_E_INVALID, "dt_rays_occluded: null dir");
+  if (!occluded) return fail(DT_E_INVALID, "dt_rays_occluded: null occluded");
+  if (n_rays < 0) return fail(DT_E_INVALID, "dt_rays_occluded: n_rays < 0");
+  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_rays_occluded: scenes with a RectPrismWithCylinder");
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n_rays == 0) return DT_OK;
+  RayqTmp tmp;
+  tmp.st = (hipStream_t)stream;
+  if (int rc = rayq_begin(sc, g, tmp)) return rc;
+  const size_t n = (size_t)n_rays;
+  const void *dstart = start, *ddir = dir, *dskip = skip_shape;
+  void* docc = occluded;
+  if (!on_device) {
+    void* d = nullptr;
+    if (int rc = tmp.stage(start, 3 * n * sizeof(double), &d)) return rc;
+    dstart = d;
+    if (int rc = tmp.stage(dir, 3 * n * sizeof(double), &d)) return rc;
+    ddir = d;
+    if (skip_shape) {
+      if (int rc = tmp.stage(skip_shape, n * sizeof(int32_t), &d)) return rc;
+      dskip = d;
+    }
+    if (int rc = tmp.stage(nullptr, n, &docc)) return rc;
+  }
+  static int resident = 0;
+  const int grid = rayq_grid(dt_rayq_occl_kernel_ptr(), n_rays, resident);
+  HIPCHK(hipEventRecord(tmp.e0, tmp.st));
+  HIPCHK(dt_launch_rayq_occl(tmp.launch, n_rays, (const double*)dstart, (const double*)ddir, (const int32_t*)dskip,
+                             (uint8_t*)docc, grid, tmp.st));
+  HIPCHK(hipEventRecord(tmp.e1, tmp.st));
+  if (!on_device) HIPCHK(hipMemcpyAsync(occluded, docc, n, hipMemcpyDeviceToHost, tmp.st));
+  unsigned long long h[ST_N + 1];
+  HIPCHK(hipMemcpyAsync(h, tmp.stats, sizeof(h), hipMemcpyDeviceToHost, tmp.st));
+  HIPCHK(hipStreamSynchronize(tmp.st));
+  if (stats) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
+    stats->shadow_rays = h[ST_SHADOW];
     stats->kernel_ms = ms;
   }
   return DT_OK;

@@ -59,6 +59,8 @@ extern "C" {
 /* (still 8, new exports and new structs, no struct changed: dt_camera_get and its dt_camera,
  *    dt_temporal_params_default, dt_reproject and its dt_temporal_params and dt_history -- temporal reuse
  *    for animation previews) */
+/* (still 8, new exports and one new struct, no struct changed: dt_trace_rays and its dt_ray_hits,
+ *    dt_rays_occluded -- ray queries: closest hit and visibility for caller-supplied rays) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -502,6 +504,59 @@ typedef struct dt_features {      /* each plane optional (NULL: not wanted); all
 int dt_render_features(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
                        int32_t n_samples, const dt_features* out, int32_t out_on_device,
                        void* stream, dt_stats* stats);
+
+/* ---- ray queries: closest hit and visibility for rays the caller supplies ----
+ * No reference counterpart: the reference traces only what its camera and its bounces produce. The
+ * primitive under picking, line of sight, light visibility from a set of surface points (baking, probes,
+ * ambient occlusion) and a second bounce computed by the caller from the point and normal of the first.
+ * start and dir hold 3 doubles per ray; every array of a call is on one side, host (on_device=0: staged
+ * through temporaries, as dt_render_features stages its planes) or device (1). Both calls are synchronous,
+ * with a launch record, counters and events of their own: they neither read nor rebuild the scene's
+ * primary-ray lists, and a render of the scene afterwards is unaffected. Like every call on one scene
+ * they must not overlap another call on that scene from another host thread. g: the globals of the
+ * scene's renders, as for dt_intersect_primary; only what traversal reads matters, the camera is not read.
+ *
+ * A ray is VOID if start or dir has a non-finite component or dir is all zero. A void ray is never
+ * traced and reports a miss (not occluded); its neighbours are unaffected.
+ *
+ * dt_trace_rays: rayColor's gather and closest hit (render_final_project.cpp:491-538) for the ray
+ * (dir, start) on the unshifted scene (shift 0 on every frame): every leaf whose box the ray passes, in the
+ * reference's stack order, then the shapes in that order, strictly closer wins, t carried from shape to
+ * shape (oracle.c or_primary_hit). dir is used unnormalised, as the renders use their primary rays. Per
+ * hit the attributes are those dt_render_features computes for one sample; a miss writes -1, FLT_MAX and
+ * zeros. The normal and the colour are computed only for the planes that take them.
+ * stats (optional): rays = the rays traced (the non-void ones), prism_norm_fallback (counted iff normal
+ * is wanted), tex_fetches and uv_out_of_range (iff albedo is), kernel_ms; everything else 0.
+ *
+ * The walk is the renders' wave-uniform one: 64 consecutive rays share a wave, which visits the union of
+ * its rays' nodes. Rays that are neighbours in the arrays should be neighbours in space (README.md). */
+typedef struct dt_ray_hits {   /* each plane optional (NULL: not wanted); n_rays entries; all on one side */
+  int32_t* shape;    /* closest shape, -1: none */
+  float*   t;        /* its t along the unnormalised dir, FLT_MAX: none */
+  double*  point;    /* 3 per ray: start + (double)t * dir */
+  double*  normal;   /* 3 per ray: fixNorm(normalized(dir), getNorm(point)), world space */
+  double*  albedo;   /* 3 per ray: the colour rule of dt_render_features (checker square, texel / 255.0,
+                        bordercolor), one hit, no averaging */
+} dt_ray_hits;
+
+/* DT_E_INVALID, with a dt_last_error starting "dt_trace_rays: " and naming the argument: a null scene,
+ * globals, start, dir or out, an out with every plane NULL, n_rays < 0; DT_E_UNSUPPORTED: a scene with a
+ * RectPrismWithCylinder; all before any device work. n_rays == 0: DT_OK, nothing is launched. */
+int dt_trace_rays(const dt_scene* s, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
+                  const dt_ray_hits* out, int32_t on_device, void* stream, dt_stats* stats);
+
+/* Is start + dir hidden from start? The light loop's shadow test (render_final_project.cpp:806-852) with
+ * sray = dir: t_max = (float)|dir|, sn = normalized(dir); the gather runs along dir from start + 1e-3*dir,
+ * and intersectShadow(sn, start + 1e-3*sn, t_max) on every gathered shape but skip_shape[i] (optional,
+ * n_rays entries, -1: none; NULL: none for any ray -- the shape a light is, or the surface a ray leaves).
+ * occluded[i] = 1 or 0. Tree walks only: the renders' shadow grid is built per light and for the camera's
+ * origin box. A walk skips one shape for the whole wave, so a wave is served in groups of equal
+ * skip_shape: sort or group the rays by it where it varies.
+ * stats (optional): shadow_rays = the rays tested (the non-void ones), kernel_ms; everything else 0.
+ * Errors as dt_trace_rays ("dt_rays_occluded: ", a null occluded in the place of out). */
+int dt_rays_occluded(const dt_scene* s, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
+                     const int32_t* skip_shape /* optional, n_rays; -1: none */, uint8_t* occluded,
+                     int32_t on_device, void* stream, dt_stats* stats);
 
 /* ---- feature-guided denoising of previews: an edge-avoiding a-trous filter ----
  * No reference counterpart. The consumer of the feature buffers: (preview, albedo, normal, depth) ->
