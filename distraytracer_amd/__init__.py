@@ -27,7 +27,8 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "DenoiseParams", "denoise_params_default", "denoise", "denoised_filename",
            "DenoiseVarParams", "denoise_var_params_default", "variance",
            "Camera", "camera", "TemporalParams", "temporal_params_default", "reproject", "TemporalAccumulator",
-           "trace_rays", "rays_occluded", "RAY_PLANES"]
+           "trace_rays", "rays_occluded", "RAY_PLANES",
+           "render_mattes", "matte_mask", "shape_groups", "MATTE_PLANES"]
 
 
 def globals_default():
@@ -238,6 +239,123 @@ def render_features(scene, g, frame, n_samples=None, tile=None, stream=None, pla
     check(lib.dt_render_features(scene.handle, ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None, n,
                                  ctypes.byref(f), side or 0, ctypes.c_void_p(stream) if stream else None,
                                  ctypes.byref(st)), "dt_render_features")
+    return out
+
+
+MATTE_PLANES = ("id", "weight", "distinct")
+
+
+def shape_groups(desc, by="material"):
+    """A group per shape of a scene descriptor (a BuiltScene or a SceneDesc), as an int32 array for
+    render_mattes: by="material" one group per distinct (mesh triangle?, model, material, emit, flags &
+    (LIGHT | TEXTURE | GLOSSY | MESH), tex_frame, color) signature, numbered in order of first appearance
+    (a mesh, or the cylinders of one skeleton, become one object); "shape" the identity; "type" the shape
+    type."""
+    import numpy as np
+    d = desc.desc if isinstance(desc, BuiltScene) else desc
+    n = int(d.n_shapes)
+    if by == "shape":
+        return np.arange(n, dtype=np.int32)
+    if by == "type":
+        return np.array([d.shapes[i].type for i in range(n)], dtype=np.int32)
+    if by != "material":
+        raise DTError("shape_groups: by is 'material', 'shape' or 'type', not %r" % (by,))
+    F_LIGHT, F_TEXTURE, F_GLOSSY, F_MESH, TRIANGLE = 1, 4, 8, 32, 3
+    seen, out = {}, np.empty(n, dtype=np.int32)
+    for i in range(n):
+        s = d.shapes[i]
+        sig = (s.type == TRIANGLE and bool(s.flags & F_MESH), s.model, s.material, s.emit,
+               s.flags & (F_LIGHT | F_TEXTURE | F_GLOSSY | F_MESH), s.tex_frame, tuple(s.color))
+        out[i] = seen.setdefault(sig, len(seen))
+    return out
+
+
+def render_mattes(scene, g, frame, n_samples=None, groups=None, layers=4, tiles=None, planes=("id", "weight"), out=None,
+                  stream=None, stats=None):
+    """Object mattes (include/dt.h dt_render_mattes): for every owned pixel the `layers` groups that cover
+    most of its leading n_samples samples (None: spp), ranked, from the render's own primary rays. groups:
+    an int32 group per shape (shape_groups; None: every shape its own group). Returns a dict: id (int32, -1:
+    no such layer) and weight (float32), shaped (yRes, xRes, layers) for a whole image (rows as render's
+    output) and flat (layers per slot) for a slab; distinct (int32, (yRes, xRes) or flat) when asked for;
+    "layers"; and "overflow_pixels", the owned pixels that met more than 64 groups. `out`: a dict of planes to
+    write into instead (it decides the planes), all CUDA torch tensors or all host arrays, where only owned
+    pixels are written; without it, new CUDA tensors (id -1, weight and distinct 0). `tiles`: a Tiles."""
+    import numpy as np
+    tile = tiles
+    n1 = accum_doubles(g, tile) // 3
+    n = _spp(g) if n_samples is None else int(n_samples)
+    layers = int(layers)
+    whole = tile is None or tile.layout == DT_OUT_IMAGE
+    if out is None:
+        import torch
+        if not 1 <= layers <= 8:
+            raise DTError("render_mattes: layers %d outside 1..8" % layers)
+        out = {}
+        for name in planes:
+            if name not in MATTE_PLANES:
+                raise DTError("render_mattes: unknown plane %r" % (name,))
+            shape = ((g.yRes, g.xRes) if whole else (n1,)) if name == "distinct" else \
+                ((g.yRes, g.xRes, layers) if whole else (n1 * layers,))
+            out[name] = torch.zeros(shape, dtype=torch.float32, device="cuda") if name == "weight" else \
+                torch.full(shape, -1 if name == "id" else 0, dtype=torch.int32, device="cuda")
+    from ._lib import Mattes
+    m = Mattes()
+    side = None
+    for name, a in out.items():
+        if name not in MATTE_PLANES:
+            raise DTError("render_mattes: unknown plane %r" % (name,))
+        p, dev = _ptr(a) if name == "weight" else _ptr_typed(a, "torch.int32", "int32")
+        need = n1 if name == "distinct" else n1 * layers
+        if _numel_any(a) != need:
+            raise DTError("render_mattes: plane %s holds %d elements, (g, tiles, layers) need %d"
+                          % (name, _numel_any(a), need))
+        if side is not None and dev != side:
+            raise DTError("render_mattes: the planes must all be on the same side")
+        side = dev
+        setattr(m, name, p)
+    built = scene._keep
+    n_shapes = int((built.desc if isinstance(built, BuiltScene) else built).n_shapes)
+    gp = None
+    if groups is not None:
+        gmap = np.ascontiguousarray(groups.cpu().numpy() if hasattr(groups, "data_ptr") else groups, dtype=np.int32)
+        if gmap.size != n_shapes:
+            raise DTError("render_mattes: groups holds %d entries, the scene has %d shapes" % (gmap.size, n_shapes))
+        gp = ctypes.c_void_p(gmap.ctypes.data)
+    st = stats if stats is not None else Stats()
+    over = ctypes.c_uint64(0)
+    check(lib.dt_render_mattes(scene.handle, ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None, n, gp,
+                               n_shapes, layers, ctypes.byref(m), side or 0, ctypes.c_void_p(stream) if stream else None,
+                               ctypes.byref(st), ctypes.byref(over)), "dt_render_mattes")
+    res = dict(out)
+    res["layers"] = layers
+    res["overflow_pixels"] = over.value
+    return res
+
+
+def matte_mask(mattes, groups, out=None, stream=None):
+    """The antialiased matte of a set of groups from render_mattes' id and weight planes (include/dt.h
+    dt_matte_mask): per pixel the float32 sum, in layer order, of the weights of the layers whose group is in
+    `groups` (an int, or 1..64 ints). Returns a float32 plane on the side of the planes, shaped like them
+    without the layer axis (or `out`). On the device it is enqueued on `stream`."""
+    import numpy as np
+    ids, w = mattes["id"], mattes["weight"]
+    layers = int(mattes["layers"]) if "layers" in mattes else int(ids.shape[-1])
+    ip, idev = _ptr_typed(ids, "torch.int32", "int32")
+    wp, wdev = _ptr(w)
+    if idev != wdev or _numel_any(ids) != _numel_any(w) or layers < 1 or _numel_any(ids) % layers:
+        raise DTError("matte_mask: id and weight hold `layers` entries per pixel, on the same side")
+    n = _numel_any(ids) // layers
+    gl = np.ascontiguousarray(np.atleast_1d(np.asarray(groups)).ravel(), dtype=np.int32)
+    if out is None:
+        shape = tuple(ids.shape[:-1]) if len(ids.shape) > 1 else (n,)
+        out = _ray_new(ids, shape, "torch.float32", "float32")
+    op, odev = _ptr(out)
+    if odev != idev or _numel_any(out) != n:
+        raise DTError("matte_mask: out holds one float32 per pixel, on the side of the planes")
+    none = ctypes.cast(_NO_RAYS, ctypes.c_void_p)
+    check(lib.dt_matte_mask(n, layers, ip if ip.value else none, wp if wp.value else none,
+                            ctypes.c_void_p(gl.ctypes.data) if gl.size else none, int(gl.size), op if op.value else none,
+                            idev, ctypes.c_void_p(stream) if stream else None), "dt_matte_mask")
     return out
 
 
@@ -743,6 +861,13 @@ class Progressive:
         if self.samples_done < 1:
             raise DTError("Progressive.features: no window rendered yet")
         return render_features(self.scene, self.g, self.frame, self.samples_done, self.tile, planes=planes)
+
+    def mattes(self, groups=None, layers=4):
+        """The object mattes of the samples rendered so far (render_mattes of the leading samples_done
+        samples of every owned pixel, in the accumulator's layout), as features() covers them."""
+        if self.samples_done < 1:
+            raise DTError("Progressive.mattes: no window rendered yet")
+        return render_mattes(self.scene, self.g, self.frame, self.samples_done, groups, layers, self.tile)
 
     def _variance_plane(self):
         raise DTError("Progressive.denoised(variance=True): the sums of squares live in AdaptiveProgressive; "

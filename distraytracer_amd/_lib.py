@@ -105,6 +105,15 @@ class RayHits(ctypes.Structure):
                 ("normal", ctypes.c_void_p), ("albedo", ctypes.c_void_p)]
 
 
+class Mattes(ctypes.Structure):
+    """dt_mattes: the planes of dt_render_mattes (a null pointer: not wanted)"""
+    _fields_ = [("id", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("distinct", ctypes.c_void_p)]
+
+
+DT_MATTE_TABLE = 64       # distinct groups a pixel's histogram holds
+DT_MATTE_MAX_LAYERS = 8
+
+
 class DenoiseParams(ctypes.Structure):
     """dt_denoise_params: levels 1..6, demodulate 0/1, the four edge-stopping widths (> 0, inf: term off)"""
     _fields_ = [("levels", c_int32), ("demodulate", c_int32), ("sigma_normal", c_float), ("sigma_depth", c_float),
@@ -171,7 +180,7 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_denoise_params_default", "dt_denoise_workspace_floats", "dt_denoise",
            "dt_variance", "dt_denoise_var_params_default", "dt_denoise_var_workspace_floats", "dt_denoise_var",
            "dt_camera_get", "dt_temporal_params_default", "dt_reproject",
-           "dt_trace_rays", "dt_rays_occluded"]
+           "dt_trace_rays", "dt_rays_occluded", "dt_render_mattes", "dt_matte_mask"]
 
 
 class DTError(RuntimeError):
@@ -255,6 +264,10 @@ def _load():
                                     c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_rays_occluded": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, c_int32, ctypes.c_void_p, P(Stats)]),
+        "dt_render_mattes": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, ctypes.c_void_p, c_int32,
+                                       c_int32, P(Mattes), c_int32, ctypes.c_void_p, P(Stats), P(c_uint64)]),
+        "dt_matte_mask": (c_int32, [c_int64, c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_int32,
+                                    ctypes.c_void_p, c_int32, ctypes.c_void_p]),
         "dt_denoise_params_default": (None, [P(DenoiseParams)]),
         "dt_denoise_workspace_floats": (c_int64, [c_int32, c_int32, P(DenoiseParams)]),
         "dt_denoise": (c_int32, [c_int32, c_int32, ctypes.c_void_p, P(Features), P(DenoiseParams), ctypes.c_void_p,

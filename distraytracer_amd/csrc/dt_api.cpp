@@ -97,6 +97,10 @@ extern "C" hipError_t dt_launch_rayq_occl(const void* dev_launch, int64_t n, con
                                           const int32_t* skip_shape, uint8_t* occluded, int grid, hipStream_t stream);
 extern "C" const void* dt_rayq_kernel_ptr(void);
 extern "C" const void* dt_rayq_occl_kernel_ptr(void);
+extern "C" hipError_t dt_launch_mattes(const void* dev_launch, int n_samples, const int32_t* gmap, int layers, int32_t* id,
+                                       float* weight, int32_t* distinct, unsigned long long* overflow, int grid,
+                                       hipStream_t stream);
+extern "C" const void* dt_mattes_kernel_ptr(void);
 
 namespace {
 
@@ -1775,6 +1779,122 @@ int dt_render_features(const dt_scene* sc_c, const dt_globals* g, int32_t frame,
     stats->tex_fetches = h[ST_TEX];
     stats->uv_out_of_range = h[ST_UV];
     stats->prism_norm_fallback = h[ST_PRISM];
+    stats->kernel_ms = ms;
+  }
+  return DT_OK;
+}
+
+// Object mattes: dt_mattes_kernel over the samples 0 .. n_samples-1 of every owned pixel. Synchronous; as
+// dt_render_features its launch record, counters and events are its own and it shares only the scene's
+// primary-ray lists. Every argument check, the map's entries included, comes before any device work.
+int dt_render_mattes(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t n_samples,
+                     const int32_t* group_of_shape, int32_t n_shapes, int32_t layers, const dt_mattes* out,
+                     int32_t out_on_device, void* stream, dt_stats* stats, uint64_t* overflow_pixels)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  if (!sc) return fail(DT_E_INVALID, "dt_render_mattes: null scene");
+  if (!g) return fail(DT_E_INVALID, "dt_render_mattes: null globals");
+  if (!out) return fail(DT_E_INVALID, "dt_render_mattes: null out");
+  if (!out->id && !out->weight && !out->distinct)
+    return fail(DT_E_INVALID, "dt_render_mattes: out wants no plane (every pointer is null)");
+  if (int rc = dt_window_check(g, 0, n_samples)) return fail(rc, "dt_render_mattes: n_samples: " + g_err);
+  if (layers < 1 || layers > DT_MATTE_MAX_LAYERS)
+    return fail(DT_E_INVALID, "dt_render_mattes: layers " + std::to_string(layers) + " outside 1.." +
+                                  std::to_string(DT_MATTE_MAX_LAYERS));
+  if (n_shapes < 0) return fail(DT_E_INVALID, "dt_render_mattes: n_shapes " + std::to_string(n_shapes) + " is negative");
+  if (group_of_shape)
+    for (int32_t i = 0; i < n_shapes; ++i)
+      if (group_of_shape[i] < 0)
+        return fail(DT_E_INVALID, "dt_render_mattes: group_of_shape[" + std::to_string(i) + "] is negative");
+  // (the scene is looked at only from here on)
+  if ((size_t)n_shapes != sc->flat.hdr.size())
+    return fail(DT_E_INVALID, "dt_render_mattes: n_shapes " + std::to_string(n_shapes) + ", the scene has " +
+                                  std::to_string(sc->flat.hdr.size()) + " shapes");
+  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_render_mattes: scenes with a RectPrismWithCylinder");
+  hipStream_t st = (hipStream_t)stream;
+  dtd::DParams P;
+  std::vector<float> zs;
+  int rc = prepare_render(sc, g, frame, tiles, P, zs);
+  if (rc) return rc;
+  if ((rc = scene_upload(sc)) || (rc = update_primary_lists(sc, P, true))) return rc;
+  // the planes' lengths and the pixels the launch produces, as dt_render_features counts them
+  const int64_t n1 = P.layout == DT_OUT_SLAB ? P.n_owned_tiles * P.tw * P.th : (int64_t)P.xRes * P.yRes;
+  uint64_t pixels = 0;
+  for (int64_t slot = 0; slot < P.n_owned_tiles; ++slot) {
+    const int64_t t = dtd::tile_of(slot, P.rank, P.world);
+    if (t >= P.n_tiles) continue;
+    const int ty = (int)(t / P.tiles_x), tx = (int)(t - (int64_t)ty * P.tiles_x);
+    const int xa = P.x0 + tx * P.tw, ya = P.y0 + ty * P.th;
+    const int xb = xa + P.tw < P.x1 ? xa + P.tw : P.x1, yb = ya + P.th < P.y1 ? ya + P.th : P.y1;
+    if (xb > xa && yb > ya) pixels += (uint64_t)(xb - xa) * (uint64_t)(yb - ya);
+  }
+  struct Tmp {   // released on every return path, after the stream's work that may use them
+    hipStream_t st = nullptr;
+    void *launch = nullptr, *stats = nullptr, *map = nullptr, *plane[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~Tmp()
+    {
+      if (launch) (void)hipStreamSynchronize(st);
+      for (void* b : {launch, stats, map, plane[0], plane[1], plane[2]})
+        if (b) (void)hipFree(b);
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+    }
+  } tmp;
+  tmp.st = st;
+  // the counters, and after them the overflow count
+  const size_t n_stats = sizeof(unsigned long long) * (ST_N + 2);
+  HIPCHK(hipMalloc(&tmp.launch, dt_launch_size()));
+  HIPCHK(hipMalloc(&tmp.stats, n_stats));
+  HIPCHK(hipMemsetAsync(tmp.stats, 0, n_stats, st));
+  HScene hs;
+  fill_hscene(sc, hs);
+  hs.stats = (unsigned long long*)tmp.stats;
+  hs.queue = hs.stats + ST_N;
+  std::vector<uint8_t> L(dt_launch_size(), 0);
+  memcpy(L.data() + dt_scene_struct_offset(), &hs, sizeof(hs));
+  memcpy(L.data() + dt_params_struct_offset(), &P, sizeof(P));
+  HIPCHK(hipMemcpyAsync(tmp.launch, L.data(), L.size(), hipMemcpyHostToDevice, st));
+  if (group_of_shape && n_shapes > 0) {
+    HIPCHK(hipMalloc(&tmp.map, (size_t)n_shapes * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(tmp.map, group_of_shape, (size_t)n_shapes * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  }
+  // host planes are staged through device copies of the caller's arrays: the entries of pixels this
+  // rank does not own go back as they came
+  void* host[3] = {out->id, out->weight, out->distinct};
+  void* dev[3] = {out->id, out->weight, out->distinct};
+  const size_t bytes[3] = {(size_t)n1 * layers * sizeof(int32_t), (size_t)n1 * layers * sizeof(float),
+                           (size_t)n1 * sizeof(int32_t)};
+  if (!out_on_device)
+    for (int k = 0; k < 3; ++k)
+      if (host[k]) {
+        HIPCHK(hipMalloc(&tmp.plane[k], bytes[k]));
+        HIPCHK(hipMemcpyAsync(tmp.plane[k], host[k], bytes[k], hipMemcpyHostToDevice, st));
+        dev[k] = tmp.plane[k];
+      }
+  static int resident = 0;
+  if (!resident) resident = max_resident_waves(dt_mattes_kernel_ptr(), 64);
+  const int grid = (int)(P.n_items < resident ? P.n_items : resident);
+  HIPCHK(hipEventCreate(&tmp.e0));
+  HIPCHK(hipEventCreate(&tmp.e1));
+  HIPCHK(hipEventRecord(tmp.e0, st));
+  HIPCHK(dt_launch_mattes(tmp.launch, n_samples, (const int32_t*)tmp.map, layers, (int32_t*)dev[0], (float*)dev[1],
+                          (int32_t*)dev[2], (unsigned long long*)tmp.stats + ST_N + 1, grid > 0 ? grid : 1, st));
+  HIPCHK(hipEventRecord(tmp.e1, st));
+  if (!out_on_device)
+    for (int k = 0; k < 3; ++k)
+      if (host[k]) HIPCHK(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, st));
+  unsigned long long h[ST_N + 2];
+  HIPCHK(hipMemcpyAsync(h, tmp.stats, n_stats, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (overflow_pixels) *overflow_pixels = h[ST_N + 1];
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
+    stats->pixels = pixels;
+    stats->samples = pixels * (uint64_t)n_samples;
+    stats->rays = stats->samples;
     stats->kernel_ms = ms;
   }
   return DT_OK;

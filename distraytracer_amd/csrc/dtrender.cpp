@@ -25,6 +25,11 @@
 //                     0.5*coverage)*255), PREFIX.depth.png (depth / the frame's largest depth, grey) and
 //                     PREFIX.coverage.png (grey), each clamped to 0..255. The frame file is the same bytes
 //                     as without the flag.
+//   --mattes PREFIX   after the frame, the object mattes of all spp samples (dt_render_mattes; --matte-layers K,
+//                     1..8, default 4) as PREFIX.matte.png: a false-colour image, each group a hashed colour,
+//                     the layers blended by weight. Groups: one per material signature, as
+//                     distraytracer_amd.shape_groups(desc, "material"). The frame file is the same bytes as
+//                     without the flag.
 //   --denoise         also write the denoised frame (dt_denoise with the default parameters on the frame
 //                     and the albedo, normal and depth planes of the samples taken, on the device) to
 //                     <stem>.denoised.<ext> beside the frame; with --progressive or --adaptive that file is
@@ -39,7 +44,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/dt.h"
@@ -119,7 +126,8 @@ int main(int argc, char** argv)
   std::string data_dir = DT_DATA_DIR;
   int spp = -1, depth = -1, W = -1, H = -1, progressive = 0, min_samples = 64, denoise = 0, denoise_levels = 0, denoise_variance = 0;
   double adaptive = -1.0;
-  std::string counts_file, features_prefix;
+  std::string counts_file, features_prefix, mattes_prefix;
+  int matte_layers = 4;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     if (a == "--out" && i + 1 < argc) out = argv[++i];
@@ -133,6 +141,8 @@ int main(int argc, char** argv)
     else if (a == "--min-samples" && i + 1 < argc) min_samples = atoi(argv[++i]);
     else if (a == "--counts" && i + 1 < argc) counts_file = argv[++i];
     else if (a == "--features" && i + 1 < argc) features_prefix = argv[++i];
+    else if (a == "--mattes" && i + 1 < argc) mattes_prefix = argv[++i];
+    else if (a == "--matte-layers" && i + 1 < argc) matte_layers = atoi(argv[++i]);
     else if (a == "--denoise") denoise = 1;
     else if (a == "--denoise-variance") denoise_variance = 1;
     else if (a == "--denoise-levels" && i + 1 < argc) denoise_levels = atoi(argv[++i]);
@@ -341,6 +351,45 @@ int main(int argc, char** argv)
     }
     printf("features: %llu pixels in %.3f ms (kernel) -> %s.{albedo,normal,depth,coverage}.png\n",
            (unsigned long long)fst.pixels, fst.kernel_ms, features_prefix.c_str());
+  }
+  if (!mattes_prefix.empty()) {
+    // one group per material signature, numbered in order of first appearance (shape_groups "material")
+    typedef std::tuple<int, int, int, int, unsigned, int, double, double, double> Sig;
+    std::map<Sig, int32_t> seen;
+    std::vector<int32_t> group_of((size_t)desc->n_shapes);
+    for (int i = 0; i < desc->n_shapes; ++i) {
+      const dt_shape_desc& sh = desc->shapes[i];
+      const Sig sig(sh.type == DT_SHAPE_TRIANGLE && (sh.flags & DT_F_MESH) ? 1 : 0, sh.model, sh.material, sh.emit,
+                    sh.flags & (DT_F_LIGHT | DT_F_TEXTURE | DT_F_GLOSSY | DT_F_MESH), sh.tex_frame, sh.color[0],
+                    sh.color[1], sh.color[2]);
+      group_of[i] = seen.emplace(sig, (int32_t)seen.size()).first->second;
+    }
+    const int n = (int)sqrt((double)g.antialias_samples);
+    const size_t n_px = (size_t)g.xRes * g.yRes;
+    const int L = matte_layers;
+    std::vector<int32_t> mid(n_px * (size_t)(L > 0 ? L : 1), -1);
+    std::vector<float> mw(mid.size(), 0.0f), pix(3 * n_px, 0.0f);
+    dt_mattes m;
+    memset(&m, 0, sizeof m);
+    m.id = mid.data(); m.weight = mw.data();
+    dt_stats mst;
+    uint64_t over = 0;
+    rc = dt_render_mattes(s, &g, frame, nullptr, n * n, group_of.data(), desc->n_shapes, L, &m, 0, nullptr, &mst, &over);
+    if (rc) return die("dt_render_mattes", rc);
+    for (size_t q = 0; q < n_px; ++q)
+      for (int j = 0; j < L; ++j) {
+        const int32_t id = mid[L * q + j];
+        if (id < 0) continue;
+        uint32_t h = (uint32_t)id * 2654435761u + 0x9e3779b9u;   // a colour per group
+        h ^= h >> 15; h *= 0x2c1b3c6du; h ^= h >> 12;
+        for (int k = 0; k < 3; ++k) pix[3 * q + k] += mw[L * q + j] * (float)(64 + ((h >> (8 * k)) & 0xFF) * 3 / 4);
+      }
+    for (float& v : pix) v = v < 0.0f ? 0.0f : v > 255.0f ? 255.0f : v;
+    const std::string pf = mattes_prefix + ".matte.png";
+    rc = dt_write_png(pf.c_str(), g.xRes, g.yRes, pix.data());
+    if (rc) return die("dt_write_png (mattes)", rc);
+    printf("mattes: %llu pixels, %d groups, %d layers, %llu overflow pixels in %.3f ms (kernel) -> %s\n",
+           (unsigned long long)mst.pixels, (int)seen.size(), L, (unsigned long long)over, mst.kernel_ms, pf.c_str());
   }
   double msps = st.samples / (st.kernel_ms * 1e-3) / 1e6;
   printf("Rendered %s frame %d: %dx%d, %d spp, depth %d in %.2f ms (kernel, %.1f Mpixel-samples/s) -> %s\n",

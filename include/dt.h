@@ -61,6 +61,8 @@ extern "C" {
  *    for animation previews) */
 /* (still 8, new exports and one new struct, no struct changed: dt_trace_rays and its dt_ray_hits,
  *    dt_rays_occluded -- ray queries: closest hit and visibility for caller-supplied rays) */
+/* (still 8, new exports and one new struct, no struct changed: dt_render_mattes and its dt_mattes,
+ *    dt_matte_mask -- object mattes: ranked per-pixel group coverage) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -504,6 +506,60 @@ typedef struct dt_features {      /* each plane optional (NULL: not wanted); all
 int dt_render_features(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
                        int32_t n_samples, const dt_features* out, int32_t out_on_device,
                        void* stream, dt_stats* stats);
+
+/* ---- object mattes: ranked per-pixel group coverage ----
+ * No reference counterpart. What a compositor cuts antialiased mattes from (the Cryptomatte-style answer):
+ * for every owned pixel the `layers` groups that cover most of it, ranked, each with its share of the
+ * pixel's samples, taken from the render's own primary rays, so that the mattes line up with the colour
+ * image edge for edge, depth of field included.
+ * Rays: the samples 0 .. n_samples-1 of every owned pixel (n_samples as for dt_render_features:
+ * dt_window_check(g, 0, n_samples)), each the render's own primary ray (RNG pixel y*xRes+x, sample i, key
+ * (seed, frame)) traced to its closest hit at shift 0 on every frame, exactly as dt_render_features traces
+ * it; in dt_intersect_primary's numbering ray ((i/8)*W*H + y*W + x)*8 + i%8.
+ * Group: a hit on shape h has group group_of_shape ? group_of_shape[h] : h. group_of_shape is always a
+ * host array of n_shapes entries, each >= 0 (the call uploads it, 4 bytes per shape); n_shapes must be the
+ * scene's shape count, with or without a map. A miss has no group.
+ * Histogram: a pixel's samples are taken in ascending sample order. A sample whose group is in the table
+ * adds 1 to its count; a sample with a new group takes the next entry while the table holds fewer than
+ * DT_MATTE_TABLE groups; after that the sample is dropped and the pixel is an overflow pixel.
+ * *overflow_pixels (optional): the owned overflow pixels, each counted once (with spp < 64 there are none).
+ * Ranking: the table's entries by count descending, ties by group ascending; layer j < layers is entry j of
+ * that order, layers beyond the table's size hold id -1, weight 0. weight is exactly
+ * (float)((double)count / (double)n_samples); distinct[q] is the table's size.
+ * Slots and sides: q is the pixel's slot exactly as in dt_render_features (DT_OUT_IMAGE and DT_OUT_SLAB
+ * alike); id and weight hold layers * dt_accum_doubles(g, tiles)/3 elements, distinct dt_accum_doubles/3.
+ * Only owned pixels are written. All planes are host (out_on_device=0: staged through device copies of the
+ * caller's arrays, as dt_render_features stages) or device (1); a NULL plane is not wanted. Synchronous.
+ * Like dt_render_features it has a launch record, counters and events of its own and shares only the
+ * scene's primary-ray lists: a render of the scene afterwards is unaffected.
+ * stats (optional): pixels produced, samples = rays = pixels * n_samples, kernel_ms; everything else 0.
+ * DT_E_INVALID, with a dt_last_error starting "dt_render_mattes: " and naming the argument: a null scene,
+ * globals or out, an out with every plane NULL, a bad n_samples, layers outside 1..DT_MATTE_MAX_LAYERS, an
+ * n_shapes that is not the scene's, a negative map entry (with its index); DT_E_UNSUPPORTED: a scene with a
+ * RectPrismWithCylinder; all before any device work. */
+typedef struct dt_mattes {      /* each plane optional (NULL: not wanted), not all NULL; all on one side */
+  int32_t* id;        /* layers per pixel, entry layers*q + j: the group ranked j, -1: no such layer */
+  float*   weight;    /* layers per pixel, same indexing: (float)((double)count / (double)n_samples), 0 for -1 */
+  int32_t* distinct;  /* 1 per pixel, entry q: distinct groups in the pixel's table (<= DT_MATTE_TABLE) */
+} dt_mattes;
+#define DT_MATTE_TABLE      64   /* distinct groups a pixel's histogram holds */
+#define DT_MATTE_MAX_LAYERS 8
+
+int dt_render_mattes(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                     int32_t n_samples, const int32_t* group_of_shape /* host, n_shapes entries, or NULL */,
+                     int32_t n_shapes, int32_t layers, const dt_mattes* out, int32_t out_on_device,
+                     void* stream, dt_stats* stats, uint64_t* overflow_pixels /* optional */);
+
+/* The matte of a set of groups: mask[q] is the f32 sum, from 0.0f, in layer order j = 0 .. layers-1, of
+ * weight[layers*q + j] over the layers whose id is in groups (a host array of 1..64 entries, each >= 0;
+ * -1 never matches). id, weight (layers * n_pixels) and mask (n_pixels) are all host (on_device=0: a host
+ * loop) or all device (1: one kernel on stream, enqueue only). DT_E_INVALID, with a dt_last_error starting
+ * "dt_matte_mask: " and naming the argument: a null pointer, n_pixels < 0, layers outside
+ * 1..DT_MATTE_MAX_LAYERS, n_groups outside 1..64, a negative group. n_pixels == 0: DT_OK, nothing is
+ * launched. */
+int dt_matte_mask(int64_t n_pixels, int32_t layers, const int32_t* id, const float* weight,
+                  const int32_t* groups, int32_t n_groups /* host array, 1..64 entries */,
+                  float* mask, int32_t on_device, void* stream);
 
 /* ---- ray queries: closest hit and visibility for rays the caller supplies ----
  * No reference counterpart: the reference traces only what its camera and its bounces produce. The
