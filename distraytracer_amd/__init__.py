@@ -15,7 +15,7 @@ an error (there is no CPU path in this package).
 import ctypes
 
 from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT, DT_OUT_IMAGE, DT_OUT_SLAB, AccelInfo, BVHNode, Camera, DenoiseParams, DenoiseVarParams, DTError, Globals, SceneDesc,
-                   Stats, TemporalParams, Tiles, check, lib)
+                   Stats, TemporalParams, Tiles, UpsampleParams, check, lib)
 
 __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_scene", "Scene",
            "render", "render_sky", "renderImage", "renderImageCloud", "write_ppm", "DATA_DIR",
@@ -28,7 +28,8 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "DenoiseVarParams", "denoise_var_params_default", "variance",
            "Camera", "camera", "TemporalParams", "temporal_params_default", "reproject", "TemporalAccumulator",
            "trace_rays", "rays_occluded", "RAY_PLANES",
-           "render_mattes", "matte_mask", "shape_groups", "MATTE_PLANES"]
+           "render_mattes", "matte_mask", "shape_groups", "MATTE_PLANES",
+           "UpsampleParams", "upsample_params_default", "upsample", "low_res_globals"]
 
 
 def globals_default():
@@ -566,6 +567,74 @@ def denoise(g, colour, feats, params=None, out=None, stream=None, variance=None)
 
 
 _denoise = denoise   # (renderImage's denoise argument hides the name)
+
+
+def upsample_params_default():
+    """dt_upsample_params_default: factor 2, demodulate 1 and the sigmas chosen in BASELINE.md."""
+    p = UpsampleParams()
+    lib.dt_upsample_params_default(ctypes.byref(p))
+    return p
+
+
+def low_res_globals(g, factor):
+    """A copy of g with xRes and yRes divided by factor (DTError if they do not divide); everything else,
+    the seed and `aspect` included, unchanged: low-resolution pixel (x, y) covers exactly the factor x factor
+    full-resolution pixels from (factor*x, factor*y)."""
+    factor = int(factor)
+    if factor < 1 or g.xRes % factor or g.yRes % factor:
+        raise DTError("low_res_globals: %dx%d is not a multiple of factor %d" % (g.xRes, g.yRes, factor))
+    lo = g.copy()
+    lo.xRes, lo.yRes = g.xRes // factor, g.yRes // factor
+    return lo
+
+
+def upsample(g_hi, colour_lo, feats_lo, feats_hi, params=None, out=None, stream=None):
+    """The guided upsampling of include/dt.h dt_upsample to a whole frame of g_hi.xRes x g_hi.yRes: colour_lo
+    (3 floats per pixel, as render / denoise give it) and feats_lo at the resolution of
+    low_res_globals(g_hi, params.factor), feats_hi at g_hi's; each feats a dict with the albedo, normal and
+    depth planes of render_features (other planes are ignored). All numpy float32 arrays (the host loop) or
+    all CUDA float32 tensors (the kernel, enqueued on `stream`). params: an UpsampleParams (None:
+    upsample_params_default()). Returns out (a new array or tensor unless given)."""
+    params = params if params is not None else upsample_params_default()
+    s = int(params.factor)
+    W, H = int(g_hi.xRes), int(g_hi.yRes)
+    if s < 2 or s > 4:
+        raise DTError("upsample: factor outside 2..4")
+    if W < 1 or H < 1 or W % s or H % s:   # (the plane sizes below divide by s)
+        raise DTError("upsample: %dx%d is not a multiple of factor %d" % (W, H, s))
+    n_hi, n_lo = W * H, (W // s) * (H // s)
+    cp, side = _ptr(colour_lo)
+    from ._lib import Features
+    fl, fh = Features(), Features()
+    for f, feats, which, n_px in ((fl, feats_lo, "feats_lo", n_lo), (fh, feats_hi, "feats_hi", n_hi)):
+        for name, need in (("albedo", 3 * n_px), ("normal", 3 * n_px), ("depth", n_px)):
+            if name not in feats:
+                raise DTError("upsample: the %s plane of %s is missing" % (name, which))
+            a = feats[name]
+            p, dev = _ptr(a)
+            if _numel_any(a) != need:
+                raise DTError("upsample: plane %s of %s holds %d elements, needs %d" % (name, which, _numel_any(a), need))
+            if dev != side:
+                raise DTError("upsample: colour_lo and the planes must all be on the same side")
+            setattr(f, name, p)
+    if _numel_any(colour_lo) != 3 * n_lo:
+        raise DTError("upsample: colour_lo holds %d elements, %dx%d needs %d" % (_numel_any(colour_lo), W // s, H // s, 3 * n_lo))
+    if out is None:
+        if side:
+            import torch
+            out = torch.empty(3 * n_hi, dtype=torch.float32, device=colour_lo.device)
+        else:
+            import numpy as np
+            out = np.empty(3 * n_hi, np.float32)
+    op, odev = _ptr(out)
+    if odev != side or _numel_any(out) != 3 * n_hi:
+        raise DTError("upsample: out must hold %d elements on the side of colour_lo" % (3 * n_hi))
+    check(lib.dt_upsample(W, H, cp, ctypes.byref(fl), ctypes.byref(fh), ctypes.byref(params), op, side,
+                          ctypes.c_void_p(stream) if stream else None, None), "dt_upsample")
+    return out
+
+
+_upsample = upsample   # (renderImage's upsample argument hides the name)
 
 
 def camera(g):
@@ -1147,8 +1216,32 @@ def denoised_filename(filename):
     return stem + ".denoised" + ext
 
 
+def _render_image_upsampled(filename, frame, built, g, how, denoise):
+    """renderImage(..., upsample=how) after the scene is built: g is the full resolution"""
+    import torch
+    params = how if isinstance(how, UpsampleParams) else upsample_params_default()
+    if not isinstance(how, UpsampleParams):
+        params.factor = int(how)
+    g_lo = low_res_globals(g, params.factor)
+    names = ("albedo", "normal", "depth")
+    scene = Scene(built, g_lo)
+    lo = torch.zeros(3 * g_lo.xRes * g_lo.yRes, dtype=torch.float32, device="cuda")
+    st = render(scene, g_lo, frame, lo)
+    feats_lo = render_features(scene, g_lo, frame, planes=names)
+    if denoise:
+        lo = _denoise(g_lo, lo, feats_lo, None if denoise is True else denoise)
+    scene.close()
+    scene = Scene(built, g)
+    feats_hi = render_features(scene, g, frame, planes=names)
+    scene.close()
+    img = _upsample(g, lo, feats_lo, feats_hi, params).cpu().numpy()
+    if filename:
+        (write_png if filename.endswith(".png") else write_ppm)(filename, g, img)
+    return img, st
+
+
 def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progressive=None, adaptive=None,
-                features=None, denoise=None):
+                features=None, denoise=None, upsample=None):
     """render_final_project.cpp:965: build (sceneBuilder names a scene.h builder), render the
     frame on the current GPU, write the PPM. Returns (image, stats). progressive=callback renders in
     one-chunk sample windows (Progressive) and calls callback(image, samples_done) with the resolved
@@ -1162,13 +1255,24 @@ def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progr
     denoised_filename(filename), as `dtrender --denoise` does; the frame file's bytes are unchanged.
     denoise="variance" or a DenoiseVarParams filters with the per-pixel colour width of dt_denoise_var on the
     adaptive sampler's variance, as `dtrender --denoise-variance` does; it needs adaptive (DTError without). A
-    scene with a RectPrismWithCylinder has no feature planes: DTError (DT_E_UNSUPPORTED)."""
+    scene with a RectPrismWithCylinder has no feature planes: DTError (DT_E_UNSUPPORTED).
+    upsample=s (2, 3 or 4) or an UpsampleParams renders a mixed-resolution preview instead, as
+    `dtrender --upsample s` computes it: the frame at low_res_globals(g, s), the albedo, normal and depth
+    planes at both resolutions (the full-resolution ones from a second Scene), then upsample(); the
+    full-resolution result is written under filename and returned, with the stats of the low-resolution
+    render. With denoise=True or a DenoiseParams the low-resolution frame is denoised first. Not with
+    progressive, adaptive, features or denoising by variance (DTError). Without upsample nothing changes."""
     import numpy as np
     by_variance = isinstance(denoise, DenoiseVarParams) or (isinstance(denoise, str) and denoise == "variance")
     if by_variance and adaptive is None:
         raise DTError("renderImage: denoise by variance needs adaptive=tol (the sums of squares are adaptive sampling's)")
     g = g if g is not None else globals_default()
+    if upsample and (progressive is not None or adaptive is not None or features or by_variance):
+        raise DTError("renderImage: upsample renders one low-resolution frame: not with progressive, adaptive, "
+                      "features or denoising by variance")
     built = build_scene(sceneBuilder, frame if builder_frame is None else builder_frame, g)
+    if upsample:
+        return _render_image_upsampled(filename, frame, built, g, upsample, denoise)
     scene = Scene(built, g)
     img = np.zeros(3 * g.xRes * g.yRes, dtype=np.float32)
     if adaptive is not None:

@@ -127,6 +127,12 @@ class DenoiseVarParams(ctypes.Structure):
                 ("sigma_albedo", c_float), ("sigma_variance", c_float), ("variance_floor", c_float), ("_pad", c_float)]
 
 
+class UpsampleParams(ctypes.Structure):
+    """dt_upsample_params: factor 2..4, demodulate 0/1, the three edge-stopping widths (> 0, inf: term off)"""
+    _fields_ = [("factor", c_int32), ("demodulate", c_int32), ("sigma_normal", c_float), ("sigma_depth", c_float),
+                ("sigma_albedo", c_float), ("_pad", c_float)]
+
+
 class Camera(ctypes.Structure):
     """dt_camera: the render's camera as dt_camera_get gives it (eye, the right / up / backward unit vectors, the
     near-plane window, the resolution)"""
@@ -180,7 +186,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_denoise_params_default", "dt_denoise_workspace_floats", "dt_denoise",
            "dt_variance", "dt_denoise_var_params_default", "dt_denoise_var_workspace_floats", "dt_denoise_var",
            "dt_camera_get", "dt_temporal_params_default", "dt_reproject",
-           "dt_trace_rays", "dt_rays_occluded", "dt_render_mattes", "dt_matte_mask"]
+           "dt_trace_rays", "dt_rays_occluded", "dt_render_mattes", "dt_matte_mask",
+           "dt_upsample_params_default", "dt_upsample"]
 
 
 class DTError(RuntimeError):
@@ -278,6 +285,9 @@ def _load():
         "dt_denoise_var_workspace_floats": (c_int64, [c_int32, c_int32, P(DenoiseVarParams)]),
         "dt_denoise_var": (c_int32, [c_int32, c_int32, ctypes.c_void_p, ctypes.c_void_p, P(Features), P(DenoiseVarParams),
                                      ctypes.c_void_p, ctypes.c_void_p, c_int32, ctypes.c_void_p, P(c_float)]),
+        "dt_upsample_params_default": (None, [P(UpsampleParams)]),
+        "dt_upsample": (c_int32, [c_int32, c_int32, ctypes.c_void_p, P(Features), P(Features), P(UpsampleParams),
+                                  ctypes.c_void_p, c_int32, ctypes.c_void_p, P(c_float)]),
         "dt_camera_get": (c_int32, [P(Globals), P(Camera)]),
         "dt_temporal_params_default": (None, [P(TemporalParams)]),
         "dt_reproject": (c_int32, [P(Camera), ctypes.c_void_p, ctypes.c_void_p, P(Features), P(Camera), P(Features),

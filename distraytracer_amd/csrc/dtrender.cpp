@@ -38,6 +38,11 @@
 //   --denoise-variance  as --denoise, with the variance-guided filter: dt_variance of the adaptive sampler's
 //                     sums, then dt_denoise_var with the default parameters (--denoise-levels applies).
 //                     Needs --adaptive: a usage error and exit status 2 without it, before any rendering.
+//   --upsample S      also a mixed-resolution preview (S = 2, 3 or 4; the resolution must divide): the frame
+//                     rendered once more at 1/S of the resolution in each axis, the albedo, normal and depth
+//                     planes at both resolutions, and dt_upsample with the default parameters on the device,
+//                     written to <stem>.upsampled.<ext> beside the frame at the full resolution. The frame
+//                     file is the same bytes as without the flag.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -115,6 +120,60 @@ static int write_denoised(const dt_scene* s, const dt_globals& g, int frame, int
   return 0;
 }
 
+// --upsample: the frame of g at 1/factor of the resolution (a scene of its own: the primary-ray lists are
+// per resolution), the guides of both resolutions (the full-resolution ones from `s`) and dt_upsample on
+// the device, written to `fn`
+static int write_upsampled(const dt_scene_desc* desc, const dt_scene* s, const dt_globals& g, int frame, int n_samples,
+                           int factor, const std::string& fn, bool png)
+{
+  dt_upsample_params up;
+  dt_upsample_params_default(&up);
+  up.factor = factor;
+  dt_globals lo = g;
+  lo.xRes = g.xRes / factor;
+  lo.yRes = g.yRes / factor;
+  const size_t n_hi = (size_t)g.xRes * g.yRes, n_lo = (size_t)lo.xRes * lo.yRes;
+  // colour, albedo, normal (3 per pixel), depth (1) at the low resolution; albedo, normal, depth, out at the full one
+  float* d = nullptr;
+  if (hipMalloc((void**)&d, 10 * (n_lo + n_hi) * sizeof(float)) != hipSuccess ||
+      hipMemset(d, 0, 10 * (n_lo + n_hi) * sizeof(float)) != hipSuccess) {
+    fprintf(stderr, "upsample buffers: hipMalloc failed\n");
+    return 1;
+  }
+  dt_features fl, fh;
+  memset(&fl, 0, sizeof fl);
+  memset(&fh, 0, sizeof fh);
+  fl.albedo = d + 3 * n_lo; fl.normal = d + 6 * n_lo; fl.depth = d + 9 * n_lo;
+  float* hi = d + 10 * n_lo;
+  fh.albedo = hi; fh.normal = hi + 3 * n_hi; fh.depth = hi + 6 * n_hi;
+  float* out = hi + 7 * n_hi;
+  dt_scene* sl = nullptr;
+  int rc = dt_scene_create(desc, &lo, &sl);
+  if (rc) return die("dt_scene_create (low resolution)", rc);
+  dt_stats st;
+  rc = dt_render(sl, &lo, frame, nullptr, d, 1, nullptr, &st);
+  if (rc) return die("dt_render (low resolution)", rc);
+  rc = dt_render_features(sl, &lo, frame, nullptr, n_samples, &fl, 1, nullptr, nullptr);
+  if (rc) return die("dt_render_features (low resolution)", rc);
+  dt_scene_destroy(sl);
+  rc = dt_render_features(s, &g, frame, nullptr, n_samples, &fh, 1, nullptr, nullptr);
+  if (rc) return die("dt_render_features", rc);
+  float ms = 0.0f;
+  rc = dt_upsample(g.xRes, g.yRes, d, &fl, &fh, &up, out, 1, nullptr, &ms);
+  if (rc) return die("dt_upsample", rc);
+  std::vector<float> img(3 * n_hi);
+  if (hipMemcpy(img.data(), out, 3 * n_hi * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+    fprintf(stderr, "upsample: hipMemcpy failed\n");
+    return 1;
+  }
+  (void)hipFree(d);
+  rc = png ? dt_write_png(fn.c_str(), g.xRes, g.yRes, img.data()) : dt_write_ppm(fn.c_str(), g.xRes, g.yRes, img.data());
+  if (rc) return die("dt_write_ppm/png (upsampled)", rc);
+  printf("upsampled: %dx%d traced in %.2f ms, dt_upsample x%d in %.3f ms (kernel) -> %s\n", lo.xRes, lo.yRes, st.kernel_ms,
+         factor, ms, fn.c_str());
+  return 0;
+}
+
 int main(int argc, char** argv)
 {
   dt_globals g;
@@ -124,7 +183,7 @@ int main(int argc, char** argv)
   int arg = (argc > 2 && argv[2][0] != '-') ? atoi(argv[2]) : 0;
   std::string out;
   std::string data_dir = DT_DATA_DIR;
-  int spp = -1, depth = -1, W = -1, H = -1, progressive = 0, min_samples = 64, denoise = 0, denoise_levels = 0, denoise_variance = 0;
+  int spp = -1, depth = -1, W = -1, H = -1, progressive = 0, min_samples = 64, denoise = 0, denoise_levels = 0, denoise_variance = 0, upsample = 0;
   double adaptive = -1.0;
   std::string counts_file, features_prefix, mattes_prefix;
   int matte_layers = 4;
@@ -146,6 +205,7 @@ int main(int argc, char** argv)
     else if (a == "--denoise") denoise = 1;
     else if (a == "--denoise-variance") denoise_variance = 1;
     else if (a == "--denoise-levels" && i + 1 < argc) denoise_levels = atoi(argv[++i]);
+    else if (a == "--upsample" && i + 1 < argc) upsample = atoi(argv[++i]);
   }
   if (denoise_variance && adaptive < 0.0) {
     fprintf(stderr, "usage: --denoise-variance needs --adaptive TOL (the variance comes from the adaptive sampler's sums)\n");
@@ -203,6 +263,10 @@ int main(int argc, char** argv)
   if (spp > 0) g.antialias_samples = spp;
   if (depth > 0) g.max_depth = depth;
   if (W > 0) { g.xRes = W; g.yRes = H; }
+  if (upsample && (upsample < 2 || upsample > 4 || g.xRes % upsample || g.yRes % upsample)) {
+    fprintf(stderr, "usage: --upsample S needs S = 2, 3 or 4 and a resolution that S divides (%dx%d)\n", g.xRes, g.yRes);
+    return 2;
+  }
   dt_scene* s = nullptr;
   rc = dt_scene_create(desc, &g, &s);
   if (rc) return die("dt_scene_create", rc);
@@ -214,6 +278,7 @@ int main(int argc, char** argv)
   const size_t slash = fn.find_last_of('/'), dot = fn.find_last_of('.');
   const bool has_ext = dot != std::string::npos && dot > (slash == std::string::npos ? 0 : slash + 1);
   const std::string dn_fn = has_ext ? fn.substr(0, dot) + ".denoised" + fn.substr(dot) : fn + ".denoised";
+  const std::string up_fn = has_ext ? fn.substr(0, dot) + ".upsampled" + fn.substr(dot) : fn + ".upsampled";
   int samples_taken = (int)sqrt((double)g.antialias_samples);
   samples_taken *= samples_taken;
   if (adaptive >= 0.0) {
@@ -321,6 +386,10 @@ int main(int argc, char** argv)
     rc = png ? dt_write_png(fn.c_str(), g.xRes, g.yRes, img.data()) : dt_write_ppm(fn.c_str(), g.xRes, g.yRes, img.data());
     if (rc) return die("dt_write_ppm/png", rc);
     if (denoise && write_denoised(s, g, frame, samples_taken, denoise_levels, img, dn_fn, png)) return 1;
+  }
+  if (upsample) {
+    const int n = (int)sqrt((double)g.antialias_samples);
+    if (int bad = write_upsampled(desc, s, g, frame, n * n, upsample, up_fn, png)) return bad;
   }
   if (!features_prefix.empty()) {
     const int n = (int)sqrt((double)g.antialias_samples);

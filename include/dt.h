@@ -63,6 +63,8 @@ extern "C" {
  *    dt_rays_occluded -- ray queries: closest hit and visibility for caller-supplied rays) */
 /* (still 8, new exports and one new struct, no struct changed: dt_render_mattes and its dt_mattes,
  *    dt_matte_mask -- object mattes: ranked per-pixel group coverage) */
+/* (still 8, new exports and one new struct, no struct changed: dt_upsample_params_default, dt_upsample and
+ *    its dt_upsample_params -- guided upsampling of previews) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -857,6 +859,78 @@ int dt_reproject(const dt_camera* cur, const float* colour, const float* varianc
                  const dt_camera* prev, const dt_features* prev_feat, const dt_history* hist_in,
                  const dt_temporal_params* p, float* out, float* out_var, const dt_history* hist_out,
                  int32_t on_device, void* stream, float* kernel_ms);
+
+/* ---- guided upsampling of previews: low-resolution lighting, full-resolution guides ----
+ * No reference counterpart. Mixed-resolution preview: the lighting is traced at 1/s of the resolution in
+ * each axis (1/s^2 of the rays), the guides (dt_render_features: albedo, normal, depth) at full
+ * resolution, and dt_upsample reconstructs the full-resolution image by joint-bilateral upsampling
+ * (Kopf et al. 2007) of the low-resolution colour demodulated by its albedo, steered by the
+ * full-resolution guides and remodulated by the full-resolution albedo, which puts texture and checker
+ * detail back at full sharpness. The camera makes the pixel correspondence exact: rays leave pixel
+ * corners at l + (r-l)*x/W and `aspect` is a global of its own, so with W = s*w, H = s*h the
+ * low-resolution pixel (x, y) covers exactly the full-resolution pixels s*x..s*x+s-1 by s*y..s*y+s-1,
+ * and in buffer rows (DT_OUT_IMAGE indexing, rows flipped) full-resolution row R lies in low-resolution
+ * row R div s.
+ *
+ * Whole frames only, DT_OUT_IMAGE indexing. W = xRes, H = yRes, s = factor, w = W/s, h = H/s. Primes mark
+ * the low-resolution planes: C' (3 per pixel, what dt_render / dt_resolve / dt_denoise give at w x h),
+ * A', N' (3 per pixel), Z' (1 per pixel) of feat_lo at w x h; A, N, Z of feat_hi at W x H. Coverage is not
+ * read. All arithmetic is IEEE f32, every operation below one rounded operation (no contraction, no libm
+ * beyond floorf, fabsf, fminf, fmaxf), the same on the host and on the device.
+ *   dot(u,u) = (u0*u0 + u1*u1) + u2*u2
+ * Constants, computed on the host:
+ *   isn = 1.0f/(sn*sn)   isa = 1.0f/(sa*sa)   isz = 1.0f/(sz*sz)   fs = (float)s
+ *                                                       sn, sz, sa: sigma_normal, _depth, _albedo
+ * Low-resolution pixel q (computed per tap, nothing is stored):
+ *   d'[k]   = demodulate ? fmaxf(A'_q[k], 0.0625f) : 1.0f
+ *   E'_q[k] = C'_q[k] / d'[k]
+ *   q is bad if any channel of C'_q is NaN
+ * Full-resolution pixel p = (R, X), slot R*W + X:
+ *   d[k] = demodulate ? fmaxf(A_p[k], 0.0625f) : 1.0f
+ *   rz = 1.0f / (Z_p*Z_p + 1e-6f)
+ *   xc = X / s ; rc = R / s                              (integer division)
+ *   fx = ((float)X + 0.5f) / fs - 0.5f ; fy = ((float)R + 0.5f) / fs - 0.5f
+ * Taps j = -1..1 (outer, rows), i = -1..1 (inner), q = (rc+j, xc+i); a tap outside the low-resolution
+ * image is skipped (no clamping), a bad tap is skipped:
+ *   T(t) = fmaxf(0.0f, 1.0f - fabsf(t) * 0.5f)           (a tent of half-width 2 low-resolution pixels)
+ *   hsp  = T(fx - (float)(xc+i)) * T(fy - (float)(rc+j))
+ *   xn = dot(N_p - N'_q) * isn
+ *   xa = dot(A_p - A'_q) * isa
+ *   dz = Z_p - Z'_q ; xz = ((dz*dz) * rz) * isz
+ *   R(x) = t*t with t = fmaxf(0.0f, 1.0f - x)            (fmaxf drops a NaN: weight 0)
+ *   w  = (hsp * (R(xn) * R(xz))) * R(xa)
+ *   if (w > 0) { S[k] = S[k] + w * E'_q[k] (k = 0,1,2) ; Wt = Wt + w }       S, Wt from 0
+ * Result:
+ *   E[k] = Wt > 0 ? S[k] / Wt : E'_(rc,xc)[k]            (the fallback: the nearest low-resolution pixel)
+ *   out[3p+k] = fminf(fmaxf(E[k] * d[k], 0.0f), 255.0f)
+ *   if Wt == 0 and (rc, xc) is bad: out[3p+k] = C'_(rc,xc)[k], all three channels unchanged
+ * Limits: the guides are first-hit only, so the contents of a mirror or a glass pane are upsampled by the
+ * spatial term alone; the lighting keeps its low-resolution detail, so shadow edges and specular
+ * highlights stay soft; whole frames only (a tile share or a slab lacks its neighbours).
+ *
+ * factor: 2, 3 or 4. Each sigma > 0; +inf disables its term. dt_upsample_params_default: factor 2,
+ * demodulate 1 and the sigmas chosen in BASELINE.md. */
+typedef struct dt_upsample_params {
+  int32_t factor;        /* s: 2, 3 or 4 */
+  int32_t demodulate;    /* 0 or 1 */
+  float   sigma_normal;  /* > 0, +inf disables the term */
+  float   sigma_depth;
+  float   sigma_albedo;
+  float   _pad;
+} dt_upsample_params;
+
+void dt_upsample_params_default(dt_upsample_params* p);
+/* xRes, yRes: the full resolution W, H. colour_lo: 3*w*h floats; feat_lo, feat_hi need albedo, normal and
+ * depth (at w x h and W x H), their other planes are ignored; out: 3*W*H floats. All on one side: host
+ * (on_device=0: a plain loop) or device (1: one kernel on `stream`, enqueue only; with kernel_ms it is
+ * timed with HIP events and the call synchronises). No workspace: E' is computed per tap. out must not
+ * alias an input; nothing outside it is written. DT_E_INVALID before any device work, with a
+ * dt_last_error starting "dt_upsample: " and naming the argument: a null argument or a missing plane,
+ * xRes or yRes < 1, a factor outside 2..4, xRes or yRes not a multiple of the factor, demodulate not 0 or
+ * 1, a sigma that is <= 0 or NaN, aliasing. */
+int  dt_upsample(int32_t xRes, int32_t yRes, const float* colour_lo, const dt_features* feat_lo,
+                 const dt_features* feat_hi, const dt_upsample_params* p, float* out, int32_t on_device,
+                 void* stream, float* kernel_ms);
 
 /* renderImageCloud (render_final_project.cpp:1224-1279). Sets eye/up/lookingAt as the
  * reference does (1227-1229) on a local copy; g is not modified. */
