@@ -200,23 +200,44 @@ def intersect_primary(scene, g, frame, first_ray, hit_shape, hit_t, stream=None)
 
 
 FEATURE_PLANES = ("albedo", "normal", "depth", "coverage", "shape")
+GUIDE_MAX_BOUNCES = 8   # DT_GUIDE_MAX_BOUNCES
+GUIDE_STOP, GUIDE_REFLECT, GUIDE_REFRACT = 0, 1, 2
+
+
+def guide_bounce(g, material, flags, inside, in_dir, normal, point):
+    """The bounce rule of the specular-path feature buffers for one hit (include/dt.h dt_guide_bounce):
+    (result, next_dir, next_start) with result GUIDE_STOP, GUIDE_REFLECT or GUIDE_REFRACT and the next
+    segment's unnormalised direction and start as tuples of 3 floats (None, None for GUIDE_STOP). in_dir is
+    the normalised ray, normal the fixNorm'ed normal, point the hit point."""
+    D3 = ctypes.c_double * 3
+    a, b, c = D3(*[float(v) for v in in_dir]), D3(*[float(v) for v in normal]), D3(*[float(v) for v in point])
+    nd, ns = D3(), D3()
+    rc = lib.dt_guide_bounce(ctypes.byref(g), int(material), int(flags), int(inside), a, b, c, nd, ns)
+    if rc < 0:
+        check(rc, "dt_guide_bounce")
+    return (rc, tuple(nd), tuple(ns)) if rc else (rc, None, None)
 
 
 def render_features(scene, g, frame, n_samples=None, tile=None, stream=None, planes=FEATURE_PLANES, out=None,
-                    stats=None):
+                    stats=None, specular_bounces=0):
     """First-hit feature buffers of the leading n_samples samples (None: spp) of every owned pixel
     (include/dt.h dt_render_features): a dict plane name -> tensor. albedo and normal hold
     accum_doubles(g, tile) float32 elements, indexed like render's output; depth and coverage
     (float32) and shape (int32) a third of that, entry q for the pixel at floats 3q..3q+2. `out`: a
     dict of planes to write into, all CUDA torch tensors or all host arrays (numpy, CPU tensors),
     where only owned pixels are written; without it, new CUDA tensors (zeros, shape -1). stats: a Stats
-    to fill with the call's counts."""
+    to fill with the call's counts.
+    specular_bounces=K (1..8): the specular-path feature buffers instead (dt_render_features_path): the guide
+    ray follows up to K perfect specular bounces and the planes describe the surface it ends on; "bounces"
+    (float32, one per pixel: the mean number of segments followed beyond the first) is then a legal plane."""
     n3 = accum_doubles(g, tile)
     n = _spp(g) if n_samples is None else int(n_samples)
+    path = int(specular_bounces) != 0
+    legal = FEATURE_PLANES + ("bounces",) if path else FEATURE_PLANES
     if out is None:
         import torch
         for name in planes:
-            if name not in FEATURE_PLANES:
+            if name not in legal:
                 raise DTError("render_features: unknown plane %r" % (name,))
         out = {name: (torch.full((n3 // 3,), -1, dtype=torch.int32, device="cuda") if name == "shape" else
                       torch.zeros(n3 if name in ("albedo", "normal") else n3 // 3, dtype=torch.float32, device="cuda"))
@@ -224,8 +245,9 @@ def render_features(scene, g, frame, n_samples=None, tile=None, stream=None, pla
     from ._lib import Features
     f = Features()
     side = None
+    bounces_p = None
     for name, a in out.items():
-        if name not in FEATURE_PLANES:
+        if name not in legal:
             raise DTError("render_features: unknown plane %r" % (name,))
         p, dev = _ptr_typed(a, "torch.int32", "int32") if name == "shape" else _ptr(a)
         need = n3 if name in ("albedo", "normal") else n3 // 3
@@ -235,8 +257,17 @@ def render_features(scene, g, frame, n_samples=None, tile=None, stream=None, pla
         if side is not None and dev != side:
             raise DTError("render_features: the planes must all be on the same side")
         side = dev
-        setattr(f, name, p)
+        if name == "bounces":
+            bounces_p = p
+        else:
+            setattr(f, name, p)
     st = stats if stats is not None else Stats()
+    if path:
+        check(lib.dt_render_features_path(scene.handle, ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None,
+                                          n, int(specular_bounces), ctypes.byref(f), bounces_p, side or 0,
+                                          ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)),
+              "dt_render_features_path")
+        return out
     check(lib.dt_render_features(scene.handle, ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None, n,
                                  ctypes.byref(f), side or 0, ctypes.c_void_p(stream) if stream else None,
                                  ctypes.byref(st)), "dt_render_features")
@@ -923,13 +954,15 @@ class Progressive:
         self.nan_pixels = resolve(self.g, self.accum, self.samples_done, out, self.tile)
         return out
 
-    def features(self, planes=FEATURE_PLANES):
+    def features(self, planes=FEATURE_PLANES, specular_bounces=0):
         """The first-hit feature buffers of the samples rendered so far (render_features of the leading
         samples_done samples of every owned pixel, in the accumulator's layout; with adaptive sampling
-        of every pixel alike, whether or not it has stopped)."""
+        of every pixel alike, whether or not it has stopped). specular_bounces=K: the specular-path
+        buffers of those samples, as render_features takes it."""
         if self.samples_done < 1:
             raise DTError("Progressive.features: no window rendered yet")
-        return render_features(self.scene, self.g, self.frame, self.samples_done, self.tile, planes=planes)
+        return render_features(self.scene, self.g, self.frame, self.samples_done, self.tile, planes=planes,
+                               specular_bounces=specular_bounces)
 
     def mattes(self, groups=None, layers=4):
         """The object mattes of the samples rendered so far (render_mattes of the leading samples_done
@@ -1216,7 +1249,7 @@ def denoised_filename(filename):
     return stem + ".denoised" + ext
 
 
-def _render_image_upsampled(filename, frame, built, g, how, denoise):
+def _render_image_upsampled(filename, frame, built, g, how, denoise, guide_bounces=0):
     """renderImage(..., upsample=how) after the scene is built: g is the full resolution"""
     import torch
     params = how if isinstance(how, UpsampleParams) else upsample_params_default()
@@ -1227,12 +1260,12 @@ def _render_image_upsampled(filename, frame, built, g, how, denoise):
     scene = Scene(built, g_lo)
     lo = torch.zeros(3 * g_lo.xRes * g_lo.yRes, dtype=torch.float32, device="cuda")
     st = render(scene, g_lo, frame, lo)
-    feats_lo = render_features(scene, g_lo, frame, planes=names)
+    feats_lo = render_features(scene, g_lo, frame, planes=names, specular_bounces=guide_bounces)
     if denoise:
         lo = _denoise(g_lo, lo, feats_lo, None if denoise is True else denoise)
     scene.close()
     scene = Scene(built, g)
-    feats_hi = render_features(scene, g, frame, planes=names)
+    feats_hi = render_features(scene, g, frame, planes=names, specular_bounces=guide_bounces)
     scene.close()
     img = _upsample(g, lo, feats_lo, feats_hi, params).cpu().numpy()
     if filename:
@@ -1241,7 +1274,7 @@ def _render_image_upsampled(filename, frame, built, g, how, denoise):
 
 
 def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progressive=None, adaptive=None,
-                features=None, denoise=None, upsample=None):
+                features=None, denoise=None, upsample=None, guide_bounces=0):
     """render_final_project.cpp:965: build (sceneBuilder names a scene.h builder), render the
     frame on the current GPU, write the PPM. Returns (image, stats). progressive=callback renders in
     one-chunk sample windows (Progressive) and calls callback(image, samples_done) with the resolved
@@ -1261,7 +1294,10 @@ def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progr
     planes at both resolutions (the full-resolution ones from a second Scene), then upsample(); the
     full-resolution result is written under filename and returned, with the stats of the low-resolution
     render. With denoise=True or a DenoiseParams the low-resolution frame is denoised first. Not with
-    progressive, adaptive, features or denoising by variance (DTError). Without upsample nothing changes."""
+    progressive, adaptive, features or denoising by variance (DTError). Without upsample nothing changes.
+    guide_bounces=K (1..8) takes the specular-path feature buffers (render_features(specular_bounces=K)) for
+    the feature images, both denoisers and the upsampler, as `dtrender --guide-bounces K` does: the guides
+    then describe what mirrors and glass show. With 0 nothing changes."""
     import numpy as np
     by_variance = isinstance(denoise, DenoiseVarParams) or (isinstance(denoise, str) and denoise == "variance")
     if by_variance and adaptive is None:
@@ -1272,7 +1308,7 @@ def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progr
                       "features or denoising by variance")
     built = build_scene(sceneBuilder, frame if builder_frame is None else builder_frame, g)
     if upsample:
-        return _render_image_upsampled(filename, frame, built, g, upsample, denoise)
+        return _render_image_upsampled(filename, frame, built, g, upsample, denoise, guide_bounces)
     scene = Scene(built, g)
     img = np.zeros(3 * g.xRes * g.yRes, dtype=np.float32)
     if adaptive is not None:
@@ -1293,13 +1329,15 @@ def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progr
     if filename:
         (write_png if filename.endswith(".png") else write_ppm)(filename, g, img)
     if features:
-        planes = render_features(scene, g, frame, planes=("albedo", "normal", "depth", "coverage"))
+        planes = render_features(scene, g, frame, planes=("albedo", "normal", "depth", "coverage"),
+                                 specular_bounces=guide_bounces)
         for name, v in feature_images(g, {k: t.cpu().numpy() for k, t in planes.items()}).items():
             write_png("%s.%s.png" % (features, name), g, v)
     if denoise and filename:
         import torch
         n = p.samples_done if adaptive is not None else None
-        planes = render_features(scene, g, frame, n, planes=("albedo", "normal", "depth"))
+        planes = render_features(scene, g, frame, n, planes=("albedo", "normal", "depth"),
+                                 specular_bounces=guide_bounces)
         if by_variance:
             clean = _denoise(g, torch.from_numpy(img).to("cuda"), planes, None if denoise == "variance" else denoise,
                              variance=p.variance())

@@ -187,7 +187,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_variance", "dt_denoise_var_params_default", "dt_denoise_var_workspace_floats", "dt_denoise_var",
            "dt_camera_get", "dt_temporal_params_default", "dt_reproject",
            "dt_trace_rays", "dt_rays_occluded", "dt_render_mattes", "dt_matte_mask",
-           "dt_upsample_params_default", "dt_upsample"]
+           "dt_upsample_params_default", "dt_upsample",
+           "dt_guide_bounce", "dt_render_features_path"]
 
 
 class DTError(RuntimeError):
@@ -267,6 +268,10 @@ def _load():
                                            ctypes.c_void_p, c_int32, ctypes.c_void_p, P(c_float)]),
         "dt_render_features": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, P(Features), c_int32,
                                          ctypes.c_void_p, P(Stats)]),
+        "dt_guide_bounce": (c_int32, [P(Globals), c_int32, ctypes.c_uint32, c_int32, P(c_double), P(c_double), P(c_double),
+                                      P(c_double), P(c_double)]),
+        "dt_render_features_path": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, c_int32,
+                                              P(Features), ctypes.c_void_p, c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_trace_rays": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p, P(RayHits),
                                     c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_rays_occluded": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p,

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "dt_adapt.h"
+#include "dt_guide.h"
 #include "host_internal.h"
 
 using namespace dth;
@@ -90,6 +91,10 @@ extern "C" const void* dt_isect_kernel_ptr(void);
 extern "C" hipError_t dt_launch_features(const void* dev_launch, int n_samples, float* albedo, float* normal, float* depth,
                                          float* coverage, int32_t* shape, int grid, hipStream_t stream);
 extern "C" const void* dt_features_kernel_ptr(void);
+extern "C" hipError_t dt_launch_features_path(const void* dev_launch, int n_samples, int max_bounces, float* albedo,
+                                              float* normal, float* depth, float* coverage, int32_t* shape,
+                                              float* bounces, int grid, hipStream_t stream);
+extern "C" const void* dt_features_path_kernel_ptr(void);
 extern "C" hipError_t dt_launch_rayq(const void* dev_launch, int64_t n, const double* start, const double* dir,
                                      int32_t* shape, float* t, double* point, double* normal, double* albedo, int grid,
                                      hipStream_t stream);
@@ -1685,17 +1690,24 @@ int dt_intersect_primary(const dt_scene* sc_c, const dt_globals* g, int32_t fram
 // First-hit feature buffers: dt_features_kernel over the samples 0 .. n_samples-1 of every owned pixel.
 // Synchronous; like dt_intersect_primary its launch record, counters and events are its own and it
 // shares only the scene's primary-ray lists. Every argument check comes before the scene is looked at.
-int dt_render_features(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
-                       int32_t n_samples, const dt_features* out, int32_t out_on_device, void* stream, dt_stats* stats)
+// Specular-path feature buffers (dt_render_features_path, `path`): the same call with
+// dt_features_path_kernel, max_bounces and one more plane; its errors carry its own prefix.
+static int render_features_common(bool path, const dt_scene* sc_c, const dt_globals* g, int32_t frame,
+                                  const dt_tiles* tiles, int32_t n_samples, int32_t max_bounces, const dt_features* out,
+                                  float* bounces, int32_t out_on_device, void* stream, dt_stats* stats)
 {
   dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  if (!sc) return fail(DT_E_INVALID, "dt_render_features: null scene");
-  if (!g) return fail(DT_E_INVALID, "dt_render_features: null globals");
-  if (!out) return fail(DT_E_INVALID, "dt_render_features: null planes");
-  if (!out->albedo && !out->normal && !out->depth && !out->coverage && !out->shape)
-    return fail(DT_E_INVALID, "dt_render_features: no plane wanted (every pointer is null)");
-  if (int rc = dt_window_check(g, 0, n_samples)) return rc;
-  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_render_features: scenes with a RectPrismWithCylinder");
+  const std::string who = path ? "dt_render_features_path: " : "dt_render_features: ";
+  if (!sc) return fail(DT_E_INVALID, who + "null scene");
+  if (!g) return fail(DT_E_INVALID, who + "null globals");
+  if (!out) return fail(DT_E_INVALID, who + "null planes");
+  if (!out->albedo && !out->normal && !out->depth && !out->coverage && !out->shape && !bounces)
+    return fail(DT_E_INVALID, who + "no plane wanted (every pointer is null)");
+  if (int rc = dt_window_check(g, 0, n_samples)) return path ? fail(rc, who + "n_samples: " + g_err) : rc;
+  if (path && (max_bounces < 0 || max_bounces > DT_GUIDE_MAX_BOUNCES))
+    return fail(DT_E_INVALID, who + "max_bounces must be in 0.." + std::to_string(DT_GUIDE_MAX_BOUNCES) + ", got " +
+                                  std::to_string(max_bounces));
+  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, who + "scenes with a RectPrismWithCylinder");
   hipStream_t st = (hipStream_t)stream;
   dtd::DParams P;
   std::vector<float> zs;
@@ -1717,12 +1729,12 @@ int dt_render_features(const dt_scene* sc_c, const dt_globals* g, int32_t frame,
   }
   struct Tmp {   // released on every return path, after the stream's work that may use them
     hipStream_t st = nullptr;
-    void *launch = nullptr, *stats = nullptr, *plane[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    void *launch = nullptr, *stats = nullptr, *plane[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~Tmp()
     {
       if (launch) (void)hipStreamSynchronize(st);
-      for (void* b : {launch, stats, plane[0], plane[1], plane[2], plane[3], plane[4]})
+      for (void* b : {launch, stats, plane[0], plane[1], plane[2], plane[3], plane[4], plane[5]})
         if (b) (void)hipFree(b);
       if (e0) (void)hipEventDestroy(e0);
       if (e1) (void)hipEventDestroy(e1);
@@ -1743,28 +1755,33 @@ int dt_render_features(const dt_scene* sc_c, const dt_globals* g, int32_t frame,
   HIPCHK(hipMemcpyAsync(tmp.launch, L.data(), L.size(), hipMemcpyHostToDevice, st));
   // host planes are staged through device copies of the caller's arrays: the entries of pixels this
   // rank does not own go back as they came
-  void* host[5] = {out->albedo, out->normal, out->depth, out->coverage, out->shape};
-  void* dev[5] = {out->albedo, out->normal, out->depth, out->coverage, out->shape};
-  const size_t bytes[5] = {(size_t)n3 * sizeof(float), (size_t)n3 * sizeof(float), (size_t)n1 * sizeof(float),
-                           (size_t)n1 * sizeof(float), (size_t)n1 * sizeof(int32_t)};
+  void* host[6] = {out->albedo, out->normal, out->depth, out->coverage, out->shape, bounces};
+  void* dev[6] = {out->albedo, out->normal, out->depth, out->coverage, out->shape, bounces};
+  const size_t bytes[6] = {(size_t)n3 * sizeof(float), (size_t)n3 * sizeof(float), (size_t)n1 * sizeof(float),
+                           (size_t)n1 * sizeof(float), (size_t)n1 * sizeof(int32_t), (size_t)n1 * sizeof(float)};
   if (!out_on_device)
-    for (int k = 0; k < 5; ++k)
+    for (int k = 0; k < 6; ++k)
       if (host[k]) {
         HIPCHK(hipMalloc(&tmp.plane[k], bytes[k]));
         HIPCHK(hipMemcpyAsync(tmp.plane[k], host[k], bytes[k], hipMemcpyHostToDevice, st));
         dev[k] = tmp.plane[k];
       }
-  static int resident = 0;
-  if (!resident) resident = max_resident_waves(dt_features_kernel_ptr(), 64);
+  static int resident_first = 0, resident_path = 0;
+  int& resident = path ? resident_path : resident_first;
+  if (!resident) resident = max_resident_waves(path ? dt_features_path_kernel_ptr() : dt_features_kernel_ptr(), 64);
   const int grid = (int)(P.n_items < resident ? P.n_items : resident);
   HIPCHK(hipEventCreate(&tmp.e0));
   HIPCHK(hipEventCreate(&tmp.e1));
   HIPCHK(hipEventRecord(tmp.e0, st));
-  HIPCHK(dt_launch_features(tmp.launch, n_samples, (float*)dev[0], (float*)dev[1], (float*)dev[2], (float*)dev[3],
-                            (int32_t*)dev[4], grid > 0 ? grid : 1, st));
+  if (path)
+    HIPCHK(dt_launch_features_path(tmp.launch, n_samples, max_bounces, (float*)dev[0], (float*)dev[1], (float*)dev[2],
+                                   (float*)dev[3], (int32_t*)dev[4], (float*)dev[5], grid > 0 ? grid : 1, st));
+  else
+    HIPCHK(dt_launch_features(tmp.launch, n_samples, (float*)dev[0], (float*)dev[1], (float*)dev[2], (float*)dev[3],
+                              (int32_t*)dev[4], grid > 0 ? grid : 1, st));
   HIPCHK(hipEventRecord(tmp.e1, st));
   if (!out_on_device)
-    for (int k = 0; k < 5; ++k)
+    for (int k = 0; k < 6; ++k)
       if (host[k]) HIPCHK(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, st));
   unsigned long long h[ST_N + 1];
   HIPCHK(hipMemcpyAsync(h, tmp.stats, n_stats, hipMemcpyDeviceToHost, st));
@@ -1775,13 +1792,44 @@ int dt_render_features(const dt_scene* sc_c, const dt_globals* g, int32_t frame,
     HIPCHK(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
     stats->pixels = pixels;
     stats->samples = pixels * (uint64_t)n_samples;
-    stats->rays = stats->samples;
+    stats->rays = path ? h[ST_RAYS] : stats->samples;   // path: the segments traced
+    if (path) stats->reflect_errors = h[ST_REFL];
     stats->tex_fetches = h[ST_TEX];
     stats->uv_out_of_range = h[ST_UV];
     stats->prism_norm_fallback = h[ST_PRISM];
     stats->kernel_ms = ms;
   }
   return DT_OK;
+}
+
+int dt_render_features(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t n_samples,
+                       const dt_features* out, int32_t out_on_device, void* stream, dt_stats* stats)
+{
+  return render_features_common(false, s, g, frame, tiles, n_samples, 0, out, nullptr, out_on_device, stream, stats);
+}
+
+int dt_render_features_path(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                            int32_t n_samples, int32_t max_bounces, const dt_features* out, float* bounces,
+                            int32_t out_on_device, void* stream, dt_stats* stats)
+{
+  return render_features_common(true, s, g, frame, tiles, n_samples, max_bounces, out, bounces, out_on_device, stream,
+                                stats);
+}
+
+// The bounce rule of dt_render_features_path for one hit (dt_guide.h), for tests and callers.
+int dt_guide_bounce(const dt_globals* g, int32_t material, uint32_t flags, int32_t inside, const double in[3],
+                    const double n[3], const double p[3], double next_dir[3], double next_start[3])
+{
+  if (!g || !in || !n || !p || !next_dir || !next_start) return fail(DT_E_INVALID, "dt_guide_bounce: null argument");
+  dtm::V3 nd = dtm::v3(0, 0, 0), ns = dtm::v3(0, 0, 0);
+  bool refl_err = false;
+  const int rc = dtd::guide_bounce(g->reflect, g->nogloss, g->refr_air, g->refr_glass, material, flags, inside,
+                                   dtm::v3a(in), dtm::v3a(n), dtm::v3a(p), nd, ns, refl_err);
+  if (rc != dtd::DT_GUIDE_STOP) {
+    next_dir[0] = nd.x; next_dir[1] = nd.y; next_dir[2] = nd.z;
+    next_start[0] = ns.x; next_start[1] = ns.y; next_start[2] = ns.z;
+  }
+  return rc;
 }
 
 // Object mattes: dt_mattes_kernel over the samples 0 .. n_samples-1 of every owned pixel. Synchronous; as

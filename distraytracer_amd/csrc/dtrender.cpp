@@ -43,6 +43,12 @@
 //                     planes at both resolutions, and dt_upsample with the default parameters on the device,
 //                     written to <stem>.upsampled.<ext> beside the frame at the full resolution. The frame
 //                     file is the same bytes as without the flag.
+//   --guide-bounces K the feature buffers of --features, --denoise, --denoise-variance and --upsample are the
+//                     specular-path ones (dt_render_features_path, K = 1..8 perfect specular bounces): the
+//                     guides describe what mirrors and glass show, not the reflector. Without it (or with 0)
+//                     every byte written is the same as before.
+//   --nogloss         glossy reflectors render as perfect mirrors (dt_globals.nogloss = 1, the reference's
+//                     switch): the steel doors, the floor and the checker cylinder of `final` then bounce guides
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -60,6 +66,16 @@ static int die(const char* what, int rc)
 {
   fprintf(stderr, "%s failed (%d): %s\n", what, rc, dt_last_error());
   return 1;
+}
+
+// --guide-bounces K: the guides of every consumer below are dt_render_features_path's
+static int guide_bounces = 0;
+static int render_guides(const dt_scene* s, const dt_globals& g, int frame, int n_samples, const dt_features* f,
+                         int on_device, dt_stats* st)
+{
+  if (guide_bounces > 0)
+    return dt_render_features_path(s, &g, frame, nullptr, n_samples, guide_bounces, f, nullptr, on_device, nullptr, st);
+  return dt_render_features(s, &g, frame, nullptr, n_samples, f, on_device, nullptr, st);
 }
 
 // the adaptive sampler's device buffers (--denoise-variance filters by them; all null: --denoise)
@@ -97,7 +113,7 @@ static int write_denoised(const dt_scene* s, const dt_globals& g, int frame, int
   memset(&f, 0, sizeof f);
   f.albedo = d + 3 * n_px; f.normal = d + 6 * n_px; f.depth = d + 9 * n_px;
   float* out = d + 10 * n_px;
-  int rc = dt_render_features(s, &g, frame, nullptr, n_samples, &f, 1, nullptr, nullptr);
+  int rc = render_guides(s, g, frame, n_samples, &f, 1, nullptr);
   if (rc) return die("dt_render_features", rc);
   if (sums) {
     float* var = d + 13 * n_px;
@@ -153,10 +169,10 @@ static int write_upsampled(const dt_scene_desc* desc, const dt_scene* s, const d
   dt_stats st;
   rc = dt_render(sl, &lo, frame, nullptr, d, 1, nullptr, &st);
   if (rc) return die("dt_render (low resolution)", rc);
-  rc = dt_render_features(sl, &lo, frame, nullptr, n_samples, &fl, 1, nullptr, nullptr);
+  rc = render_guides(sl, lo, frame, n_samples, &fl, 1, nullptr);
   if (rc) return die("dt_render_features (low resolution)", rc);
   dt_scene_destroy(sl);
-  rc = dt_render_features(s, &g, frame, nullptr, n_samples, &fh, 1, nullptr, nullptr);
+  rc = render_guides(s, g, frame, n_samples, &fh, 1, nullptr);
   if (rc) return die("dt_render_features", rc);
   float ms = 0.0f;
   rc = dt_upsample(g.xRes, g.yRes, d, &fl, &fh, &up, out, 1, nullptr, &ms);
@@ -186,7 +202,7 @@ int main(int argc, char** argv)
   int spp = -1, depth = -1, W = -1, H = -1, progressive = 0, min_samples = 64, denoise = 0, denoise_levels = 0, denoise_variance = 0, upsample = 0;
   double adaptive = -1.0;
   std::string counts_file, features_prefix, mattes_prefix;
-  int matte_layers = 4;
+  int matte_layers = 4, nogloss = 0;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     if (a == "--out" && i + 1 < argc) out = argv[++i];
@@ -206,6 +222,12 @@ int main(int argc, char** argv)
     else if (a == "--denoise-variance") denoise_variance = 1;
     else if (a == "--denoise-levels" && i + 1 < argc) denoise_levels = atoi(argv[++i]);
     else if (a == "--upsample" && i + 1 < argc) upsample = atoi(argv[++i]);
+    else if (a == "--guide-bounces" && i + 1 < argc) guide_bounces = atoi(argv[++i]);
+    else if (a == "--nogloss") nogloss = 1;
+  }
+  if (guide_bounces < 0 || guide_bounces > DT_GUIDE_MAX_BOUNCES) {
+    fprintf(stderr, "usage: --guide-bounces K needs K in 0..%d\n", DT_GUIDE_MAX_BOUNCES);
+    return 2;
   }
   if (denoise_variance && adaptive < 0.0) {
     fprintf(stderr, "usage: --denoise-variance needs --adaptive TOL (the variance comes from the adaptive sampler's sums)\n");
@@ -262,6 +284,7 @@ int main(int argc, char** argv)
   if (scene == "spheres") { g.xRes = 256; g.yRes = 256; g.antialias_samples = 1; g.max_depth = 1; }
   if (spp > 0) g.antialias_samples = spp;
   if (depth > 0) g.max_depth = depth;
+  if (nogloss) g.nogloss = 1;
   if (W > 0) { g.xRes = W; g.yRes = H; }
   if (upsample && (upsample < 2 || upsample > 4 || g.xRes % upsample || g.yRes % upsample)) {
     fprintf(stderr, "usage: --upsample S needs S = 2, 3 or 4 and a resolution that S divides (%dx%d)\n", g.xRes, g.yRes);
@@ -399,7 +422,7 @@ int main(int argc, char** argv)
     memset(&f, 0, sizeof f);
     f.albedo = alb.data(); f.normal = nrm.data(); f.depth = dep.data(); f.coverage = cov.data();
     dt_stats fst;
-    rc = dt_render_features(s, &g, frame, nullptr, n * n, &f, 0, nullptr, &fst);
+    rc = render_guides(s, g, frame, n * n, &f, 0, &fst);
     if (rc) return die("dt_render_features", rc);
     float dmax = 0.0f;
     for (size_t q = 0; q < n_px; ++q) dmax = dep[q] > dmax ? dep[q] : dmax;

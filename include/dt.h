@@ -65,6 +65,8 @@ extern "C" {
  *    dt_matte_mask -- object mattes: ranked per-pixel group coverage) */
 /* (still 8, new exports and one new struct, no struct changed: dt_upsample_params_default, dt_upsample and
  *    its dt_upsample_params -- guided upsampling of previews) */
+/* (still 8, new exports only, no struct changed: dt_guide_bounce, dt_render_features_path -- specular-path
+ *    feature buffers: guides seen through mirrors and glass) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -508,6 +510,68 @@ typedef struct dt_features {      /* each plane optional (NULL: not wanted); all
 int dt_render_features(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
                        int32_t n_samples, const dt_features* out, int32_t out_on_device,
                        void* stream, dt_stats* stats);
+
+/* ---- specular-path feature buffers: guides seen through mirrors and glass ----
+ * No reference counterpart. dt_render_features describes the first hit, so for a mirror or a pane of glass
+ * every guide is the flat reflector's and says nothing of what it shows. Here a sample's guide ray follows
+ * perfect specular bounces, and the planes describe the first surface that is not a perfect reflector or
+ * refractor. The planes are a dt_features: dt_denoise, dt_denoise_var and dt_upsample take them as they are.
+ *
+ * The bounce rule (dt_guide_bounce; csrc/dt_guide.h, one definition for host and kernel): the render's own
+ * mirror and glass arithmetic (rayColor) without the Fresnel weights, a pure function of the hit. With
+ * in = normalized(ray), n = the fixNorm'ed normal, p = the hit point, eps = 1e-3f:
+ *   specular := g->reflect && material in {GLASS, STEEL, ALUMINUM, WATER, LINOLEUM}
+ *               && !((flags & DT_F_GLOSSY) && !g->nogloss)
+ *   not specular                -> 0 (stop: this surface is the guide)
+ *   GLASS: cos_theta = (float)dot(n, -in); sin_theta = (float)sqrt(1 - (double)cos_theta^2);
+ *          q = r1 / r2 with (r1, r2) = inside ? (refr_glass, refr_air) : (refr_air, refr_glass);
+ *          chk = (float)(1 - (double)q^2 * (1 - dot(in, n)^2))
+ *          chk >= 0 -> next_dir = (q * sin_theta) * ((1 / sin_theta) * (in + cos_theta * n)) - sqrtf(chk) * n,
+ *                      next_start = p + eps * in                                   -> 2 (refract)
+ *          otherwise the mirror rule (total internal reflection)
+ *   refl = in - (2 * dot(n, in)) * n; rn = dot(refl, n)
+ *          rn <= 0 -> 0 (the call below counts it in reflect_errors); rn <= eps -> 0;
+ *          else next_dir = refl, next_start = p + eps * refl                       -> 1 (reflect)
+ * At normal incidence on glass 1 / sin_theta is inf and next_dir is not finite: a void ray (dt_trace_rays).
+ * next_dir and next_start are written only for 1 and 2. A null argument: DT_E_INVALID. No device work. */
+int dt_guide_bounce(const dt_globals* g, int32_t material, uint32_t flags, int32_t inside, const double in[3],
+                    const double n[3], const double p[3], double next_dir[3], double next_start[3]);
+
+/* dt_render_features_path: samples, rays, slots q, layouts, sides, staging, the window rule for n_samples and
+ * "only owned pixels are written" are exactly dt_render_features's. Per sample, segment k = 0, 1, ...
+ * (segment 0 is the primary ray (ray, eye_sample)):
+ *   the segment (dir_k, start_k) is traced to its closest hit as dt_trace_rays specifies it (shift 0, dir
+ *   unnormalised): shape h_k, t_k, inside_k. A void ray (dt_trace_rays's rule) is not traced. A void ray or
+ *   a miss ends the sample as a MISS, which adds nothing to A, N, D, H below. On a hit
+ *     L   = L + (double)t_k * |dir_k|                      (f64, from 0)
+ *     p_k = start_k + (double)t_k * dir_k,   n_k = fixNorm(normalized(dir_k), getNorm(p_k))
+ *   and if k < max_bounces and the bounce rule at (h_k's material and flags, inside_k, normalized(dir_k), n_k,
+ *   p_k) says reflect or refract, the sample goes on with its next ray. Otherwise it ENDS ON h_k: its
+ *   colour is dt_render_features's colour rule at (h_k, p_k), its normal n_k (world space, not un-reflected:
+ *   the normal of what the mirror shows), its depth L, the length of the whole path.
+ * Planes, from the f64 left-to-right sums over the samples in ascending order, n = n_samples, H = the samples
+ * that ended on a surface, B = the sum over all n samples of the segments followed beyond the first:
+ *   albedo = (float)(A / n)   normal = (float)(N / n)   coverage = (float)(H / n)
+ *   depth = H ? (float)(D / H) : 0       shape[q] = the shape sample 0 ended on (-1: a miss)
+ *   bounces[q] = (float)(B / n)          (optional; 1 per pixel, entry q, on the side of the planes)
+ * max_bounces = 0 is dt_render_features bit for bit in every plane (bounces is 0).
+ * stats (optional): pixels, samples = pixels * n, rays = the segments traced, reflect_errors, tex_fetches,
+ * uv_out_of_range and prism_norm_fallback (every segment's hit takes its normal), kernel_ms; everything else 0.
+ * Errors as dt_render_features (bounces counts as a plane: with it, every pointer of out may be NULL), with a
+ * dt_last_error starting "dt_render_features_path: ", plus max_bounces outside 0..DT_GUIDE_MAX_BOUNCES:
+ * DT_E_INVALID; a scene with a RectPrismWithCylinder: DT_E_UNSUPPORTED; all before any device work.
+ * Synchronous, with a launch record, counters and events of its own; it shares only the scene's primary-ray
+ * lists, and a render of the scene afterwards is unaffected.
+ * Limits. Glossy reflectors (DT_F_GLOSSY with nogloss = 0) stop the chain: they are rough, and their own
+ * surface is the right guide. Glass follows transmission only, never its reflection. dt_reproject must keep
+ * first-hit guides: its world point is the first hit's, and a path's depth and normal do not reproject.
+ * Cost: after the first bounce a wave visits the union of its lanes' nodes, so a later segment costs nearer
+ * dt_trace_rays's scattered figure than its camera-order one. */
+#define DT_GUIDE_MAX_BOUNCES 8
+int dt_render_features_path(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                            int32_t n_samples, int32_t max_bounces /* 0..DT_GUIDE_MAX_BOUNCES */,
+                            const dt_features* out, float* bounces /* optional, 1 per pixel */,
+                            int32_t out_on_device, void* stream, dt_stats* stats);
 
 /* ---- object mattes: ranked per-pixel group coverage ----
  * No reference counterpart. What a compositor cuts antialiased mattes from (the Cryptomatte-style answer):
