@@ -1608,9 +1608,145 @@ int dt_resolve_adaptive(const dt_globals* g, const dt_tiles* tiles, const double
   return DT_OK;
 }
 
+// One synchronous launch of an auxiliary kernel (the Makefile's AUX_BUILDS: the intersection benchmark, the
+// feature buffers, the mattes, the ray queries). The launch record, the counters and the two events are
+// the call's own, so it may run beside renders of the same scene on other streams. The caller checks its
+// arguments and calls prepare_render; then begin(), plane() per array, start(), the kernel's launch
+// wrapper as finish()'s argument. Everything is released on every return path, after the stream's work
+// that may use it; the record's host bytes live as long.
+struct AuxLaunch {
+  hipStream_t st;
+  void* launch = nullptr;                     // the launch record on the device
+  unsigned long long* counters = nullptr;     // device: ST_N counters, the queue word, begin()'s `extra` words
+  std::vector<unsigned long long> h;          // ... as finish() read them back
+  float kernel_ms = 0;
+
+  explicit AuxLaunch(void* stream) : st((hipStream_t)stream) {}
+  AuxLaunch(const AuxLaunch&) = delete;
+  ~AuxLaunch()
+  {
+    if (!bufs.empty()) (void)hipStreamSynchronize(st);
+    for (void* b : bufs) (void)hipFree(b);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+
+  // The scene on the device and the record of (scene, P) with zeroed counters of the call's own.
+  // primary_lists: the launch shoots P's camera rays and shares the scene's primary-ray lists; without
+  // them (rays that are not the camera's) the lists are neither read nor rebuilt.
+  int begin(dt_scene* sc, dtd::DParams& P, bool primary_lists, int extra = 0)
+  {
+    if (int rc = scene_upload(sc)) return rc;
+    if (primary_lists) {
+      if (int rc = update_primary_lists(sc, P, true)) return rc;
+    } else {
+      P.pl_block = P.pl_nbx = P.pl_nby = P.pl_bump = 0;
+    }
+    h.assign(ST_N + 1 + extra, 0);
+    void* d = nullptr;
+    if (int rc = alloc(dt_launch_size(), &launch)) return rc;
+    if (int rc = alloc(h.size() * sizeof(h[0]), &d)) return rc;
+    counters = (unsigned long long*)d;
+    HIPCHK(hipMemsetAsync(counters, 0, h.size() * sizeof(h[0]), st));
+    HScene hs;
+    fill_hscene(sc, hs);
+    if (!primary_lists) hs.pl_cells = hs.pl_list = nullptr;
+    hs.stats = counters;
+    hs.queue = hs.stats + ST_N;
+    record.assign(dt_launch_size(), 0);
+    memcpy(record.data() + dt_scene_struct_offset(), &hs, sizeof(hs));
+    memcpy(record.data() + dt_params_struct_offset(), &P, sizeof(P));
+    HIPCHK(hipMemcpyAsync(launch, record.data(), record.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    return DT_OK;
+  }
+
+  // The device side of one of the caller's arrays: p itself when it is null or on the device, else a
+  // temporary of `bytes`, holding p's bytes first (copy_in) and copied back to p by finish() (copy_out).
+  int plane(const void* p, size_t bytes, bool on_device, bool copy_in, bool copy_out, void** dev)
+  {
+    *dev = const_cast<void*>(p);
+    if (!p || on_device) return DT_OK;
+    if (int rc = alloc(bytes, dev)) return rc;
+    if (copy_in) HIPCHK(hipMemcpyAsync(*dev, p, bytes, hipMemcpyHostToDevice, st));
+    if (copy_out) back.push_back({const_cast<void*>(p), *dev, bytes});
+    return DT_OK;
+  }
+
+  int start()
+  {
+    HIPCHK(hipEventRecord(e0, st));
+    return DT_OK;
+  }
+
+  // after the launch: the staged arrays and the counters back, the stream drained, the kernel's time
+  int finish(hipError_t launched)
+  {
+    if (launched != hipSuccess)
+      return fail(DT_E_NO_DEVICE, std::string("auxiliary kernel launch: ") + hipGetErrorString(launched));
+    HIPCHK(hipEventRecord(e1, st));
+    for (const Back& b : back) HIPCHK(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h.data(), counters, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipEventElapsedTime(&kernel_ms, e0, e1));
+    return DT_OK;
+  }
+
+ private:
+  struct Back {
+    void *host, *dev;
+    size_t bytes;
+  };
+  std::vector<void*> bufs;
+  std::vector<Back> back;
+  std::vector<uint8_t> record;   // the launch record's host bytes
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+
+  int alloc(size_t bytes, void** dev)
+  {
+    HIPCHK(hipMalloc(dev, bytes));
+    bufs.push_back(*dev);
+    return DT_OK;
+  }
+};
+
+// the grid of a persistent launch over `work` items or waves: the kernel's resident waves at the most
+// (cached by the caller per kernel), one block at the least
+static int aux_grid(const void* kernel_fn, int& resident, int64_t work)
+{
+  if (!resident) resident = max_resident_waves(kernel_fn, 64);
+  const int grid = (int)(work < resident ? work : resident);
+  return grid > 0 ? grid : 1;
+}
+
+// prepare_render for the whole image on one rank
+static int prepare_whole(const dt_scene* sc, const dt_globals* g, int32_t frame, dtd::DParams& P)
+{
+  std::vector<float> zs;
+  dt_tiles whole;
+  memset(&whole, 0, sizeof(whole));
+  whole.world = 1;
+  return prepare_render(sc, g, frame, &whole, P, zs);
+}
+
+// the pixels a launch over P's items produces: the owned tiles' pixels inside the window (pixel_of's `valid`)
+static uint64_t owned_pixels(const dtd::DParams& P)
+{
+  uint64_t pixels = 0;
+  for (int64_t slot = 0; slot < P.n_owned_tiles; ++slot) {
+    const int64_t t = dtd::tile_of(slot, P.rank, P.world);
+    if (t >= P.n_tiles) continue;
+    const int ty = (int)(t / P.tiles_x), tx = (int)(t - (int64_t)ty * P.tiles_x);
+    const int xa = P.x0 + tx * P.tw, ya = P.y0 + ty * P.th;
+    const int xb = xa + P.tw < P.x1 ? xa + P.tw : P.x1, yb = ya + P.th < P.y1 ? ya + P.th : P.y1;
+    if (xb > xa && yb > ya) pixels += (uint64_t)(xb - xa) * (uint64_t)(yb - ya);
+  }
+  return pixels;
+}
+
 // Intersection micro-benchmark: dt_isect_kernel over rays first_ray .. first_ray+n_rays-1
-// of the globals' camera. Synchronous; its own launch record and counters, so it may run beside
-// renders of the same scene on other streams.
+// of the globals' camera.
 int dt_intersect_primary(const dt_scene* sc_c, const dt_globals* g, int32_t frame, int64_t first_ray, int64_t n_rays,
                          int32_t* hit_shape, float* hit_t, int32_t out_on_device, void* stream, float* kernel_ms)
 {
@@ -1622,74 +1758,24 @@ int dt_intersect_primary(const dt_scene* sc_c, const dt_globals* g, int32_t fram
     if (kernel_ms) *kernel_ms = 0;
     return DT_OK;
   }
-  hipStream_t st = (hipStream_t)stream;
   dtd::DParams P;
-  std::vector<float> zs;
-  dt_tiles whole;
-  memset(&whole, 0, sizeof(whole));
-  whole.world = 1;
-  int rc = prepare_render(sc, g, frame, &whole, P, zs);
-  if (rc) return rc;
-  if ((rc = scene_upload(sc)) || (rc = update_primary_lists(sc, P, true))) return rc;
-  struct Tmp {   // released on every return path, after the stream's work that may use them
-    hipStream_t st = nullptr;
-    void *launch = nullptr, *stats = nullptr, *shape = nullptr, *t = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Tmp()
-    {
-      if (launch) (void)hipStreamSynchronize(st);
-      for (void* b : {launch, stats, shape, t})
-        if (b) (void)hipFree(b);
-      if (e0) (void)hipEventDestroy(e0);
-      if (e1) (void)hipEventDestroy(e1);
-    }
-  } tmp;
-  tmp.st = st;
-  const size_t n_stats = sizeof(unsigned long long) * (ST_N + 1);
-  HIPCHK(hipMalloc(&tmp.launch, dt_launch_size()));
-  HIPCHK(hipMalloc(&tmp.stats, n_stats));
-  HIPCHK(hipMemsetAsync(tmp.stats, 0, n_stats, st));
-  HScene hs;
-  fill_hscene(sc, hs);
-  hs.stats = (unsigned long long*)tmp.stats;
-  hs.queue = hs.stats + ST_N;
-  std::vector<uint8_t> L(dt_launch_size(), 0);
-  memcpy(L.data() + dt_scene_struct_offset(), &hs, sizeof(hs));
-  memcpy(L.data() + dt_params_struct_offset(), &P, sizeof(P));
-  HIPCHK(hipMemcpyAsync(tmp.launch, L.data(), L.size(), hipMemcpyHostToDevice, st));
-  int32_t* dshape = hit_shape;
-  float* dt_ = hit_t;
-  if (!out_on_device) {
-    HIPCHK(hipMalloc(&tmp.shape, (size_t)n_rays * sizeof(int32_t)));
-    HIPCHK(hipMalloc(&tmp.t, (size_t)n_rays * sizeof(float)));
-    dshape = (int32_t*)tmp.shape;
-    dt_ = (float*)tmp.t;
-  }
+  if (int rc = prepare_whole(sc, g, frame, P)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, true)) return rc;
+  void *dshape = nullptr, *dt_ = nullptr;
+  if (int rc = aux.plane(hit_shape, (size_t)n_rays * sizeof(int32_t), out_on_device, false, true, &dshape)) return rc;
+  if (int rc = aux.plane(hit_t, (size_t)n_rays * sizeof(float), out_on_device, false, true, &dt_)) return rc;
   static int resident = 0;
-  if (!resident) resident = max_resident_waves(dt_isect_kernel_ptr(), 64);
-  const int64_t waves = (n_rays + 63) / 64;
-  const int grid = (int)(waves < resident ? waves : resident);
-  HIPCHK(hipEventCreate(&tmp.e0));
-  HIPCHK(hipEventCreate(&tmp.e1));
-  HIPCHK(hipEventRecord(tmp.e0, st));
-  HIPCHK(dt_launch_isect(tmp.launch, first_ray, n_rays, dshape, dt_, grid > 0 ? grid : 1, st));
-  HIPCHK(hipEventRecord(tmp.e1, st));
-  if (!out_on_device) {
-    HIPCHK(hipMemcpyAsync(hit_shape, dshape, (size_t)n_rays * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hit_t, dt_, (size_t)n_rays * sizeof(float), hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));
-  if (kernel_ms) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
-    *kernel_ms = ms;
-  }
+  const int grid = aux_grid(dt_isect_kernel_ptr(), resident, (n_rays + 63) / 64);
+  if (int rc = aux.start()) return rc;
+  if (int rc = aux.finish(dt_launch_isect(aux.launch, first_ray, n_rays, (int32_t*)dshape, (float*)dt_, grid, aux.st)))
+    return rc;
+  if (kernel_ms) *kernel_ms = aux.kernel_ms;
   return DT_OK;
 }
 
 // First-hit feature buffers: dt_features_kernel over the samples 0 .. n_samples-1 of every owned pixel.
-// Synchronous; like dt_intersect_primary its launch record, counters and events are its own and it
-// shares only the scene's primary-ray lists. Every argument check comes before the scene is looked at.
+// It shares only the scene's primary-ray lists. Every argument check comes before the scene is looked at.
 // Specular-path feature buffers (dt_render_features_path, `path`): the same call with
 // dt_features_path_kernel, max_bounces and one more plane; its errors carry its own prefix.
 static int render_features_common(bool path, const dt_scene* sc_c, const dt_globals* g, int32_t frame,
@@ -1708,96 +1794,41 @@ static int render_features_common(bool path, const dt_scene* sc_c, const dt_glob
     return fail(DT_E_INVALID, who + "max_bounces must be in 0.." + std::to_string(DT_GUIDE_MAX_BOUNCES) + ", got " +
                                   std::to_string(max_bounces));
   if (sc->no_cull) return fail(DT_E_UNSUPPORTED, who + "scenes with a RectPrismWithCylinder");
-  hipStream_t st = (hipStream_t)stream;
   dtd::DParams P;
   std::vector<float> zs;
-  int rc = prepare_render(sc, g, frame, tiles, P, zs);
-  if (rc) return rc;
-  if ((rc = scene_upload(sc)) || (rc = update_primary_lists(sc, P, true))) return rc;
-  // the planes' lengths (dt_accum_doubles) and the pixels the launch produces: the owned tiles' pixels
-  // inside the window (pixel_of's `valid`)
-  const int64_t n3 = P.layout == DT_OUT_SLAB ? P.n_owned_tiles * P.tw * P.th * 3 : (int64_t)3 * P.xRes * P.yRes;
-  const int64_t n1 = n3 / 3;
-  uint64_t pixels = 0;
-  for (int64_t slot = 0; slot < P.n_owned_tiles; ++slot) {
-    const int64_t t = dtd::tile_of(slot, P.rank, P.world);
-    if (t >= P.n_tiles) continue;
-    const int ty = (int)(t / P.tiles_x), tx = (int)(t - (int64_t)ty * P.tiles_x);
-    const int xa = P.x0 + tx * P.tw, ya = P.y0 + ty * P.th;
-    const int xb = xa + P.tw < P.x1 ? xa + P.tw : P.x1, yb = ya + P.th < P.y1 ? ya + P.th : P.y1;
-    if (xb > xa && yb > ya) pixels += (uint64_t)(xb - xa) * (uint64_t)(yb - ya);
-  }
-  struct Tmp {   // released on every return path, after the stream's work that may use them
-    hipStream_t st = nullptr;
-    void *launch = nullptr, *stats = nullptr, *plane[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Tmp()
-    {
-      if (launch) (void)hipStreamSynchronize(st);
-      for (void* b : {launch, stats, plane[0], plane[1], plane[2], plane[3], plane[4], plane[5]})
-        if (b) (void)hipFree(b);
-      if (e0) (void)hipEventDestroy(e0);
-      if (e1) (void)hipEventDestroy(e1);
-    }
-  } tmp;
-  tmp.st = st;
-  const size_t n_stats = sizeof(unsigned long long) * (ST_N + 1);
-  HIPCHK(hipMalloc(&tmp.launch, dt_launch_size()));
-  HIPCHK(hipMalloc(&tmp.stats, n_stats));
-  HIPCHK(hipMemsetAsync(tmp.stats, 0, n_stats, st));
-  HScene hs;
-  fill_hscene(sc, hs);
-  hs.stats = (unsigned long long*)tmp.stats;
-  hs.queue = hs.stats + ST_N;
-  std::vector<uint8_t> L(dt_launch_size(), 0);
-  memcpy(L.data() + dt_scene_struct_offset(), &hs, sizeof(hs));
-  memcpy(L.data() + dt_params_struct_offset(), &P, sizeof(P));
-  HIPCHK(hipMemcpyAsync(tmp.launch, L.data(), L.size(), hipMemcpyHostToDevice, st));
-  // host planes are staged through device copies of the caller's arrays: the entries of pixels this
-  // rank does not own go back as they came
+  if (int rc = prepare_render(sc, g, frame, tiles, P, zs)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, true)) return rc;
+  // the planes' lengths (dt_accum_doubles). Host planes are staged through device copies of the caller's
+  // arrays: the entries of pixels this rank does not own go back as they came
+  const size_t n3 = P.layout == DT_OUT_SLAB ? (size_t)(P.n_owned_tiles * P.tw * P.th * 3) : (size_t)3 * P.xRes * P.yRes;
+  const size_t n1 = n3 / 3;
   void* host[6] = {out->albedo, out->normal, out->depth, out->coverage, out->shape, bounces};
-  void* dev[6] = {out->albedo, out->normal, out->depth, out->coverage, out->shape, bounces};
-  const size_t bytes[6] = {(size_t)n3 * sizeof(float), (size_t)n3 * sizeof(float), (size_t)n1 * sizeof(float),
-                           (size_t)n1 * sizeof(float), (size_t)n1 * sizeof(int32_t), (size_t)n1 * sizeof(float)};
-  if (!out_on_device)
-    for (int k = 0; k < 6; ++k)
-      if (host[k]) {
-        HIPCHK(hipMalloc(&tmp.plane[k], bytes[k]));
-        HIPCHK(hipMemcpyAsync(tmp.plane[k], host[k], bytes[k], hipMemcpyHostToDevice, st));
-        dev[k] = tmp.plane[k];
-      }
+  void* dev[6];
+  const size_t bytes[6] = {n3 * sizeof(float), n3 * sizeof(float), n1 * sizeof(float),
+                           n1 * sizeof(float), n1 * sizeof(int32_t), n1 * sizeof(float)};
+  for (int k = 0; k < 6; ++k)
+    if (int rc = aux.plane(host[k], bytes[k], out_on_device, true, true, &dev[k])) return rc;
   static int resident_first = 0, resident_path = 0;
-  int& resident = path ? resident_path : resident_first;
-  if (!resident) resident = max_resident_waves(path ? dt_features_path_kernel_ptr() : dt_features_kernel_ptr(), 64);
-  const int grid = (int)(P.n_items < resident ? P.n_items : resident);
-  HIPCHK(hipEventCreate(&tmp.e0));
-  HIPCHK(hipEventCreate(&tmp.e1));
-  HIPCHK(hipEventRecord(tmp.e0, st));
-  if (path)
-    HIPCHK(dt_launch_features_path(tmp.launch, n_samples, max_bounces, (float*)dev[0], (float*)dev[1], (float*)dev[2],
-                                   (float*)dev[3], (int32_t*)dev[4], (float*)dev[5], grid > 0 ? grid : 1, st));
-  else
-    HIPCHK(dt_launch_features(tmp.launch, n_samples, (float*)dev[0], (float*)dev[1], (float*)dev[2], (float*)dev[3],
-                              (int32_t*)dev[4], grid > 0 ? grid : 1, st));
-  HIPCHK(hipEventRecord(tmp.e1, st));
-  if (!out_on_device)
-    for (int k = 0; k < 6; ++k)
-      if (host[k]) HIPCHK(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, st));
-  unsigned long long h[ST_N + 1];
-  HIPCHK(hipMemcpyAsync(h, tmp.stats, n_stats, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  const int grid = path ? aux_grid(dt_features_path_kernel_ptr(), resident_path, P.n_items)
+                        : aux_grid(dt_features_kernel_ptr(), resident_first, P.n_items);
+  if (int rc = aux.start()) return rc;
+  const hipError_t launched =
+      path ? dt_launch_features_path(aux.launch, n_samples, max_bounces, (float*)dev[0], (float*)dev[1], (float*)dev[2],
+                                     (float*)dev[3], (int32_t*)dev[4], (float*)dev[5], grid, aux.st)
+           : dt_launch_features(aux.launch, n_samples, (float*)dev[0], (float*)dev[1], (float*)dev[2], (float*)dev[3],
+                                (int32_t*)dev[4], grid, aux.st);
+  if (int rc = aux.finish(launched)) return rc;
   if (stats) {
     memset(stats, 0, sizeof(*stats));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
-    stats->pixels = pixels;
-    stats->samples = pixels * (uint64_t)n_samples;
-    stats->rays = path ? h[ST_RAYS] : stats->samples;   // path: the segments traced
-    if (path) stats->reflect_errors = h[ST_REFL];
-    stats->tex_fetches = h[ST_TEX];
-    stats->uv_out_of_range = h[ST_UV];
-    stats->prism_norm_fallback = h[ST_PRISM];
-    stats->kernel_ms = ms;
+    stats->pixels = owned_pixels(P);
+    stats->samples = stats->pixels * (uint64_t)n_samples;
+    stats->rays = path ? aux.h[ST_RAYS] : stats->samples;   // path: the segments traced
+    if (path) stats->reflect_errors = aux.h[ST_REFL];
+    stats->tex_fetches = aux.h[ST_TEX];
+    stats->uv_out_of_range = aux.h[ST_UV];
+    stats->prism_norm_fallback = aux.h[ST_PRISM];
+    stats->kernel_ms = aux.kernel_ms;
   }
   return DT_OK;
 }
@@ -1832,9 +1863,9 @@ int dt_guide_bounce(const dt_globals* g, int32_t material, uint32_t flags, int32
   return rc;
 }
 
-// Object mattes: dt_mattes_kernel over the samples 0 .. n_samples-1 of every owned pixel. Synchronous; as
-// dt_render_features its launch record, counters and events are its own and it shares only the scene's
-// primary-ray lists. Every argument check, the map's entries included, comes before any device work.
+// Object mattes: dt_mattes_kernel over the samples 0 .. n_samples-1 of every owned pixel. As
+// dt_render_features it shares only the scene's primary-ray lists. Every argument check, the map's
+// entries included, comes before any device work.
 int dt_render_mattes(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t n_samples,
                      const int32_t* group_of_shape, int32_t n_shapes, int32_t layers, const dt_mattes* out,
                      int32_t out_on_device, void* stream, dt_stats* stats, uint64_t* overflow_pixels)
@@ -1859,164 +1890,42 @@ int dt_render_mattes(const dt_scene* sc_c, const dt_globals* g, int32_t frame, c
     return fail(DT_E_INVALID, "dt_render_mattes: n_shapes " + std::to_string(n_shapes) + ", the scene has " +
                                   std::to_string(sc->flat.hdr.size()) + " shapes");
   if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_render_mattes: scenes with a RectPrismWithCylinder");
-  hipStream_t st = (hipStream_t)stream;
   dtd::DParams P;
   std::vector<float> zs;
-  int rc = prepare_render(sc, g, frame, tiles, P, zs);
-  if (rc) return rc;
-  if ((rc = scene_upload(sc)) || (rc = update_primary_lists(sc, P, true))) return rc;
-  // the planes' lengths and the pixels the launch produces, as dt_render_features counts them
-  const int64_t n1 = P.layout == DT_OUT_SLAB ? P.n_owned_tiles * P.tw * P.th : (int64_t)P.xRes * P.yRes;
-  uint64_t pixels = 0;
-  for (int64_t slot = 0; slot < P.n_owned_tiles; ++slot) {
-    const int64_t t = dtd::tile_of(slot, P.rank, P.world);
-    if (t >= P.n_tiles) continue;
-    const int ty = (int)(t / P.tiles_x), tx = (int)(t - (int64_t)ty * P.tiles_x);
-    const int xa = P.x0 + tx * P.tw, ya = P.y0 + ty * P.th;
-    const int xb = xa + P.tw < P.x1 ? xa + P.tw : P.x1, yb = ya + P.th < P.y1 ? ya + P.th : P.y1;
-    if (xb > xa && yb > ya) pixels += (uint64_t)(xb - xa) * (uint64_t)(yb - ya);
-  }
-  struct Tmp {   // released on every return path, after the stream's work that may use them
-    hipStream_t st = nullptr;
-    void *launch = nullptr, *stats = nullptr, *map = nullptr, *plane[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Tmp()
-    {
-      if (launch) (void)hipStreamSynchronize(st);
-      for (void* b : {launch, stats, map, plane[0], plane[1], plane[2]})
-        if (b) (void)hipFree(b);
-      if (e0) (void)hipEventDestroy(e0);
-      if (e1) (void)hipEventDestroy(e1);
-    }
-  } tmp;
-  tmp.st = st;
-  // the counters, and after them the overflow count
-  const size_t n_stats = sizeof(unsigned long long) * (ST_N + 2);
-  HIPCHK(hipMalloc(&tmp.launch, dt_launch_size()));
-  HIPCHK(hipMalloc(&tmp.stats, n_stats));
-  HIPCHK(hipMemsetAsync(tmp.stats, 0, n_stats, st));
-  HScene hs;
-  fill_hscene(sc, hs);
-  hs.stats = (unsigned long long*)tmp.stats;
-  hs.queue = hs.stats + ST_N;
-  std::vector<uint8_t> L(dt_launch_size(), 0);
-  memcpy(L.data() + dt_scene_struct_offset(), &hs, sizeof(hs));
-  memcpy(L.data() + dt_params_struct_offset(), &P, sizeof(P));
-  HIPCHK(hipMemcpyAsync(tmp.launch, L.data(), L.size(), hipMemcpyHostToDevice, st));
-  if (group_of_shape && n_shapes > 0) {
-    HIPCHK(hipMalloc(&tmp.map, (size_t)n_shapes * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(tmp.map, group_of_shape, (size_t)n_shapes * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  }
-  // host planes are staged through device copies of the caller's arrays: the entries of pixels this
-  // rank does not own go back as they came
+  if (int rc = prepare_render(sc, g, frame, tiles, P, zs)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, true, /*extra: the overflow count*/ 1)) return rc;
+  void* map = nullptr;
+  if (n_shapes > 0)
+    if (int rc = aux.plane(group_of_shape, (size_t)n_shapes * sizeof(int32_t), false, true, false, &map)) return rc;
+  // the planes, staged as dt_render_features stages its own
+  const size_t n1 = P.layout == DT_OUT_SLAB ? (size_t)(P.n_owned_tiles * P.tw * P.th) : (size_t)P.xRes * P.yRes;
   void* host[3] = {out->id, out->weight, out->distinct};
-  void* dev[3] = {out->id, out->weight, out->distinct};
-  const size_t bytes[3] = {(size_t)n1 * layers * sizeof(int32_t), (size_t)n1 * layers * sizeof(float),
-                           (size_t)n1 * sizeof(int32_t)};
-  if (!out_on_device)
-    for (int k = 0; k < 3; ++k)
-      if (host[k]) {
-        HIPCHK(hipMalloc(&tmp.plane[k], bytes[k]));
-        HIPCHK(hipMemcpyAsync(tmp.plane[k], host[k], bytes[k], hipMemcpyHostToDevice, st));
-        dev[k] = tmp.plane[k];
-      }
+  void* dev[3];
+  const size_t bytes[3] = {n1 * layers * sizeof(int32_t), n1 * layers * sizeof(float), n1 * sizeof(int32_t)};
+  for (int k = 0; k < 3; ++k)
+    if (int rc = aux.plane(host[k], bytes[k], out_on_device, true, true, &dev[k])) return rc;
   static int resident = 0;
-  if (!resident) resident = max_resident_waves(dt_mattes_kernel_ptr(), 64);
-  const int grid = (int)(P.n_items < resident ? P.n_items : resident);
-  HIPCHK(hipEventCreate(&tmp.e0));
-  HIPCHK(hipEventCreate(&tmp.e1));
-  HIPCHK(hipEventRecord(tmp.e0, st));
-  HIPCHK(dt_launch_mattes(tmp.launch, n_samples, (const int32_t*)tmp.map, layers, (int32_t*)dev[0], (float*)dev[1],
-                          (int32_t*)dev[2], (unsigned long long*)tmp.stats + ST_N + 1, grid > 0 ? grid : 1, st));
-  HIPCHK(hipEventRecord(tmp.e1, st));
-  if (!out_on_device)
-    for (int k = 0; k < 3; ++k)
-      if (host[k]) HIPCHK(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, st));
-  unsigned long long h[ST_N + 2];
-  HIPCHK(hipMemcpyAsync(h, tmp.stats, n_stats, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (overflow_pixels) *overflow_pixels = h[ST_N + 1];
+  const int grid = aux_grid(dt_mattes_kernel_ptr(), resident, P.n_items);
+  if (int rc = aux.start()) return rc;
+  if (int rc = aux.finish(dt_launch_mattes(aux.launch, n_samples, (const int32_t*)map, layers, (int32_t*)dev[0],
+                                           (float*)dev[1], (int32_t*)dev[2], aux.counters + ST_N + 1, grid, aux.st)))
+    return rc;
+  if (overflow_pixels) *overflow_pixels = aux.h[ST_N + 1];
   if (stats) {
     memset(stats, 0, sizeof(*stats));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
-    stats->pixels = pixels;
-    stats->samples = pixels * (uint64_t)n_samples;
+    stats->pixels = owned_pixels(P);
+    stats->samples = stats->pixels * (uint64_t)n_samples;
     stats->rays = stats->samples;
-    stats->kernel_ms = ms;
+    stats->kernel_ms = aux.kernel_ms;
   }
   return DT_OK;
 }
 
 // Ray queries (dt_trace_rays, dt_rays_occluded): dt_rayq_kernel / dt_rayq_occl_kernel over rays the caller
-// hands over. Synchronous. A query has a launch record, counters and events of its own and takes only
-// the traversal parameters from g (prepare_render; the camera it fills in is not read): it neither
-// reads nor rebuilds the scene's primary-ray lists, and a render afterwards finds the scene as it was.
-struct RayqTmp {   // released on every return path, after the stream's work that may use them
-  hipStream_t st = nullptr;
-  void *launch = nullptr, *stats = nullptr;
-  std::vector<void*> bufs;
-  std::vector<uint8_t> record;   // the launch record's host bytes
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~RayqTmp()
-  {
-    if (launch) (void)hipStreamSynchronize(st);
-    for (void* b : bufs)
-      if (b) (void)hipFree(b);
-    if (launch) (void)hipFree(launch);
-    if (stats) (void)hipFree(stats);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-  // a device buffer of `bytes`, holding host's bytes when host is given
-  int stage(const void* host, size_t bytes, void** dev)
-  {
-    HIPCHK(hipMalloc(dev, bytes));
-    bufs.push_back(*dev);
-    if (host) HIPCHK(hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, st));
-    return DT_OK;
-  }
-};
-
-// the query's launch record and zeroed counters on the device, and its two events
-static int rayq_begin(dt_scene* sc, const dt_globals* g, RayqTmp& tmp)
-{
-  dtd::DParams P;
-  std::vector<float> zs;
-  dt_tiles whole;
-  memset(&whole, 0, sizeof(whole));
-  whole.world = 1;
-  int rc = prepare_render(sc, g, 0, &whole, P, zs);
-  if (rc) return rc;
-  if ((rc = scene_upload(sc))) return rc;
-  P.pl_block = P.pl_nbx = P.pl_nby = P.pl_bump = 0;   // no primary lists: the rays are not the camera's
-  const size_t n_stats = sizeof(unsigned long long) * (ST_N + 1);
-  HIPCHK(hipMalloc(&tmp.launch, dt_launch_size()));
-  HIPCHK(hipMalloc(&tmp.stats, n_stats));
-  HIPCHK(hipMemsetAsync(tmp.stats, 0, n_stats, tmp.st));
-  HScene hs;
-  fill_hscene(sc, hs);
-  hs.pl_cells = hs.pl_list = nullptr;
-  hs.stats = (unsigned long long*)tmp.stats;
-  hs.queue = hs.stats + ST_N;
-  std::vector<uint8_t>& L = tmp.record;   // (lives until the stream has drained)
-  L.assign(dt_launch_size(), 0);
-  memcpy(L.data() + dt_scene_struct_offset(), &hs, sizeof(hs));
-  memcpy(L.data() + dt_params_struct_offset(), &P, sizeof(P));
-  HIPCHK(hipMemcpyAsync(tmp.launch, L.data(), L.size(), hipMemcpyHostToDevice, tmp.st));
-  HIPCHK(hipEventCreate(&tmp.e0));
-  HIPCHK(hipEventCreate(&tmp.e1));
-  return DT_OK;
-}
-
-static int rayq_grid(const void* kernel_fn, int64_t n_rays, int& resident)
-{
-  if (!resident) resident = max_resident_waves(kernel_fn, 64);
-  const int64_t waves = (n_rays + 63) / 64;
-  const int grid = (int)(waves < resident ? waves : resident);
-  return grid > 0 ? grid : 1;
-}
-
+// hands over. A query takes only the traversal parameters from g (prepare_render; the camera it fills in
+// is not read): it neither reads nor rebuilds the scene's primary-ray lists, and a render afterwards
+// finds the scene as it was.
 int dt_trace_rays(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
                   const dt_ray_hits* out, int32_t on_device, void* stream, dt_stats* stats)
 {
@@ -2032,45 +1941,32 @@ int dt_trace_rays(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, con
   if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_trace_rays: scenes with a RectPrismWithCylinder");
   if (stats) memset(stats, 0, sizeof(*stats));
   if (n_rays == 0) return DT_OK;
-  RayqTmp tmp;
-  tmp.st = (hipStream_t)stream;
-  if (int rc = rayq_begin(sc, g, tmp)) return rc;
+  dtd::DParams P;
+  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, false)) return rc;
   const size_t n = (size_t)n_rays;
-  const void *dstart = start, *ddir = dir;
+  void *dstart = nullptr, *ddir = nullptr;
+  if (int rc = aux.plane(start, 3 * n * sizeof(double), on_device, true, false, &dstart)) return rc;
+  if (int rc = aux.plane(dir, 3 * n * sizeof(double), on_device, true, false, &ddir)) return rc;
   void* host[5] = {out->shape, out->t, out->point, out->normal, out->albedo};
-  void* dev[5] = {out->shape, out->t, out->point, out->normal, out->albedo};
+  void* dev[5];
   const size_t bytes[5] = {n * sizeof(int32_t), n * sizeof(float), 3 * n * sizeof(double), 3 * n * sizeof(double),
                            3 * n * sizeof(double)};
-  if (!on_device) {
-    void* d = nullptr;
-    if (int rc = tmp.stage(start, 3 * n * sizeof(double), &d)) return rc;
-    dstart = d;
-    if (int rc = tmp.stage(dir, 3 * n * sizeof(double), &d)) return rc;
-    ddir = d;
-    for (int k = 0; k < 5; ++k)
-      if (host[k])
-        if (int rc = tmp.stage(nullptr, bytes[k], &dev[k])) return rc;
-  }
+  for (int k = 0; k < 5; ++k)
+    if (int rc = aux.plane(host[k], bytes[k], on_device, false, true, &dev[k])) return rc;
   static int resident = 0;
-  const int grid = rayq_grid(dt_rayq_kernel_ptr(), n_rays, resident);
-  HIPCHK(hipEventRecord(tmp.e0, tmp.st));
-  HIPCHK(dt_launch_rayq(tmp.launch, n_rays, (const double*)dstart, (const double*)ddir, (int32_t*)dev[0], (float*)dev[1],
-                        (double*)dev[2], (double*)dev[3], (double*)dev[4], grid, tmp.st));
-  HIPCHK(hipEventRecord(tmp.e1, tmp.st));
-  if (!on_device)
-    for (int k = 0; k < 5; ++k)
-      if (host[k]) HIPCHK(hipMemcpyAsync(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost, tmp.st));
-  unsigned long long h[ST_N + 1];
-  HIPCHK(hipMemcpyAsync(h, tmp.stats, sizeof(h), hipMemcpyDeviceToHost, tmp.st));
-  HIPCHK(hipStreamSynchronize(tmp.st));
+  const int grid = aux_grid(dt_rayq_kernel_ptr(), resident, (n_rays + 63) / 64);
+  if (int rc = aux.start()) return rc;
+  if (int rc = aux.finish(dt_launch_rayq(aux.launch, n_rays, (const double*)dstart, (const double*)ddir, (int32_t*)dev[0],
+                                         (float*)dev[1], (double*)dev[2], (double*)dev[3], (double*)dev[4], grid, aux.st)))
+    return rc;
   if (stats) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
-    stats->rays = h[ST_RAYS];
-    stats->tex_fetches = h[ST_TEX];
-    stats->uv_out_of_range = h[ST_UV];
-    stats->prism_norm_fallback = h[ST_PRISM];
-    stats->kernel_ms = ms;
+    stats->rays = aux.h[ST_RAYS];
+    stats->tex_fetches = aux.h[ST_TEX];
+    stats->uv_out_of_range = aux.h[ST_UV];
+    stats->prism_norm_fallback = aux.h[ST_PRISM];
+    stats->kernel_ms = aux.kernel_ms;
   }
   return DT_OK;
 }
@@ -2088,39 +1984,25 @@ int dt_rays_occluded(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, 
   if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_rays_occluded: scenes with a RectPrismWithCylinder");
   if (stats) memset(stats, 0, sizeof(*stats));
   if (n_rays == 0) return DT_OK;
-  RayqTmp tmp;
-  tmp.st = (hipStream_t)stream;
-  if (int rc = rayq_begin(sc, g, tmp)) return rc;
+  dtd::DParams P;
+  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, false)) return rc;
   const size_t n = (size_t)n_rays;
-  const void *dstart = start, *ddir = dir, *dskip = skip_shape;
-  void* docc = occluded;
-  if (!on_device) {
-    void* d = nullptr;
-    if (int rc = tmp.stage(start, 3 * n * sizeof(double), &d)) return rc;
-    dstart = d;
-    if (int rc = tmp.stage(dir, 3 * n * sizeof(double), &d)) return rc;
-    ddir = d;
-    if (skip_shape) {
-      if (int rc = tmp.stage(skip_shape, n * sizeof(int32_t), &d)) return rc;
-      dskip = d;
-    }
-    if (int rc = tmp.stage(nullptr, n, &docc)) return rc;
-  }
+  void *dstart = nullptr, *ddir = nullptr, *dskip = nullptr, *docc = nullptr;
+  if (int rc = aux.plane(start, 3 * n * sizeof(double), on_device, true, false, &dstart)) return rc;
+  if (int rc = aux.plane(dir, 3 * n * sizeof(double), on_device, true, false, &ddir)) return rc;
+  if (int rc = aux.plane(skip_shape, n * sizeof(int32_t), on_device, true, false, &dskip)) return rc;
+  if (int rc = aux.plane(occluded, n, on_device, false, true, &docc)) return rc;
   static int resident = 0;
-  const int grid = rayq_grid(dt_rayq_occl_kernel_ptr(), n_rays, resident);
-  HIPCHK(hipEventRecord(tmp.e0, tmp.st));
-  HIPCHK(dt_launch_rayq_occl(tmp.launch, n_rays, (const double*)dstart, (const double*)ddir, (const int32_t*)dskip,
-                             (uint8_t*)docc, grid, tmp.st));
-  HIPCHK(hipEventRecord(tmp.e1, tmp.st));
-  if (!on_device) HIPCHK(hipMemcpyAsync(occluded, docc, n, hipMemcpyDeviceToHost, tmp.st));
-  unsigned long long h[ST_N + 1];
-  HIPCHK(hipMemcpyAsync(h, tmp.stats, sizeof(h), hipMemcpyDeviceToHost, tmp.st));
-  HIPCHK(hipStreamSynchronize(tmp.st));
+  const int grid = aux_grid(dt_rayq_occl_kernel_ptr(), resident, (n_rays + 63) / 64);
+  if (int rc = aux.start()) return rc;
+  if (int rc = aux.finish(dt_launch_rayq_occl(aux.launch, n_rays, (const double*)dstart, (const double*)ddir,
+                                              (const int32_t*)dskip, (uint8_t*)docc, grid, aux.st)))
+    return rc;
   if (stats) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, tmp.e0, tmp.e1));
-    stats->shadow_rays = h[ST_SHADOW];
-    stats->kernel_ms = ms;
+    stats->shadow_rays = aux.h[ST_SHADOW];
+    stats->kernel_ms = aux.kernel_ms;
   }
   return DT_OK;
 }
