@@ -2280,8 +2280,11 @@ struct Entry {
   float k;
   int depth;   // >0 NODE ; -1 FINISH
   uint32_t key;
-  int _pad;
+#if DT_DONATE
+  int _pad;    // the node's pre-order path (work sharing only; elsewhere the word is tail padding, never written)
+#endif
 };
+static_assert(sizeof(Entry) == 64, "Entry: one 64-byte stack slot");
 
 struct PassOut {
   V3 color;
@@ -2559,9 +2562,6 @@ __device__ __forceinline__ void dn_put(const DnCtx& dn, int& pos, double x, doub
   r.aux = aux;
   ++pos;
 }
-#define DT_ROOT_PAD 0
-#else
-#define DT_ROOT_PAD 1
 #endif
 
 // One full rayColor tree for the lanes with `active`. Appends to out.color in the
@@ -2605,15 +2605,22 @@ __device__ __forceinline__ void run_pass(const Ctx& c_in, bool active, V3 ray0, 
   const DParams& P = *c.P;
   int sp = 0;
   int prio_steps = 0;
+  // The root node is never a stack entry. Every lane's root is the node of the first DFS step and of
+  // no later one, so that step is the root step for the whole wave (root_step, wave-uniform). Of the
+  // root's fields only the ray and the origin differ per lane: they wait in nrec rows 0-5, which are
+  // free from here until the root step's light loop parks normal and e_dir in them. By then the ray
+  // and the origin have been read for the last time (isectP, in and e_dir are formed from the copies
+  // read after the closest-hit walk), and nothing below the parking reads the rows as a root again.
+  // k, depth and key are constants of the pass. sp takes the values it took when the root was pushed
+  // to slot 0 and popped at once: the root's FINISH slot is slot 0, its children start at slot 1.
+  // (red, dens and the sky march use this LDS only after run_pass has returned.)
+  const int rl_ = threadIdx.x & (DT_WAVE - 1);
   if (active && P.max_depth > 0) {
-    Entry e;
-    e.a = ray0; e.b = org0; e.k = 1.0f; e.depth = P.max_depth; e.key = rootkey; e._pad = DT_ROOT_PAD;  // root
-    stack[sp++] = e;
-#if DT_DONATE
-    npend = 1;
-#endif
+    nrec[0][rl_] = ray0.x; nrec[1][rl_] = ray0.y; nrec[2][rl_] = ray0.z;
+    nrec[3][rl_] = org0.x; nrec[4][rl_] = org0.y; nrec[5][rl_] = org0.z;
   }
-  while (true) {
+  bool root_step = true;
+  for (;; root_step = false) {
     DT_T(t0);
 #if DT_DONATE
     // ---- work sharing: a free lane (own sample finished, no list open) takes the bottom-most
@@ -2677,7 +2684,8 @@ __device__ __forceinline__ void run_pass(const Ctx& c_in, bool active, V3 ray0, 
 #if DT_DONATE
     bool waiting = false;   // a donated subtree's list is not complete yet
 #endif
-    int pidx = 0;   // the popped NODE entry's slot
+    int pidx = 0;   // the popped NODE entry's slot (unused in the root step)
+    if (root_step) have = active && P.max_depth > 0;   // sp == 0: the pop loop below does not run
 #if DT_DONATE
     while (sp > 0) {
       const int d = stack[--sp].depth;
@@ -2772,13 +2780,21 @@ __device__ __forceinline__ void run_pass(const Ctx& c_in, bool active, V3 ray0, 
     // they are used, behind compiler barriers, instead of being held in registers across the walks:
     // the allocator spilled them to scratch right after the pop, a store of data already there.
     // (re-reading node key and k inside the light loops as well measured C3 -2.7%, profiles/r03f)
+    // The root step reads the ray and the origin from their LDS rows in the same two places (a
+    // uniform branch on root_step) and takes the other fields from the pass constants.
 #define DT_EF(f) (stack[pidx].f)
-    V3 ray = DT_EF(a), eye = DT_EF(b);
-    const bool is_root = have && DT_EF(_pad) == DT_ROOT_PAD;
+#define DT_ROOT_RAY v3(nrec[0][rl_], nrec[1][rl_], nrec[2][rl_])
+#define DT_ROOT_ORG v3(nrec[3][rl_], nrec[4][rl_], nrec[5][rl_])
+    V3 ray, eye;
+    if (root_step) { ray = DT_ROOT_RAY; eye = DT_ROOT_ORG; }
+    else { ray = DT_EF(a); eye = DT_EF(b); }
+    const bool is_root = root_step;   // wave-uniform
 #if DT_DONATE
+    // the node's pre-order path (the root's is 0)
+#define DT_EPATH (root_step ? 0 : DT_EF(_pad))
     // in_motion of the node with the largest pre-order path so far (own sample / current list)
     if (have) {
-      const int path = DT_EF(_pad);
+      const int path = DT_EPATH;
       if (out_pos < 0) { if (path >= mk_o) { mk_o = path; mo_o = false; } }
       else if (path >= mk_t) { mk_t = path; mo_t = false; }
     }
@@ -2796,7 +2812,7 @@ __device__ __forceinline__ void run_pass(const Ctx& c_in, bool active, V3 ray0, 
     // primary rays: the pixel block's candidate list, when the wave's pixels share one block
     // (host_primlists.cpp; blur passes take the bump tree's lists when they were built)
     int pblock = -1;
-    if (P.pl_block > 0 && __ballot(is_root) && (P.pl_bump || !__ballot(have && shift != 0.0f)) && P.n_fnodes > 0 &&
+    if (P.pl_block > 0 && is_root && (P.pl_bump || !__ballot(have && shift != 0.0f)) && P.n_fnodes > 0 &&
         (P.ftree_mode & 1)) {
       const int px = (int)(c.rng.pixel % (uint32_t)P.xRes), py = (int)(c.rng.pixel / (uint32_t)P.xRes);
       const int blk = (py / P.pl_block) * P.pl_nbx + px / P.pl_block;
@@ -2805,13 +2821,24 @@ __device__ __forceinline__ void run_pass(const Ctx& c_in, bool active, V3 ray0, 
     }
     bool any = closest_hit(S, P, have, ray, eye, shift, h, cnt, pblock);
     asm volatile("" ::: "memory");   // the entry's fields: fresh loads, not values kept across the walk
-    ray = DT_EF(a);
-    eye = DT_EF(b);
-    const int depth = DT_EF(depth);
-    const float k = DT_EF(k);
-    const uint32_t node = DT_EF(key);
+    int depth;
+    float k;
+    uint32_t node;
+    if (root_step) {
+      ray = DT_ROOT_RAY;
+      eye = DT_ROOT_ORG;
+      depth = P.max_depth;
+      k = 1.0f;
+      node = rootkey;
+    } else {
+      ray = DT_EF(a);
+      eye = DT_EF(b);
+      depth = DT_EF(depth);
+      k = DT_EF(k);
+      node = DT_EF(key);
+    }
 #ifdef DT_STAMPS
-    if (__ballot(is_root)) { cnt.ph[46] += cnt.ph[26] - v_before; cnt.ph[39] += 1; }
+    if (is_root) { cnt.ph[46] += cnt.ph[26] - v_before; cnt.ph[39] += 1; }
 #endif
     DT_T(t2);
     DT_ACC(1, t1, t2);
@@ -2838,7 +2865,7 @@ __device__ __forceinline__ void run_pass(const Ctx& c_in, bool active, V3 ray0, 
 #if DT_DONATE
       {
         const bool mv = (M.flags & DT_F_MOTION) != 0;
-        const int path = DT_EF(_pad);
+        const int path = DT_EPATH;
         if (out_pos < 0) { if (path == mk_o) mo_o = mv; }
         else if (path == mk_t) mo_t = mv;
       }
@@ -2865,12 +2892,12 @@ __device__ __forceinline__ void run_pass(const Ctx& c_in, bool active, V3 ray0, 
 #if DT_DONATE
           // pre-order path of a child: the parent's, plus its call slot + 1 at the child's level (3 bits
           // per level from bit 27 down; host: max_depth <= 11, brdf_samples <= 6)
-          const int cpath_base = DT_EF(_pad);
+          const int cpath_base = DT_EPATH;
           const int cpath_shift = 30 - 3 * (P.max_depth - depth + 1);
-#define DT_CPATH(d) (cpath_base | ((d) << cpath_shift))
+#define DT_CPATH(ch, d) ((ch)._pad = cpath_base | ((d) << cpath_shift))
 #define DT_NPEND(cond) (npend += (cond) ? 1 : 0)
 #else
-#define DT_CPATH(d) 0
+#define DT_CPATH(ch, d) ((void)0)
 #define DT_NPEND(cond) ((void)0)
 #endif
           V3 refl_ray = sub(in, mul(2 * dot(normal, in), normal));
@@ -2906,7 +2933,7 @@ __device__ __forceinline__ void run_pass(const Ctx& c_in, bool active, V3 ray0, 
                 k_refl = (float)(0.5 * (pw2((double)rp) + pw2((double)rs)));
                 k_refr = 1 - k_refl;
                 Entry ch; ch.a = outr; ch.b = adj_org; ch.k = k_refr * k; ch.depth = depth - 1;
-                ch.key = child_key(node, 0); ch._pad = DT_CPATH(1);
+                ch.key = child_key(node, 0); DT_CPATH(ch, 1);
                 stack[sp++] = ch;
                 DT_NPEND(1);
               }
@@ -2957,14 +2984,14 @@ __device__ __forceinline__ void run_pass(const Ctx& c_in, bool active, V3 ray0, 
                 if (exhausted) atomicAdd(cnt.wc + WC_GLOSSY, 1u);
                 Entry ch; ch.a = sample_refl; ch.b = add(isectP, mul(eps, sample_refl));
                 ch.k = kg; ch.depth = exhausted ? 0 : depth - 1; ch.key = child_key(node, 2 + i);
-                ch._pad = DT_CPATH(2 + i);
+                DT_CPATH(ch, 2 + i);
                 stack[base + nref - 1 - i] = ch;
                 DT_NPEND(!exhausted);
               }
             } else if (nref > 0) {
               DT_WK(DT_WK_MIRROR, true);
               Entry ch; ch.a = refl_ray; ch.b = add(isectP, mul(eps, refl_ray)); ch.k = k_refl * k;
-              ch.depth = depth - 1; ch.key = child_key(node, 1); ch._pad = DT_CPATH(2);
+              ch.depth = depth - 1; ch.key = child_key(node, 1); DT_CPATH(ch, 2);
               stack[base] = ch;
               DT_NPEND(1);
             }
@@ -3954,9 +3981,10 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
     for (int i = (int)threadIdx.x; i < S.n_clear0; i += DT_WAVE) S.clear0[i] = 0ull;
     for (int i = (int)threadIdx.x; i < S.n_clear1; i += DT_WAVE) S.clear1[i] = 0ull;
   }
-  // LDS (one wave per block). nrec holds a lane's shading record across the shadow walks
-  // (inside run_pass only); red (per-chunk sample colours) and dens (cloud march chunk) are
-  // used after the passes, so they share its space. ocol: the DFS colour accumulator,
+  // LDS (one wave per block). nrec holds a lane's shading record across the shadow walks, and
+  // before the first of them the pass's root ray and origin in rows 0-5 (inside run_pass only);
+  // red (per-chunk sample colours) and dens (cloud march chunk) are used after the passes, so
+  // they share its space. ocol: the DFS colour accumulator,
   // psum: the per-pixel sums, parked here instead of in registers across the DFS.
   __shared__ double nrec[9][DT_WAVE];
   double* const red = &nrec[0][0];                        // DT_WAVE * 3 doubles
