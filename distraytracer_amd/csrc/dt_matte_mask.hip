@@ -5,16 +5,8 @@
 // one function (mm_pixel) of plain f32 additions that the host loop and the kernel both call.
 //
 // A translation unit of its own, compiled once for both libraries: dt_kernels.hip's objects stay as they are.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <string>
-
-#include "../../include/dt.h"
-
-namespace dth {
-void set_error(const std::string& e);   // dt_api.cpp (dt_last_error's message)
-}
+// The error prefix, the 1-D grid and the (untimed) launch are dt_post.h's.
+#include "dt_post.h"
 
 namespace {
 
@@ -46,11 +38,7 @@ __global__ __launch_bounds__(256) void dt_matte_mask_kernel(MmArgs a)
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < a.n_pixels; q += (int64_t)gridDim.x * 256) mm_pixel(a, q);
 }
 
-int mm_fail(const std::string& msg)
-{
-  dth::set_error("dt_matte_mask: " + msg);
-  return DT_E_INVALID;
-}
+constexpr post::Fail mm_fail{"dt_matte_mask"};
 
 }  // namespace
 
@@ -83,13 +71,9 @@ extern "C" int dt_matte_mask(int64_t n_pixels, int32_t layers, const int32_t* id
     for (int64_t q = 0; q < n_pixels; ++q) mm_pixel(a, q);
     return DT_OK;
   }
-  const int64_t blocks = (n_pixels + 255) / 256;
-  const unsigned grid = (unsigned)(blocks < 65536 ? blocks : 65536);
-  hipLaunchKernelGGL(dt_matte_mask_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    dth::set_error(std::string("dt_matte_mask: ") + hipGetErrorString(e));
-    return DT_E_NO_DEVICE;
-  }
-  return DT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  return post::launch(st, nullptr, mm_fail.who, [&] {   // untimed: nothing waits
+    hipLaunchKernelGGL(dt_matte_mask_kernel, post::linear_grid(n_pixels, 65536), dim3(256), 0, st, a);
+    return hipGetLastError();
+  });
 }

@@ -8,18 +8,12 @@
 // and square root), and the whole pixel, taps included, is one function (tp_pixel) that the host loop and
 // the kernel both call.
 //
-// A translation unit of its own: dt_kernels.hip, dt_api.cpp, dt_denoise.hip and dt_denoise_var.hip, and
-// with them every object they compile to, stay as they are.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-#include <string>
-
-#include "../../include/dt.h"
+// A translation unit of its own (dt_kernels.hip and dt_api.cpp stay as they are). The demodulation
+// divisor, the overlap test, the row grid and the timed launch are dt_post.h's; the projection's
+// arithmetic (tp_dot, tp_pixel) is used here alone and stays here.
+#include "dt_post.h"
 
 namespace dth {
-void set_error(const std::string& e);                                       // dt_api.cpp (dt_last_error's message)
 int camera_record(const dt_globals& g, dt_camera& out, std::string& err);   // host_flatten.cpp
 }
 
@@ -47,8 +41,6 @@ struct TpArgs {
 
 TP_HD float tp_dot(const float* u, const float* v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
 
-TP_HD float tp_demod(float a, int demodulate) { return demodulate ? fmaxf(a, 0.0625f) : 1.0f; }
-
 TP_HD int tp_clampi(int v, int hi) { return v < 0 ? 0 : v > hi ? hi : v; }
 
 // One pixel, steps 1-9 of include/dt.h: x the column, r the buffer row (render row y = H-1-r). The four
@@ -65,7 +57,7 @@ TP_HD void tp_pixel(const TpArgs& a, int x, int r)
   for (int k = 0; k < 3; ++k) {
     c[k] = a.C[3 * q + k];
     a_p[k] = a.A[3 * q + k];
-    d[k] = tp_demod(a_p[k], a.demodulate);
+    d[k] = post::demod(a_p[k], a.demodulate);
     e_p[k] = c[k] / d[k];
     vc[k] = has_var ? a.Vc[3 * q + k] : 0.0f;
     ve[k] = vc[k] / (d[k] * d[k]);
@@ -159,11 +151,7 @@ __global__ __launch_bounds__(256) void dt_reproject_kernel(TpArgs a)
   for (int r = blockIdx.y * 4 + threadIdx.y; r < a.H; r += gridDim.y * 4) tp_pixel(a, x, r);
 }
 
-int tp_fail(const std::string& msg)
-{
-  dth::set_error("dt_reproject: " + msg);
-  return DT_E_INVALID;
-}
+constexpr post::Fail tp_fail{"dt_reproject"};
 
 TpCam tp_cam(const dt_camera* c)
 {
@@ -188,12 +176,7 @@ struct TpPlane {
   int64_t floats;   // 4-byte elements
 };
 
-bool tp_overlap(const TpPlane& a, const TpPlane& b)
-{
-  const uintptr_t a0 = (uintptr_t)a.p, a1 = a0 + (uintptr_t)a.floats * 4;
-  const uintptr_t b0 = (uintptr_t)b.p, b1 = b0 + (uintptr_t)b.floats * 4;
-  return a0 < b1 && b0 < a1;
-}
+bool tp_overlap(const TpPlane& a, const TpPlane& b) { return post::overlap(a.p, a.floats, b.p, b.floats); }
 
 }  // namespace
 
@@ -234,17 +217,13 @@ int dt_reproject(const dt_camera* cur, const float* colour, const float* varianc
   if (!p) return tp_fail("null params");
   if (!out) return tp_fail("null out");
   if (!hist_out) return tp_fail("null hist_out");
-  if (!feat->albedo) return tp_fail("feat->albedo missing");
-  if (!feat->normal) return tp_fail("feat->normal missing");
-  if (!feat->depth) return tp_fail("feat->depth missing");
+  if (const std::string m = post::planes_missing(feat, "feat"); !m.empty()) return tp_fail(m);
   const bool has_prev = prev || prev_feat || hist_in;
   if (has_prev) {
     if (!prev) return tp_fail("null prev with a history");
     if (!prev_feat) return tp_fail("null prev_feat with a history");
     if (!hist_in) return tp_fail("null hist_in with a previous frame");
-    if (!prev_feat->albedo) return tp_fail("prev_feat->albedo missing");
-    if (!prev_feat->normal) return tp_fail("prev_feat->normal missing");
-    if (!prev_feat->depth) return tp_fail("prev_feat->depth missing");
+    if (const std::string m = post::planes_missing(prev_feat, "prev_feat"); !m.empty()) return tp_fail(m);
     if (!hist_in->colour) return tp_fail("hist_in->colour missing");
     if (!hist_in->len) return tp_fail("hist_in->len missing");
     if (variance && !hist_in->var) return tp_fail("hist_in->var missing (variance is given)");
@@ -329,31 +308,10 @@ int dt_reproject(const dt_camera* cur, const float* colour, const float* varianc
     return DT_OK;
   }
   hipStream_t st = (hipStream_t)stream;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipError_t e = hipSuccess;
-  if (kernel_ms) {
-    e = hipEventCreate(&ev0);
-    if (e == hipSuccess) e = hipEventCreate(&ev1);
-    if (e == hipSuccess) e = hipEventRecord(ev0, st);
-  }
-  if (e == hipSuccess) {
-    int64_t gy = ((int64_t)H + 3) / 4;
-    if (gy > 65535) gy = 65535;   // (the kernel strides over rows past that)
-    hipLaunchKernelGGL(dt_reproject_kernel, dim3((unsigned)(((int64_t)W + 63) / 64), (unsigned)gy), dim3(64, 4), 0, st, a);
-    e = hipGetLastError();
-  }
-  if (kernel_ms) {
-    if (e == hipSuccess) e = hipEventRecord(ev1, st);
-    if (e == hipSuccess) e = hipEventSynchronize(ev1);
-    if (e == hipSuccess) e = hipEventElapsedTime(kernel_ms, ev0, ev1);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-  }
-  if (e != hipSuccess) {
-    dth::set_error(std::string("dt_reproject: ") + hipGetErrorString(e));
-    return DT_E_NO_DEVICE;
-  }
-  return DT_OK;
+  return post::launch(st, kernel_ms, tp_fail.who, [&] {
+    hipLaunchKernelGGL(dt_reproject_kernel, post::row_grid(W, H), dim3(64, 4), 0, st, a);
+    return hipGetLastError();
+  });
 }
 
 }  // extern "C"

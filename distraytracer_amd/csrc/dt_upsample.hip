@@ -6,20 +6,10 @@
 // rounded IEEE f32 operation (no contraction, correctly rounded division), and a pixel's arithmetic is one
 // function (up_pixel) that the host loop and the kernel both call.
 //
-// A translation unit of its own: dt_kernels.hip and dt_api.cpp, and with them every object they
-// compile to, stay as they are.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <string>
-
-#include "../../include/dt.h"
-
-namespace dth {
-void set_error(const std::string& e);   // dt_api.cpp (dt_last_error's message)
-}
+// A translation unit of its own (dt_kernels.hip and dt_api.cpp stay as they are). R, dist2, the
+// demodulation divisor, the host's helpers and the timed launch are dt_post.h's; the tent up_T is used here
+// alone and stays here.
+#include "dt_post.h"
 
 namespace {
 
@@ -34,21 +24,7 @@ struct UpArgs {
   float isn, isa, isz, fs;
 };
 
-UP_HD float up_R(float x)
-{
-  const float t = fmaxf(0.0f, 1.0f - x);
-  return t * t;
-}
-
 UP_HD float up_T(float t) { return fmaxf(0.0f, 1.0f - fabsf(t) * 0.5f); }
-
-UP_HD float up_demod(float a, int demodulate) { return demodulate ? fmaxf(a, 0.0625f) : 1.0f; }
-
-UP_HD float up_dist2(float p0, float p1, float p2, const float* q)
-{
-  const float d0 = p0 - q[0], d1 = p1 - q[1], d2 = p2 - q[2];
-  return (d0 * d0 + d1 * d1) + d2 * d2;
-}
 
 // The full-resolution pixel (R, X), 0 <= R < H, 0 <= X < W: its nine taps in the stated order, the
 // fallback and the store (include/dt.h). Every low-resolution read is at a tap inside w x h.
@@ -75,15 +51,15 @@ UP_HD void up_pixel(const UpArgs& a, int R, int X)
       if (c0 != c0 || c1 != c1 || c2 != c2) continue;   // a bad tap
       const float* Aq = a.A_lo + 3 * q;
       const float hsp = up_T(fx - (float)xq) * ty;
-      const float xn = up_dist2(n0, n1, n2, a.N_lo + 3 * q) * a.isn;
-      const float xa = up_dist2(a0, a1, a2, Aq) * a.isa;
+      const float xn = post::dist2(n0, n1, n2, a.N_lo + 3 * q) * a.isn;
+      const float xa = post::dist2(a0, a1, a2, Aq) * a.isa;
       const float dz = z - a.Z_lo[q];
       const float xz = ((dz * dz) * rz) * a.isz;
-      const float wq = (hsp * (up_R(xn) * up_R(xz))) * up_R(xa);
+      const float wq = (hsp * (post::R(xn) * post::R(xz))) * post::R(xa);
       if (wq > 0.0f) {
-        s0 = s0 + wq * (c0 / up_demod(Aq[0], a.demodulate));
-        s1 = s1 + wq * (c1 / up_demod(Aq[1], a.demodulate));
-        s2 = s2 + wq * (c2 / up_demod(Aq[2], a.demodulate));
+        s0 = s0 + wq * (c0 / post::demod(Aq[0], a.demodulate));
+        s1 = s1 + wq * (c1 / post::demod(Aq[1], a.demodulate));
+        s2 = s2 + wq * (c2 / post::demod(Aq[2], a.demodulate));
         wt = wt + wq;
       }
     }
@@ -102,13 +78,13 @@ UP_HD void up_pixel(const UpArgs& a, int R, int X)
       a.out[3 * p + 2] = c2;
       return;
     }
-    e0 = c0 / up_demod(a.A_lo[3 * q], a.demodulate);
-    e1 = c1 / up_demod(a.A_lo[3 * q + 1], a.demodulate);
-    e2 = c2 / up_demod(a.A_lo[3 * q + 2], a.demodulate);
+    e0 = c0 / post::demod(a.A_lo[3 * q], a.demodulate);
+    e1 = c1 / post::demod(a.A_lo[3 * q + 1], a.demodulate);
+    e2 = c2 / post::demod(a.A_lo[3 * q + 2], a.demodulate);
   }
-  a.out[3 * p] = fminf(fmaxf(e0 * up_demod(a0, a.demodulate), 0.0f), 255.0f);
-  a.out[3 * p + 1] = fminf(fmaxf(e1 * up_demod(a1, a.demodulate), 0.0f), 255.0f);
-  a.out[3 * p + 2] = fminf(fmaxf(e2 * up_demod(a2, a.demodulate), 0.0f), 255.0f);
+  a.out[3 * p] = fminf(fmaxf(e0 * post::demod(a0, a.demodulate), 0.0f), 255.0f);
+  a.out[3 * p + 1] = fminf(fmaxf(e1 * post::demod(a1, a.demodulate), 0.0f), 255.0f);
+  a.out[3 * p + 2] = fminf(fmaxf(e2 * post::demod(a2, a.demodulate), 0.0f), 255.0f);
 }
 
 // Block (64, 4): a wave is 64 consecutive X of one full-resolution row, so its reads of A, N, Z and its
@@ -124,20 +100,7 @@ __global__ __launch_bounds__(256) void dt_upsample_kernel(UpArgs a)
   for (int64_t R = (int64_t)blockIdx.y * 4 + threadIdx.y; R < a.H; R += (int64_t)gridDim.y * 4) up_pixel(a, (int)R, (int)X);
 }
 
-int up_fail(const char* msg)
-{
-  dth::set_error(std::string("dt_upsample: ") + msg);
-  return DT_E_INVALID;
-}
-
-bool up_sigma_ok(float s) { return s > 0.0f; }   // false for a NaN
-
-bool up_overlap(const float* a, int64_t na, const float* b, int64_t nb)
-{
-  const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)na * sizeof(float);
-  const uintptr_t b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)nb * sizeof(float);
-  return a0 < b1 && b0 < a1;
-}
+constexpr post::Fail up_fail{"dt_upsample"};
 
 }  // namespace
 
@@ -163,21 +126,17 @@ int dt_upsample(int32_t xRes, int32_t yRes, const float* colour_lo, const dt_fea
   if (!feat_hi) return up_fail("null feat_hi");
   if (!p) return up_fail("null params");
   if (!out) return up_fail("null out");
-  if (!feat_lo->albedo) return up_fail("feat_lo->albedo missing");
-  if (!feat_lo->normal) return up_fail("feat_lo->normal missing");
-  if (!feat_lo->depth) return up_fail("feat_lo->depth missing");
-  if (!feat_hi->albedo) return up_fail("feat_hi->albedo missing");
-  if (!feat_hi->normal) return up_fail("feat_hi->normal missing");
-  if (!feat_hi->depth) return up_fail("feat_hi->depth missing");
+  if (const std::string m = post::planes_missing(feat_lo, "feat_lo"); !m.empty()) return up_fail(m);
+  if (const std::string m = post::planes_missing(feat_hi, "feat_hi"); !m.empty()) return up_fail(m);
   if (xRes < 1) return up_fail("xRes < 1");
   if (yRes < 1) return up_fail("yRes < 1");
   if (p->factor < 2 || p->factor > 4) return up_fail("factor outside 2..4");
   if (xRes % p->factor) return up_fail("xRes is not a multiple of factor");
   if (yRes % p->factor) return up_fail("yRes is not a multiple of factor");
   if (p->demodulate != 0 && p->demodulate != 1) return up_fail("demodulate must be 0 or 1");
-  if (!up_sigma_ok(p->sigma_normal)) return up_fail("sigma_normal must be > 0");
-  if (!up_sigma_ok(p->sigma_depth)) return up_fail("sigma_depth must be > 0");
-  if (!up_sigma_ok(p->sigma_albedo)) return up_fail("sigma_albedo must be > 0");
+  if (!post::sigma_ok(p->sigma_normal)) return up_fail("sigma_normal must be > 0");
+  if (!post::sigma_ok(p->sigma_depth)) return up_fail("sigma_depth must be > 0");
+  if (!post::sigma_ok(p->sigma_albedo)) return up_fail("sigma_albedo must be > 0");
   UpArgs a;
   a.C_lo = colour_lo;
   a.A_lo = feat_lo->albedo;
@@ -198,13 +157,13 @@ int dt_upsample(int32_t xRes, int32_t yRes, const float* colour_lo, const dt_fea
   a.isz = 1.0f / (p->sigma_depth * p->sigma_depth);
   a.fs = (float)a.s;
   const int64_t n_hi = (int64_t)a.W * a.H, n_lo = (int64_t)a.w * a.h;
-  if (up_overlap(out, 3 * n_hi, a.C_lo, 3 * n_lo)) return up_fail("out aliases colour_lo");
-  if (up_overlap(out, 3 * n_hi, a.A_lo, 3 * n_lo)) return up_fail("out aliases feat_lo->albedo");
-  if (up_overlap(out, 3 * n_hi, a.N_lo, 3 * n_lo)) return up_fail("out aliases feat_lo->normal");
-  if (up_overlap(out, 3 * n_hi, a.Z_lo, n_lo)) return up_fail("out aliases feat_lo->depth");
-  if (up_overlap(out, 3 * n_hi, a.A_hi, 3 * n_hi)) return up_fail("out aliases feat_hi->albedo");
-  if (up_overlap(out, 3 * n_hi, a.N_hi, 3 * n_hi)) return up_fail("out aliases feat_hi->normal");
-  if (up_overlap(out, 3 * n_hi, a.Z_hi, n_hi)) return up_fail("out aliases feat_hi->depth");
+  if (post::overlap(out, 3 * n_hi, a.C_lo, 3 * n_lo)) return up_fail("out aliases colour_lo");
+  if (post::overlap(out, 3 * n_hi, a.A_lo, 3 * n_lo)) return up_fail("out aliases feat_lo->albedo");
+  if (post::overlap(out, 3 * n_hi, a.N_lo, 3 * n_lo)) return up_fail("out aliases feat_lo->normal");
+  if (post::overlap(out, 3 * n_hi, a.Z_lo, n_lo)) return up_fail("out aliases feat_lo->depth");
+  if (post::overlap(out, 3 * n_hi, a.A_hi, 3 * n_hi)) return up_fail("out aliases feat_hi->albedo");
+  if (post::overlap(out, 3 * n_hi, a.N_hi, 3 * n_hi)) return up_fail("out aliases feat_hi->normal");
+  if (post::overlap(out, 3 * n_hi, a.Z_hi, n_hi)) return up_fail("out aliases feat_hi->depth");
   if (!on_device) {
     for (int R = 0; R < a.H; ++R)
       for (int X = 0; X < a.W; ++X) up_pixel(a, R, X);
@@ -212,32 +171,10 @@ int dt_upsample(int32_t xRes, int32_t yRes, const float* colour_lo, const dt_fea
     return DT_OK;
   }
   hipStream_t st = (hipStream_t)stream;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipError_t e = hipSuccess;
-  if (kernel_ms) {
-    e = hipEventCreate(&ev0);
-    if (e == hipSuccess) e = hipEventCreate(&ev1);
-    if (e == hipSuccess) e = hipEventRecord(ev0, st);
-  }
-  if (e == hipSuccess) {
-    int64_t gy = ((int64_t)a.H + 3) / 4;
-    if (gy > 65535) gy = 65535;   // (the kernel strides over rows past that)
-    const dim3 grid((unsigned)(((int64_t)a.W + 63) / 64), (unsigned)gy);
-    hipLaunchKernelGGL(dt_upsample_kernel, grid, dim3(64, 4), 0, st, a);
-    e = hipGetLastError();
-  }
-  if (kernel_ms) {
-    if (e == hipSuccess) e = hipEventRecord(ev1, st);
-    if (e == hipSuccess) e = hipEventSynchronize(ev1);
-    if (e == hipSuccess) e = hipEventElapsedTime(kernel_ms, ev0, ev1);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-  }
-  if (e != hipSuccess) {
-    dth::set_error(std::string("dt_upsample: ") + hipGetErrorString(e));
-    return DT_E_NO_DEVICE;
-  }
-  return DT_OK;
+  return post::launch(st, kernel_ms, up_fail.who, [&] {
+    hipLaunchKernelGGL(dt_upsample_kernel, post::row_grid(a.W, a.H), dim3(64, 4), 0, st, a);
+    return hipGetLastError();
+  });
 }
 
 }  // extern "C"

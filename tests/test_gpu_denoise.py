@@ -52,14 +52,23 @@ def _np(feats):
 @pytest.fixture(scope="module")
 def synthetic():
     """the shared planes: 37x23 (one workgroup column, steps 16 and 32 mostly outside) and 130x70 (three
-    workgroups in x, eighteen in y, halos crossing them at every step; 130 is no multiple of 64)"""
-    return {(w, h): synthetic_planes(w, h) for (w, h) in ((37, 23), (130, 70))}
+    workgroups in x, eighteen in y, halos crossing them at every step; 130 is no multiple of 64); the lane
+    boundary of the (64, 4) block, widths 63 (one dead lane), 64 (none) and 65 (a second block with one live
+    lane, its dead lanes clamped to W-1) with heights 3 (an idle row) and 5 (a second block row); and 1x1 and
+    1x40, where the taps have no or one column inside"""
+    return {(w, h): synthetic_planes(w, h) for (w, h) in SHAPES}
 
 
-@pytest.mark.parametrize("w,h", [(37, 23), (130, 70)])
+SHAPES = [(37, 23), (130, 70)] + [(w, h) for w in (63, 64, 65) for h in (3, 5)] + [(1, 1), (1, 40)]
+
+
+# levels 6: every tap column of step 32 falls outside for part of a 63..65 row, every tap row of step >= 4
+# outside a height of 3 or 5; levels 1: the last level is the only one; levels 2: one ping-pong swap before it
+@pytest.mark.parametrize("w,h", SHAPES)
 @pytest.mark.parametrize("p", [params(levels=6), params(levels=6, demodulate=0), params(levels=1),
+                               params(levels=1, demodulate=0), params(levels=2), params(levels=2, demodulate=0),
                                params(levels=5, sc=INF), params(levels=4, sn=INF, sz=INF, sa=INF)],
-                         ids=["l6", "l6-nodemod", "l1", "l5-colour-off", "l4-guides-off"])
+                         ids=["l6", "l6-nodemod", "l1", "l1-nodemod", "l2", "l2-nodemod", "l5-colour-off", "l4-guides-off"])
 def test_device_equals_host_equals_numpy(cuda, synthetic, w, h, p):
     c, f = synthetic[(w, h)]
     want = denoise_ref_params(w, h, c, f, p)

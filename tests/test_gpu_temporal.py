@@ -55,12 +55,13 @@ def _device_vs_host_vs_numpy(w, h, cam, p, variance, shapes):
         log_equal("%s %s device vs numpy" % (label, name), bits(dv.cpu().numpy()), bits(nv))
 
 
-@pytest.mark.parametrize("w,h", [(37, 23), (130, 70)])
+@pytest.mark.parametrize("w,h", [(37, 23), (130, 70), (64, 7), (65, 7)])
 @pytest.mark.parametrize("cam", CAMERAS)
 @pytest.mark.parametrize("demod,variance,shapes", [(1, True, True), (0, False, False)], ids=["demod-var-shapes", "plain"])
 def test_device_equals_host_equals_numpy(cuda, w, h, cam, demod, variance, shapes):
     """37x23: one workgroup column, a part of a wave idle; 130x70: three workgroups in x (130 is no multiple of
-    64) and eighteen in y, taps crossing them"""
+    64) and eighteen in y, taps crossing them; 64x7 and 65x7: the lane boundary of the (64, 4) block (no idle
+    lane; a second block with one live lane) and a second block row with an idle row"""
     _device_vs_host_vs_numpy(w, h, cam, params(demodulate=demod), variance, shapes)
 
 

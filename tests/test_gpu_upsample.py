@@ -44,8 +44,10 @@ def _guarded(g, c_lo, f_lo, f_hi, p):
     return got[guard:-guard]
 
 
-# the host test's shapes, and 260x140: five work-groups in x, 35 in y, 260 no multiple of 64
-@pytest.mark.parametrize("W,H,s", SHAPES + [(260, 140, 2)])
+# the host test's shapes; 260x140: five work-groups in x, 35 in y, 260 no multiple of 64; and the lane boundary
+# of the (64, 4) block: a width of exactly 64 (no idle lane) and the next the factor allows (a second block
+# with s live lanes), with a height that leaves rows of the last block idle where the factor allows one
+@pytest.mark.parametrize("W,H,s", SHAPES + [(260, 140, 2), (64, 6, 2), (66, 6, 2), (64, 12, 4), (68, 12, 4)])
 @pytest.mark.parametrize("which", list(PARAMS))
 def test_device_equals_host_equals_numpy(cuda, W, H, s, which):
     c_lo, f_lo, f_hi = planes(W, H, s)
