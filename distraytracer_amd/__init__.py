@@ -199,6 +199,24 @@ def intersect_primary(scene, g, frame, first_ray, hit_shape, hit_t, stream=None)
     return ms.value
 
 
+def debug_vdiv(vectors, den):
+    """The device's division of vectors[i] (n x 3 float64) by den[i] (include/dt.h dt_debug_vdiv): a dict of
+    n x 3 arrays `divs_shared`, `divs_plain`, `normalized_shared`, `normalized_plain` and the counts
+    `fallback_divs`, `fallback_normalized` of vectors whose shared path divided plainly."""
+    import numpy as np
+    v = np.ascontiguousarray(vectors, dtype=np.float64)
+    s = np.ascontiguousarray(den, dtype=np.float64)
+    if v.ndim != 2 or v.shape[1] != 3 or s.shape != (len(v),):
+        raise DTError("debug_vdiv: vectors n x 3, den n")
+    out = np.empty((4, len(v), 3), dtype=np.float64)
+    fb = (ctypes.c_uint64 * 2)()
+    PD = ctypes.POINTER(ctypes.c_double)
+    check(lib.dt_debug_vdiv(v.ctypes.data_as(PD), s.ctypes.data_as(PD), out.ctypes.data_as(PD), fb, len(v)),
+          "dt_debug_vdiv")
+    return {"divs_shared": out[0], "divs_plain": out[1], "normalized_shared": out[2], "normalized_plain": out[3],
+            "fallback_divs": int(fb[0]), "fallback_normalized": int(fb[1])}
+
+
 FEATURE_PLANES = ("albedo", "normal", "depth", "coverage", "shape")
 GUIDE_MAX_BOUNCES = 8   # DT_GUIDE_MAX_BOUNCES
 GUIDE_STOP, GUIDE_REFLECT, GUIDE_REFRACT = 0, 1, 2

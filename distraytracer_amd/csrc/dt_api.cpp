@@ -29,6 +29,8 @@ extern "C" hipError_t dt_launch_chunk_sum(const void* dev_launch, float* out, in
 extern "C" hipError_t dt_launch_unpack(const void* dev_launch, int world, int64_t slab_floats, const float* slabs,
                                        float* image, hipStream_t stream);
 extern "C" hipError_t dt_launch_normalize(const double* in, double* out, int64_t n, hipStream_t stream);
+extern "C" hipError_t dt_launch_vdiv(const double* in, const double* den, double* out, unsigned long long* fallback,
+                                     int64_t n, hipStream_t stream);
 // the trace-kernel builds (dt_kernels.hip DT_TRACE_KERNEL, Makefile TRACE_BUILDS)
 #define DT_TRACE_BUILD(k)                                                                              \
   extern "C" hipError_t k##_launch(const void* dev_launch, float* out, int grid, hipStream_t stream); \
@@ -2209,6 +2211,30 @@ extern "C" int dt_debug_normalize(const double* in, double* out, int64_t n)
   if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
   (void)hipFree(din);
   (void)hipFree(dout);
+  if (e != hipSuccess) return fail(DT_E_NO_DEVICE, std::string("HIP: ") + hipGetErrorString(e));
+  return DT_OK;
+}
+
+extern "C" int dt_debug_vdiv(const double* in, const double* den, double* out, uint64_t* fallback, int64_t n)
+{
+  if (!in || !den || !out || !fallback || n < 0 || n > (int64_t)1 << 24) return fail(DT_E_INVALID, "bad arguments");
+  fallback[0] = fallback[1] = 0;
+  if (n == 0) return DT_OK;
+  int dev_count = 0;
+  if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count < 1) return fail(DT_E_NO_DEVICE, "no HIP device");
+  // one allocation: the vectors (3n), the divisors (n), the four result blocks (12n), the two counters
+  const size_t nd = (size_t)n * 16;
+  double* d = nullptr;
+  if (hipMalloc((void**)&d, (nd + 2) * sizeof(double)) != hipSuccess) return fail(DT_E_OOM, "hipMalloc");
+  double *din = d, *dden = d + 3 * n, *dout = d + 4 * n;
+  unsigned long long* dfb = (unsigned long long*)(d + nd);
+  hipError_t e = hipMemcpy(din, in, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dden, den, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(dfb, 0, 2 * sizeof(unsigned long long));
+  if (e == hipSuccess) e = dt_launch_vdiv(din, dden, dout, dfb, n, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 12 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(fallback, dfb, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
   if (e != hipSuccess) return fail(DT_E_NO_DEVICE, std::string("HIP: ") + hipGetErrorString(e));
   return DT_OK;
 }

@@ -4703,7 +4703,54 @@ extern "C" __global__ void dt_normalize_kernel(const double* __restrict__ in, do
   out[3 * i + 2] = v.z;
 }
 
+// dt_math.h's division of a vector by one scalar on n vectors in[3i..3i+2] and divisors den[i], by
+// the shared-reciprocal path (divs_shared) and by three plain divisions (divs_plain), whatever DT_VDIV
+// this build has: out's four blocks of 3n doubles are a / den shared, a / den plain, normalized(a)
+// shared, normalized(a) plain. fallback[0], fallback[1]: the lanes whose shared a / den and whose
+// shared normalisation took the plain branch (tests/test_gpu_vdiv.py).
+extern "C" __global__ void __launch_bounds__(256)
+dt_vdiv_kernel(const double* __restrict__ in, const double* __restrict__ den, double* __restrict__ out,
+               unsigned long long* __restrict__ fallback, int64_t n)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool fb_div = false, fb_nrm = false;
+  if (i < n) {
+    const V3 a = v3(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
+    const double s = den[i];
+    bool shared = true;
+    V3 r[4];
+    r[0] = divs_shared(a, s, shared);
+    fb_div = !shared;
+    r[1] = divs_plain(a, s);
+    r[2] = r[3] = a;
+    const double nn = dot(a, a);
+    if (nn > 0) {
+      shared = true;
+      r[2] = divs_shared(a, sqrt(nn), shared);
+      fb_nrm = !shared;
+      r[3] = divs_plain(a, sqrt(nn));
+    }
+    for (int k = 0; k < 4; ++k) {
+      double* __restrict__ o = out + (int64_t)k * 3 * n + 3 * i;
+      o[0] = r[k].x;
+      o[1] = r[k].y;
+      o[2] = r[k].z;
+    }
+  }
+  const unsigned long long n_div = __popcll(__ballot(fb_div)), n_nrm = __popcll(__ballot(fb_nrm));
+  if ((threadIdx.x & 63) == 0) {
+    if (n_div) atomicAdd(fallback, n_div);
+    if (n_nrm) atomicAdd(fallback + 1, n_nrm);
+  }
+}
+
 // ---- host-side launch wrappers ---------------------------------------------------------
+extern "C" hipError_t dt_launch_vdiv(const double* in, const double* den, double* out, unsigned long long* fallback,
+                                     int64_t n, hipStream_t stream)
+{
+  hipLaunchKernelGGL(dt_vdiv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, den, out, fallback, n);
+  return hipGetLastError();
+}
 extern "C" hipError_t dt_launch_normalize(const double* in, double* out, int64_t n, hipStream_t stream)
 {
   hipLaunchKernelGGL(dt_normalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, out, n);

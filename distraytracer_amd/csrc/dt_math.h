@@ -30,7 +30,56 @@ DT_HD V3 add(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
 DT_HD V3 sub(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
 DT_HD V3 mul(double s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
 DT_HD V3 neg(V3 a) { return v3(-a.x, -a.y, -a.z); }
-DT_HD V3 divs(V3 a, double s) { return v3(a.x / s, a.y / s, a.z / s); }
+DT_HD V3 divs_plain(V3 a, double s) { return v3(a.x / s, a.y / s, a.z / s); }
+// DT_VDIV=1 (default): device code divides a vector's three components by one s with one reciprocal
+// refinement instead of three (DT_VDIV=0: three plain divisions, as the host always does).
+#ifndef DT_VDIV
+#define DT_VDIV 1
+#endif
+#if defined(__HIPCC__)
+// The compiler's f64 division n / d on gfx950, in its order (read off the ISA of the builds without this):
+//   ds = div_scale(d, d, n); r = rcp(ds); e = fma(-ds, r, 1); r = fma(r, e, r); e = fma(-ds, r, 1);
+//   r = fma(r, e, r); ns, vcc = div_scale(n, d, n); q = ns * r; t = fma(-ds, q, ns);
+//   div_fixup(div_fmas(t, r, q, vcc), d, n)
+// div_scale names the numerator, so the compiler keeps one r chain per quotient; but ds is the same bit
+// pattern for all three unless an exponent is near the range's ends. Where the three ds are bitwise equal
+// the three r chains are the same instructions on the same operands: one is computed, and every quotient
+// is the plain division's sequence on the plain division's operands, so its bits. Any other lane
+// divides plainly in a branch (shared = false there). The test of equality is the only guard.
+__device__ __forceinline__ double vdiv_quot(double n, double d, double ds, double r)
+{
+  bool vcc;
+  const double ns = __builtin_amdgcn_div_scale(n, d, true, &vcc);
+  const double q = ns * r;
+  const double t = __builtin_fma(-ds, q, ns);
+  return __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(t, r, q, vcc), d, n);
+}
+__device__ __forceinline__ V3 divs_shared(V3 a, double s, bool& shared)
+{
+  bool unused;
+  const double dx = __builtin_amdgcn_div_scale(a.x, s, false, &unused);
+  const double dy = __builtin_amdgcn_div_scale(a.y, s, false, &unused);
+  const double dz = __builtin_amdgcn_div_scale(a.z, s, false, &unused);
+  const uint64_t bx = __builtin_bit_cast(uint64_t, dx);
+  shared = bx == __builtin_bit_cast(uint64_t, dy) && bx == __builtin_bit_cast(uint64_t, dz);
+  if (__builtin_expect(!shared, 0)) return divs_plain(a, s);
+  double r = __builtin_amdgcn_rcp(dx);
+  double e = __builtin_fma(-dx, r, 1.0);
+  r = __builtin_fma(r, e, r);
+  e = __builtin_fma(-dx, r, 1.0);
+  r = __builtin_fma(r, e, r);
+  return v3(vdiv_quot(a.x, s, dx, r), vdiv_quot(a.y, s, dx, r), vdiv_quot(a.z, s, dx, r));
+}
+#endif
+DT_HD V3 divs(V3 a, double s)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && DT_VDIV
+  bool shared;
+  return divs_shared(a, s, shared);
+#else
+  return divs_plain(a, s);
+#endif
+}
 DT_HD double dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 DT_HD V3 cross(V3 a, V3 b)
 {

@@ -454,6 +454,12 @@ int64_t dt_debug_item_costs(const dt_scene* s, uint32_t* out, int64_t n);
 /* numerics check: the device kernels' normalisation of n VEC3s (Eigen normalized(), dt_math.h),
  * host arrays of 3n doubles; synchronous */
 int dt_debug_normalize(const double* in, double* out, int64_t n);
+/* numerics check of the device kernels' division of a VEC3 by one scalar (dt_math.h divs): n vectors
+ * in[3i..3i+2] and divisors den[i]; out: four blocks of 3n doubles, a / den by the shared-reciprocal
+ * path, a / den by three plain divisions, normalized(a) by either; fallback[0], fallback[1]: the
+ * vectors whose shared a / den and whose shared normalisation divided plainly after all (their three
+ * scaled divisors differ). Host arrays; synchronous. A diagnostic added under ABI 8. */
+int dt_debug_vdiv(const double* in, const double* den, double* out, uint64_t* fallback, int64_t n);
 
 /* Intersection micro-benchmark (2^24 primary rays of the C3 camera). rayColor's first
  * step (render_final_project.cpp:491-538: BVH gather + closest hit) for primary rays of the globals'

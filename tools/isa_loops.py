@@ -7,6 +7,8 @@ For every loop the compiler annotates ("in Loop: Header=BB0_n") prints the line 
 scratch accesses (spill/stack traffic) and the VALU count inside it, innermost loops first; then
 the scratch stores and loads bucketed by the innermost loop holding them (a store inside the
 DFS-step loop runs once per rayColor call and lane, one inside the item loop once per pixel).
+Further arguments name other mnemonics to bucket the same way, by prefix: the f64 division and
+square-root expansions are `v_rcp_f64 v_rsq_f64 v_div_scale_f64 v_div_fmas_f64 v_div_fixup_f64`.
 """
 import collections
 import re
@@ -29,7 +31,7 @@ def loops(lines):
     return sorted(rows)
 
 
-def main(path, kernel="dt_trace_kernel"):
+def main(path, kernel="dt_trace_kernel", *ops):
     text = open(path).read()
     m = re.search(r"^%s:.*?s_endpgm" % kernel, text, re.S | re.M)
     lines = (m.group(0) if m else text).split("\n")
@@ -45,12 +47,12 @@ def main(path, kernel="dt_trace_kernel"):
             if a <= i < j:
                 return "BB0_%s (%d lines)" % (h, n)
         return "outside loops"
-    for kind in ("scratch_store", "scratch_load"):
-        c = collections.Counter(innermost(i) for i, x in enumerate(lines) if kind in x)
+    for kind in ("scratch_store", "scratch_load") + ops:
+        c = collections.Counter(innermost(i) for i, x in enumerate(lines) if x.strip().startswith(kind))
         print("%s by innermost loop (total %d):" % (kind, sum(c.values())))
         for k, v in c.most_common():
             print("  %-28s %d" % (k, v))
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], *(sys.argv[2:3]))
+    main(*sys.argv[1:])
