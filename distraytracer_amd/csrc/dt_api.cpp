@@ -16,6 +16,7 @@
 #include "dt_adapt.h"
 #include "dt_guide.h"
 #include "host_internal.h"
+#include "host_launch.h"
 
 using namespace dth;
 
@@ -31,56 +32,24 @@ extern "C" hipError_t dt_launch_unpack(const void* dev_launch, int world, int64_
 extern "C" hipError_t dt_launch_normalize(const double* in, double* out, int64_t n, hipStream_t stream);
 extern "C" hipError_t dt_launch_vdiv(const double* in, const double* den, double* out, unsigned long long* fallback,
                                      int64_t n, hipStream_t stream);
-// the trace-kernel builds (dt_kernels.hip DT_TRACE_KERNEL, Makefile TRACE_BUILDS)
-#define DT_TRACE_BUILD(k)                                                                              \
+// The trace-kernel builds, named once (dt_kernels.hip DT_TRACE_KERNEL, Makefile TRACE_BUILDS, in its
+// order): per wave count (4, then 5) room, mesh, full (still frames), tunnel, blur (motion-blur frames)
+// and sky; then the work-sharing and the RectPrismWithCylinder build. Each exists in three modes: the
+// product build <k>, its window build <k>_win (DT_WINDOW, Makefile WIN_OBJ) and its adaptive window
+// build <k>_awin (DT_WINDOW=2, AWIN_OBJ). The declarations here and the table g_builds come from this list.
+#define DT_TRACE_BUILDS(X)                                                                               \
+  X(dt_trace_kernel) X(dt_trace_kernel_mesh) X(dt_trace_kernel_full) X(dt_trace_kernel_tunnel)           \
+  X(dt_trace_kernel_blur) X(dt_trace_kernel_sky) X(dt_trace_kernel_w5) X(dt_trace_kernel_w5_mesh)        \
+  X(dt_trace_kernel_w5_full) X(dt_trace_kernel_w5_tunnel) X(dt_trace_kernel_w5_blur)                     \
+  X(dt_trace_kernel_w5_sky) X(dt_trace_kernel_dn) X(dt_trace_kernel_rpc)
+#define DT_TRACE_DECL(k)                                                                               \
   extern "C" hipError_t k##_launch(const void* dev_launch, float* out, int grid, hipStream_t stream); \
   extern "C" const void* k##_ptr(void);                                                                \
   extern "C" int k##_traits(void);
-DT_TRACE_BUILD(dt_trace_kernel)
-DT_TRACE_BUILD(dt_trace_kernel_mesh)
-DT_TRACE_BUILD(dt_trace_kernel_full)
-DT_TRACE_BUILD(dt_trace_kernel_tunnel)
-DT_TRACE_BUILD(dt_trace_kernel_blur)
-DT_TRACE_BUILD(dt_trace_kernel_sky)
-DT_TRACE_BUILD(dt_trace_kernel_w5)
-DT_TRACE_BUILD(dt_trace_kernel_w5_mesh)
-DT_TRACE_BUILD(dt_trace_kernel_w5_full)
-DT_TRACE_BUILD(dt_trace_kernel_w5_tunnel)
-DT_TRACE_BUILD(dt_trace_kernel_w5_blur)
-DT_TRACE_BUILD(dt_trace_kernel_w5_sky)
-DT_TRACE_BUILD(dt_trace_kernel_dn)
-DT_TRACE_BUILD(dt_trace_kernel_rpc)
-// ... and each of them with the window mode of the item loop (dt_kernels.hip DT_WINDOW, Makefile WIN_OBJ)
-DT_TRACE_BUILD(dt_trace_kernel_win)
-DT_TRACE_BUILD(dt_trace_kernel_mesh_win)
-DT_TRACE_BUILD(dt_trace_kernel_full_win)
-DT_TRACE_BUILD(dt_trace_kernel_tunnel_win)
-DT_TRACE_BUILD(dt_trace_kernel_blur_win)
-DT_TRACE_BUILD(dt_trace_kernel_sky_win)
-DT_TRACE_BUILD(dt_trace_kernel_w5_win)
-DT_TRACE_BUILD(dt_trace_kernel_w5_mesh_win)
-DT_TRACE_BUILD(dt_trace_kernel_w5_full_win)
-DT_TRACE_BUILD(dt_trace_kernel_w5_tunnel_win)
-DT_TRACE_BUILD(dt_trace_kernel_w5_blur_win)
-DT_TRACE_BUILD(dt_trace_kernel_w5_sky_win)
-DT_TRACE_BUILD(dt_trace_kernel_dn_win)
-DT_TRACE_BUILD(dt_trace_kernel_rpc_win)
-// ... and the window builds with adaptive sampling (DT_WINDOW=2, Makefile AWIN_OBJ)
-DT_TRACE_BUILD(dt_trace_kernel_awin)
-DT_TRACE_BUILD(dt_trace_kernel_mesh_awin)
-DT_TRACE_BUILD(dt_trace_kernel_full_awin)
-DT_TRACE_BUILD(dt_trace_kernel_tunnel_awin)
-DT_TRACE_BUILD(dt_trace_kernel_blur_awin)
-DT_TRACE_BUILD(dt_trace_kernel_sky_awin)
-DT_TRACE_BUILD(dt_trace_kernel_w5_awin)
-DT_TRACE_BUILD(dt_trace_kernel_w5_mesh_awin)
-DT_TRACE_BUILD(dt_trace_kernel_w5_full_awin)
-DT_TRACE_BUILD(dt_trace_kernel_w5_tunnel_awin)
-DT_TRACE_BUILD(dt_trace_kernel_w5_blur_awin)
-DT_TRACE_BUILD(dt_trace_kernel_w5_sky_awin)
-DT_TRACE_BUILD(dt_trace_kernel_dn_awin)
-DT_TRACE_BUILD(dt_trace_kernel_rpc_awin)
-#undef DT_TRACE_BUILD
+#define DT_TRACE_DECL3(k) DT_TRACE_DECL(k) DT_TRACE_DECL(k##_win) DT_TRACE_DECL(k##_awin)
+DT_TRACE_BUILDS(DT_TRACE_DECL3)
+#undef DT_TRACE_DECL3
+#undef DT_TRACE_DECL
 extern "C" hipError_t dt_launch_resolve(const double* accum, float* out, int64_t n_px, int n_samples,
                                         unsigned long long* nan_px, hipStream_t stream);
 extern "C" hipError_t dt_launch_resolve_adaptive(const double* accum, const uint32_t* count, float* out, int64_t n_px,
@@ -168,6 +137,16 @@ int fail(int code, const std::string& msg)
       return fail(DT_E_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));  \
   } while (0)
 
+// the lazily grown device buffers of a scene (host_launch.h DevBuf) over the HIP calls
+struct HipMem {
+  typedef hipStream_t Stream;
+  static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+  static void free(void* p) { (void)hipFree(p); }
+  static int sync(hipStream_t st) { return (int)hipStreamSynchronize(st); }
+};
+typedef DevBuf<HipMem> DevMem;
+hipError_t reserve(DevMem& b, size_t bytes, hipStream_t st, bool* grew = nullptr) { return (hipError_t)b.reserve(bytes, st, grew); }
+
 // Scene uploads go through a non-blocking stream of the calling thread: a plain hipMemcpy runs on
 // the legacy null stream and waits for every kernel in flight, so a scene built on a worker
 // thread while the previous frame renders (tools/animate.py) would wait for that render.
@@ -245,8 +224,9 @@ struct dt_scene {
   void* d_mat = nullptr;
   void* d_lights = nullptr;
   void* d_tex = nullptr;
-  void* d_zs = nullptr;
-  size_t zs_cap = 0;
+  // the cloud z table (2048 floats); like every DevMem below grown by the launch that needs it
+  // (host_launch.h DevBuf: a failed allocation leaves it empty, so the next launch allocates again)
+  DevMem zs;
   // ST_N counters + queue word (+ the stamps builds' slots), twice: launches alternate between the
   // two (parity), and each zeroes the other for the next one (HScene::clear0)
   unsigned long long* d_stats = nullptr;
@@ -256,7 +236,7 @@ struct dt_scene {
   // frame rendered again uploads nothing: no copy kernel between its launches)
   void* d_launch = nullptr;
   std::vector<uint8_t> rec_last[2], rec2_last[2];
-  std::vector<float> zs_last;   // the z table in d_zs
+  std::vector<uint8_t> zs_last;   // the z table in zs
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_copy = nullptr;   // staging buffers may be rewritten once this has fired
   uint8_t* h_launch = nullptr;    // pinned staging for the launch record
@@ -272,22 +252,18 @@ struct dt_scene {
   std::vector<std::vector<P3>> fhull, bhull;   // leaf hull points per fast / bump tree node (host_hull.cpp)
   bool pl_bump = false;                        // lists for the blur passes follow the pass-0 lists
   std::vector<double> pl_key;
-  uint8_t* d_sky_miss = nullptr;   // 1-spp launches: missed-pixel flags (dt_sky_miss_kernel clears them)
-  int64_t sky_miss_cap = 0;
+  DevMem sky_miss;   // 1-spp launches: missed-pixel flags (dt_sky_miss_kernel clears them)
   // sky items (dt_kernels.hip DT_SKY_AGAIN): the list a still build leaves to its *_sky build, that
   // launch's record (pinned staging h_launch2, guarded by ev_copy like h_launch) and its counters
-  uint32_t* d_again = nullptr;
-  int64_t again_cap = 0;
+  DevMem again;
   void* d_launch2 = nullptr;
   uint8_t* h_launch2 = nullptr;
   unsigned long long* d_stats2 = nullptr;   // ST_N counters + queue word + list count, twice (parity)
   bool again_used = false;                  // the last render ran the second launch
-  void* d_dn_pool = nullptr;       // dt_trace_kernel_dn: DT_DN_POOL_REC work-sharing records per wave
-  int64_t dn_pool_waves = 0;
-  double* d_chunk_cols = nullptr;   // chunk items: spp sample colours per pixel item
-  int64_t chunk_cols_cap = 0;
-  uint32_t* d_item_cost = nullptr;  // DT_ITEM_COSTS=1 (diagnostic builds): per-item durations
-  int64_t item_cost_cap = 0, item_cost_n = 0;
+  DevMem dn_pool;      // dt_trace_kernel_dn: DT_DN_POOL_REC work-sharing records per wave
+  DevMem chunk_cols;   // chunk items: spp sample colours (double) per pixel item
+  DevMem item_cost;    // DT_ITEM_COSTS=1 (diagnostic builds): per-item durations (uint32_t),
+  int64_t item_cost_n = 0;   // of the last launch that recorded them
   PrimLists pl;
   bool pl_ok = false;
   void* d_pl_cells = nullptr;
@@ -295,10 +271,9 @@ struct dt_scene {
   dtd::DParams last;
   int last_px_samples = 0;   // samples per pixel of the last launch: spp, or a window's end - begin
   // adaptive window launches (dt_render_window_adaptive): the selection's buffers in one allocation
-  // (the list's length, the list, the per-wave offsets and keep bits; adapt_layout) for up to
-  // adapt_cap items; ev_sel fires when the selection kernels have run (dt_adapt_select_ms)
-  uint8_t* d_adapt = nullptr;
-  int64_t adapt_cap = -1;
+  // (the list's length, the list, the per-wave offsets and keep bits; adapt_layout); ev_sel fires
+  // when the selection kernels have run (dt_adapt_select_ms)
+  DevMem adapt;
   hipEvent_t ev_sel = nullptr;
   bool last_adaptive = false;   // the last launch ran over the selection's list: stats.pixels is its length
 };
@@ -451,14 +426,12 @@ static void release_device(dt_scene* s)
 {
   void** bufs[] = {&s->d_pl_cells, &s->d_pl_list, &s->d_nodes, &s->d_fnodes, &s->d_bnodes, &s->d_bparent,
                    &s->d_sg_cells, &s->d_sg_list, &s->d_sub_nodes, &s->d_sub_blocks, &s->d_leaf, &s->d_hdr, &s->d_geom, &s->d_mat, &s->d_lights,
-                   &s->d_tex, &s->d_zs, (void**)&s->d_stats, &s->d_launch, (void**)&s->d_sky_miss, &s->d_dn_pool,
-                   (void**)&s->d_again, &s->d_launch2, (void**)&s->d_stats2, (void**)&s->d_chunk_cols,
-                   (void**)&s->d_item_cost, (void**)&s->d_adapt};
+                   &s->d_tex, (void**)&s->d_stats, &s->d_launch, &s->d_launch2, (void**)&s->d_stats2};
   for (void** b : bufs) {
     if (*b) (void)hipFree(*b);
     *b = nullptr;
   }
-  s->adapt_cap = -1;
+  for (DevMem* b : {&s->zs, &s->sky_miss, &s->again, &s->dn_pool, &s->chunk_cols, &s->item_cost, &s->adapt}) b->release();
   s->last_adaptive = false;
   for (hipEvent_t* e : {&s->ev0, &s->ev1, &s->ev_copy, &s->ev_sel}) {
     if (*e) (void)hipEventDestroy(*e);
@@ -469,14 +442,9 @@ static void release_device(dt_scene* s)
   if (s->h_zs) (void)hipHostFree(s->h_zs);
   s->h_launch = nullptr;
   s->h_launch2 = nullptr;
-  s->again_cap = 0;
   s->again_used = false;
   s->h_zs = nullptr;
-  s->zs_cap = 0;
-  s->sky_miss_cap = 0;
-  s->dn_pool_waves = 0;
-  s->chunk_cols_cap = 0;
-  s->item_cost_cap = s->item_cost_n = 0;
+  s->item_cost_n = 0;
   s->copy_pending = s->timed = s->launched = false;
   s->pl_dirty = true;   // the primary lists go up again with the next upload
 }
@@ -799,7 +767,8 @@ static int upload_primary_lists(dt_scene* sc)
   return DT_OK;
 }
 
-// the device pointers of a scene's uploaded structures, as the kernels' DScene sees them
+// the device pointers of a scene's uploaded structures, as the kernels' DScene sees them; every
+// other field zero (enqueue_render sets the pointers its launch uses and leaves the rest null)
 static void fill_hscene(const dt_scene* sc, HScene& hs)
 {
   memset(&hs, 0, sizeof(hs));
@@ -828,42 +797,30 @@ struct Build {
   const void* (*ptr)(void);
   int (*traits)(void);
   const char* name;
-  int resident;
+  int resident;   // max_resident_waves, cached by the first launch
+  int mode, idx;  // its place in g_builds
 };
-#define DT_B(k) {k##_launch, k##_ptr, k##_traits, #k, 0}
-// per wave count (4, 5): room, mesh, full (still frames); tunnel, blur (motion-blur frames); sky
-static Build g_builds[2][6] = {
-    {DT_B(dt_trace_kernel), DT_B(dt_trace_kernel_mesh), DT_B(dt_trace_kernel_full),
-     DT_B(dt_trace_kernel_tunnel), DT_B(dt_trace_kernel_blur), DT_B(dt_trace_kernel_sky)},
-    {DT_B(dt_trace_kernel_w5), DT_B(dt_trace_kernel_w5_mesh), DT_B(dt_trace_kernel_w5_full),
-     DT_B(dt_trace_kernel_w5_tunnel), DT_B(dt_trace_kernel_w5_blur), DT_B(dt_trace_kernel_w5_sky)}};
-static Build g_dn_build = DT_B(dt_trace_kernel_dn), g_rpc_build = DT_B(dt_trace_kernel_rpc);
-// the same table of the window builds (dt_kernels.hip DT_WINDOW: trait bit 2), for dt_render_window
-static Build g_win_builds[2][6] = {
-    {DT_B(dt_trace_kernel_win), DT_B(dt_trace_kernel_mesh_win), DT_B(dt_trace_kernel_full_win),
-     DT_B(dt_trace_kernel_tunnel_win), DT_B(dt_trace_kernel_blur_win), DT_B(dt_trace_kernel_sky_win)},
-    {DT_B(dt_trace_kernel_w5_win), DT_B(dt_trace_kernel_w5_mesh_win), DT_B(dt_trace_kernel_w5_full_win),
-     DT_B(dt_trace_kernel_w5_tunnel_win), DT_B(dt_trace_kernel_w5_blur_win), DT_B(dt_trace_kernel_w5_sky_win)}};
-static Build g_dn_win_build = DT_B(dt_trace_kernel_dn_win), g_rpc_win_build = DT_B(dt_trace_kernel_rpc_win);
-// ... and of the adaptive window builds (trait bit 3), for dt_render_window_adaptive
-static Build g_awin_builds[2][6] = {
-    {DT_B(dt_trace_kernel_awin), DT_B(dt_trace_kernel_mesh_awin), DT_B(dt_trace_kernel_full_awin),
-     DT_B(dt_trace_kernel_tunnel_awin), DT_B(dt_trace_kernel_blur_awin), DT_B(dt_trace_kernel_sky_awin)},
-    {DT_B(dt_trace_kernel_w5_awin), DT_B(dt_trace_kernel_w5_mesh_awin), DT_B(dt_trace_kernel_w5_full_awin),
-     DT_B(dt_trace_kernel_w5_tunnel_awin), DT_B(dt_trace_kernel_w5_blur_awin), DT_B(dt_trace_kernel_w5_sky_awin)}};
-static Build g_dn_awin_build = DT_B(dt_trace_kernel_dn_awin), g_rpc_awin_build = DT_B(dt_trace_kernel_rpc_awin);
+#define DT_BI(k) BI_##k,
+enum { DT_TRACE_BUILDS(DT_BI) N_BUILDS };
+#undef DT_BI
+// (choose_build: wave count * BI_W5 + room, mesh, full, tunnel, blur; the sky build BI_SKY on)
+enum { BI_SKY = BI_dt_trace_kernel_sky, BI_W5 = BI_dt_trace_kernel_w5, BI_DN = BI_dt_trace_kernel_dn,
+       BI_RPC = BI_dt_trace_kernel_rpc };
+static_assert(BI_SKY == 5 && BI_W5 == 6 && BI_DN == 12 && N_BUILDS == 14, "choose_build and sky_build_for index by these");
+enum { MODE_PRODUCT = 0, MODE_WIN = 1, MODE_AWIN = 2 };   // the window builds carry trait bit 2, the adaptive ones bit 3 too
+#define DT_B(k, sfx, mode) {k##sfx##_launch, k##sfx##_ptr, k##sfx##_traits, #k #sfx, 0, mode, BI_##k},
+#define DT_B0(k) DT_B(k, , MODE_PRODUCT)
+#define DT_B1(k) DT_B(k, _win, MODE_WIN)
+#define DT_B2(k) DT_B(k, _awin, MODE_AWIN)
+static Build g_builds[3][N_BUILDS] = {{DT_TRACE_BUILDS(DT_B0)}, {DT_TRACE_BUILDS(DT_B1)}, {DT_TRACE_BUILDS(DT_B2)}};
+#undef DT_B2
+#undef DT_B1
+#undef DT_B0
 #undef DT_B
 
 // the window build of the product build b: the same flags with the window mode of the item loop
 // (adaptive: its adaptive window build)
-static Build& window_build_for(const Build& b, bool adaptive)
-{
-  for (int w = 0; w < 2; ++w)
-    for (int v = 0; v < 6; ++v)
-      if (&b == &g_builds[w][v]) return adaptive ? g_awin_builds[w][v] : g_win_builds[w][v];
-  if (&b == &g_dn_build) return adaptive ? g_dn_awin_build : g_dn_win_build;
-  return adaptive ? g_rpc_awin_build : g_rpc_win_build;
-}
+static Build& window_build_for(const Build& b, bool adaptive) { return g_builds[adaptive ? MODE_AWIN : MODE_WIN][b.idx]; }
 
 // A window launch (dt_render_window): the chunks [chunk_lo, chunk_hi) of every pixel item onto accum
 struct Window {
@@ -896,12 +853,10 @@ static AdaptLayout adapt_layout(int64_t n_items)
 
 // the feature mask a build was compiled for (its traits' bits 8..23: dt_kernels.hip DT_FEATURES)
 static unsigned build_features(const Build& b) { return ((unsigned)b.traits() >> 8) & 0xFFFFu; }
-// the *_sky build of the same wave count as the product build b (it renders b's sky items)
+// the *_sky build of the same wave count and mode as the build b (it renders b's sky items)
 static Build& sky_build_for(const Build& b)
 {
-  for (int v = 0; v < 6; ++v)
-    if (&b == &g_builds[1][v]) return g_builds[1][5];
-  return g_builds[0][5];
+  return g_builds[b.mode][(b.idx >= BI_W5 && b.idx < BI_DN ? BI_W5 : 0) + BI_SKY];
 }
 
 // The build a render of a scene with these features launches (kernel_choice: dt_scene_set_kernel).
@@ -914,8 +869,8 @@ static Build& choose_build(unsigned scene_features, bool no_cull, int kernel_cho
   const char* dn_env = kernel_choice == DT_KERNEL_AUTO ? getenv("DT_DONATE") : nullptr;
   const bool want_dn = kernel_choice == DT_KERNEL_DONATE || (dn_env && dn_env[0] == '1');
   const bool donate = !no_cull && want_dn && P.max_depth <= 11 && P.brdf_samples <= 6;
-  if (no_cull) return g_rpc_build;
-  if (donate) return g_dn_build;
+  if (no_cull) return g_builds[MODE_PRODUCT][BI_RPC];
+  if (donate) return g_builds[MODE_PRODUCT][BI_DN];
   // one pixel per wave (spp >= 64) takes the 5-waves-per-SIMD build (dt_kernels.hip DT_W5): C3 +1.8%,
   // C4 +4%; with several pixels per wave (C2, 16 spp) it loses 8% (profiles/r03ba_ab_w5.log).
   // DT_W5=0 never, DT_W5=1 at any spp with at most 8 pixels per wave (its per-pixel sums have 8 slots).
@@ -935,7 +890,7 @@ static Build& choose_build(unsigned scene_features, bool no_cull, int kernel_cho
   auto within = [&](unsigned mask) { return (feats & ~mask) == 0; };
   const int variant = blur ? (within(DT_TUNNEL_FEATURES) ? 3 : 4)
                            : within(DT_ROOM_FEATURES) ? 0 : within(DT_MESH_FEATURES) ? 1 : 2;
-  return g_builds[w5 ? 1 : 0][variant];
+  return g_builds[MODE_PRODUCT][(w5 ? BI_W5 : 0) + variant];
 }
 
 int dt_trace_build(const dt_scene_desc* desc, const dt_globals* g, int32_t frame, char* name, int32_t name_cap,
@@ -960,6 +915,99 @@ int dt_trace_build(const dt_scene_desc* desc, const dt_globals* g, int32_t frame
   return DT_OK;
 }
 
+// a staging block goes to its device copy only when its bytes differ from the last upload's (last)
+static hipError_t upload_if_changed(void* dst, const void* src, size_t bytes, std::vector<uint8_t>& last, hipStream_t st)
+{
+  if (last.size() == bytes && memcmp(last.data(), src, bytes) == 0) return hipSuccess;
+  const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) last.assign((const uint8_t*)src, (const uint8_t*)src + bytes);
+  return e;
+}
+
+// an adaptive window launch: the selection's buffers and event, and its parameters in P
+static int adaptive_setup(dt_scene* sc, dtd::DParams& P, const Window& win, hipStream_t st)
+{
+  if ((double)P.n_items >= 4294967296.0) return fail(DT_E_INVALID, "adaptive window: more than 2^32 items");
+  // (the offsets of the items of this launch: a smaller launch uses the head of a larger buffer)
+  const AdaptLayout L = adapt_layout(P.n_items);
+  HIPCHK(reserve(sc->adapt, L.bytes, st));
+  if (!sc->ev_sel) HIPCHK(hipEventCreate(&sc->ev_sel));
+  uint8_t* const d_adapt = sc->adapt.as<uint8_t>();
+  P.adapt_begin = win.begin;
+  P.adapt_end = win.end;
+  P.adapt_min = win.min_samples;
+  P.adapt_thr2 = win.thr2;
+  P.act_waves = (int32_t)L.waves;
+  P.accum2 = win.accum2;
+  P.count = win.count;
+  P.act_n = (uint32_t*)d_adapt;
+  P.act_list = (uint32_t*)(d_adapt + L.list);
+  P.act_off = (uint32_t*)(d_adapt + L.off);
+  P.act_mask = (unsigned long long*)(d_adapt + L.mask);
+  return DT_OK;
+}
+
+// The sky-item launch's buffers, all three or none: allocated into temporaries, committed together,
+// freed on a failure
+static int sky_item_buffers(dt_scene* sc, hipStream_t st)
+{
+  if (sc->d_stats2 && sc->d_launch2 && sc->h_launch2) return DT_OK;
+  unsigned long long* st2 = nullptr;
+  void* dl2 = nullptr;
+  uint8_t* hl2 = nullptr;
+  hipError_t e = hipMalloc((void**)&st2, sizeof(unsigned long long) * 2 * STATS2);
+  if (e == hipSuccess) e = hipMemsetAsync(st2, 0, sizeof(unsigned long long) * 2 * STATS2, st);
+  if (e == hipSuccess) e = hipMalloc(&dl2, 2 * dt_launch_size());
+  if (e == hipSuccess) e = hipHostMalloc((void**)&hl2, dt_launch_size(), hipHostMallocDefault);
+  if (e != hipSuccess) {
+    if (st2) (void)hipFree(st2);
+    if (dl2) (void)hipFree(dl2);
+    if (hl2) (void)hipHostFree(hl2);
+    return fail(DT_E_NO_DEVICE, std::string("sky-item launch buffers: ") + hipGetErrorString(e));
+  }
+  if (sc->d_stats2) (void)hipFree(sc->d_stats2);
+  if (sc->d_launch2) (void)hipFree(sc->d_launch2);
+  if (sc->h_launch2) (void)hipHostFree(sc->h_launch2);
+  sc->d_stats2 = st2;
+  sc->d_launch2 = dl2;
+  sc->h_launch2 = hl2;
+  sc->rec2_last[0].clear();
+  sc->rec2_last[1].clear();
+  return DT_OK;
+}
+
+// The sky-item launch's record: the trace launch's (hs, PL) with counters of its own, the listed
+// items for a queue and none of the trace launch's queue policy; uploaded to d_rec2 if it changed
+static hipError_t sky_item_record(dt_scene* sc, const HScene& hs, const dtd::DParams& PL, int par, uint8_t* d_rec2,
+                                  hipStream_t st)
+{
+  HScene hs2 = hs;
+  hs2.stats = sc->d_stats2 + par * STATS2;
+  hs2.queue = hs2.stats + ST_N;
+  hs2.clear0 = hs2.clear1 = nullptr;   // the first launch cleared them
+  hs2.n_clear0 = hs2.n_clear1 = 0;
+  dtd::DParams PL2 = PL;
+  PL2.sky_again = 2;
+  PL2.item_batch = 1;
+  PL2.queue_segs = 1;
+  PL2.prio_steps = 0;
+  memset(sc->h_launch2, 0, dt_launch_size());
+  memcpy(sc->h_launch2 + dt_scene_struct_offset(), &hs2, sizeof(hs2));
+  memcpy(sc->h_launch2 + dt_params_struct_offset(), &PL2, sizeof(PL2));
+  return upload_if_changed(d_rec2, sc->h_launch2, dt_launch_size(), sc->rec2_last[par], st);
+}
+
+// ... and the launch itself, after the trace launch that lists the items (grid: that launch's)
+static hipError_t sky_item_launch(Build& kb2, const uint8_t* d_rec2, float* out_dev, int64_t grid, hipStream_t st)
+{
+  if (!kb2.resident) kb2.resident = max_resident_waves(kb2.ptr(), 64);
+  // a few listed items in the scenes that use it (room frames: none to a handful): 512 waves
+  // start and drain faster than a full persistent grid
+  int64_t g2 = grid < kb2.resident ? grid : kb2.resident;
+  g2 = g2 < 512 ? g2 : 512;
+  return kb2.launch(d_rec2, out_dev, (int)g2, st);
+}
+
 // win: a window launch (dt_render_window) onto win->accum, out_dev unused; null: a whole render
 static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>& zs, float* out_dev,
                           hipStream_t st, const Window* win = nullptr)
@@ -971,32 +1019,26 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
   // copies themselves are stream-ordered after any earlier kernel that reads them.
   if (sc->copy_pending) HIPCHK(hipEventSynchronize(sc->ev_copy));
   size_t nz = zs.size() < 2048 ? zs.size() : 2048;
-  if (nz > sc->zs_cap) {
-    if (sc->d_zs) HIPCHK(hipStreamSynchronize(st));
-    if (sc->d_zs) (void)hipFree(sc->d_zs);
-    sc->d_zs = nullptr;
-    sc->zs_last.clear();
-    sc->zs_cap = 2048;
-    HIPCHK(hipMalloc(&sc->d_zs, sc->zs_cap * sizeof(float)));
+  if (nz) {
+    bool grew = false;
+    HIPCHK(reserve(sc->zs, 2048 * sizeof(float), st, &grew));
+    if (grew) sc->zs_last.clear();
+    memcpy(sc->h_zs, zs.data(), nz * sizeof(float));
   }
-  if (nz) memcpy(sc->h_zs, zs.data(), nz * sizeof(float));
   HScene hs;
   fill_hscene(sc, hs);
-  hs.cloud_z = (const float*)sc->d_zs;
+  hs.cloud_z = sc->zs.as<const float>();
   const int par = sc->n_launch & 1;
   hs.stats = sc->d_stats + par * STATS1;
   hs.queue = hs.stats + ST_N;
   hs.clear0 = sc->d_stats + (1 - par) * STATS1;
   hs.n_clear0 = (int32_t)STATS1;
-  hs.clear1 = nullptr;
-  hs.n_clear1 = 0;
-  const int kernel_choice = sc->kernel;
-  Build& kb_product = choose_build(sc->features, sc->no_cull, kernel_choice, P);
-  const bool donate = &kb_product == &g_dn_build;
+  Build& kb_product = choose_build(sc->features, sc->no_cull, sc->kernel, P);
+  const bool donate = kb_product.idx == BI_DN;
   // a window launch takes the window builds of the same choice (and of its *_sky build)
   const bool adaptive = win && win->accum2;
   Build& kb = win ? window_build_for(kb_product, adaptive) : kb_product;
-  Build& kb2 = win ? window_build_for(sky_build_for(kb_product), adaptive) : sky_build_for(kb_product);
+  Build& kb2 = sky_build_for(kb);
   if (win && (!(kb.traits() & 4) || !(kb2.traits() & 4)))
     return fail(DT_E_INVALID, "the trace-kernel build has no window mode");
   if (win && (bool)(kb.traits() & 8) != adaptive)
@@ -1007,149 +1049,55 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
     return fail(DT_E_INVALID, "no trace-kernel build covers the scene's features");
   if (!kb.resident) kb.resident = max_resident_waves(kb.ptr(), 64);
   const int64_t waves = kb.resident;
-  // Chunk items (spp > 64: C4's 256): every 64-sample chunk of a pixel is a queue item of its own, so
-  // a pixel's chunks run on different waves and a long pixel no longer holds one wave for four
-  // chunks in turn. The chunks store their sample colours; dt_chunk_sum_kernel adds each pixel's up
-  // in sample order after the trace launch(es) (dt_kernels.hip). For a rank's share of a split frame
-  // (world > 1): C4's world-8 shares 44.0 against 48.6 ms for the slowest (profiles/r06c_rb_*). A
-  // whole frame keeps one item per pixel: there the stored colours and the sum kernel cost C4 1.5%
-  // (1710 against 1736 Mpixel-samples/s with the chunks of a pixel dequeued together, r06b).
-  // DT_CHUNK_ITEMS=0 / 1 / 2 (2: the queue chunk-major, the tests' check) overrides the default.
-  const char* ci_env = getenv("DT_CHUNK_ITEMS");
-  int chunk_items = ci_env ? atoi(ci_env) : (P.world > 1 ? 1 : 0);
-  // (the build and, for a sky-item launch, its *_sky build must carry the code: trait bit 1)
-  if (!(kb.traits() & 2) || !(kb2.traits() & 2) || P.chunks < 2 || P.chunks > 255 || chunk_items < 0 ||
-      chunk_items > 2 || (double)P.n_items * P.chunks >= 4294967296.0)
-    chunk_items = 0;
-  // a window launch runs per-pixel items whatever DT_CHUNK_ITEMS says: the window's chunks in turn
-  // on one wave, the pixel's sums going on from the accumulator (dt_kernels.hip DT_WINDOW)
-  if (win) chunk_items = 0;
+  // chunk items: every 64-sample chunk of a pixel a queue item of its own (host_launch.h)
+  const int chunk_items = launch_chunk_items(P, kb.traits(), kb2.traits(), win != nullptr);
   P.chunk_items = chunk_items;
   P.chunk_lo = win ? win->chunk_lo : 0;
   P.chunk_hi = win ? win->chunk_hi : 0;
   hs.accum = win ? win->accum : nullptr;
-  if (adaptive) {
-    if ((double)P.n_items >= 4294967296.0) return fail(DT_E_INVALID, "adaptive window: more than 2^32 items");
-    if (P.n_items > sc->adapt_cap) {
-      HIPCHK(hipStreamSynchronize(st));
-      if (sc->d_adapt) (void)hipFree(sc->d_adapt);
-      sc->d_adapt = nullptr;
-      sc->adapt_cap = -1;
-      HIPCHK(hipMalloc((void**)&sc->d_adapt, adapt_layout(P.n_items).bytes));
-      sc->adapt_cap = P.n_items;
-    }
-    if (!sc->ev_sel) HIPCHK(hipEventCreate(&sc->ev_sel));
-    // (the offsets of the items of this launch: a smaller launch uses the head of a larger buffer)
-    const AdaptLayout L = adapt_layout(P.n_items);
-    P.adapt_begin = win->begin;
-    P.adapt_end = win->end;
-    P.adapt_min = win->min_samples;
-    P.adapt_thr2 = win->thr2;
-    P.act_waves = (int32_t)L.waves;
-    P.accum2 = win->accum2;
-    P.count = win->count;
-    P.act_n = (uint32_t*)sc->d_adapt;
-    P.act_list = (uint32_t*)(sc->d_adapt + L.list);
-    P.act_off = (uint32_t*)(sc->d_adapt + L.off);
-    P.act_mask = (unsigned long long*)(sc->d_adapt + L.mask);
-  }
-  if (chunk_items) {
-    const int64_t n_cols = P.n_items * (int64_t)P.spp * 3;
-    if (n_cols > sc->chunk_cols_cap) {
-      HIPCHK(hipStreamSynchronize(st));
-      if (sc->d_chunk_cols) (void)hipFree(sc->d_chunk_cols);
-      sc->d_chunk_cols = nullptr;
-      sc->chunk_cols_cap = 0;
-      HIPCHK(hipMalloc((void**)&sc->d_chunk_cols, sizeof(double) * (size_t)n_cols));
-      sc->chunk_cols_cap = n_cols;
-    }
-  }
-  hs.chunk_cols = chunk_items ? sc->d_chunk_cols : nullptr;
+  if (adaptive)
+    if (int rc = adaptive_setup(sc, P, *win, st)) return rc;
+  if (chunk_items) HIPCHK(reserve(sc->chunk_cols, sizeof(double) * (size_t)(P.n_items * (int64_t)P.spp * 3), st));
+  hs.chunk_cols = chunk_items ? sc->chunk_cols.as<double>() : nullptr;
   const int64_t n_queue = P.n_items * (chunk_items ? P.chunks : 1);
   // DT_ITEM_COSTS=1: every item's duration, for builds that record it (-DDT_ITEM_TIMES=2; others leave
   // the array as it is): dt_debug_item_costs
-  hs.item_cost = nullptr;
   if (getenv("DT_ITEM_COSTS") && getenv("DT_ITEM_COSTS")[0] == '1' && n_queue > 0) {
-    if (n_queue > sc->item_cost_cap) {
-      HIPCHK(hipStreamSynchronize(st));
-      if (sc->d_item_cost) (void)hipFree(sc->d_item_cost);
-      sc->d_item_cost = nullptr;
-      sc->item_cost_cap = 0;
-      HIPCHK(hipMalloc((void**)&sc->d_item_cost, sizeof(uint32_t) * (size_t)n_queue));
-      sc->item_cost_cap = n_queue;
-    }
-    HIPCHK(hipMemsetAsync(sc->d_item_cost, 0, sizeof(uint32_t) * (size_t)n_queue, st));
-    hs.item_cost = sc->d_item_cost;
+    HIPCHK(reserve(sc->item_cost, sizeof(uint32_t) * (size_t)n_queue, st));
+    HIPCHK(hipMemsetAsync(sc->item_cost.p, 0, sizeof(uint32_t) * (size_t)n_queue, st));
+    hs.item_cost = sc->item_cost.as<uint32_t>();
     sc->item_cost_n = n_queue;
   }
   int64_t grid = n_queue < waves ? n_queue : waves;
   if (grid < 1) grid = 1;
-  hs.dn_pool = nullptr;
   if (donate) {
-    if (grid > sc->dn_pool_waves) {
-      if (sc->d_dn_pool) {
-        HIPCHK(hipStreamSynchronize(st));
-        (void)hipFree(sc->d_dn_pool);
-        sc->d_dn_pool = nullptr;
-        sc->dn_pool_waves = 0;
-      }
-      HIPCHK(hipMalloc(&sc->d_dn_pool, (size_t)grid * DT_DN_POOL_REC * 32));
-      sc->dn_pool_waves = grid;
-    }
-    hs.dn_pool = sc->d_dn_pool;
+    HIPCHK(reserve(sc->dn_pool, (size_t)grid * DT_DN_POOL_REC * 32, st));
+    hs.dn_pool = sc->dn_pool.p;
   }
-  // two items per queue atomic pays when every wave takes many items (C3: ~500, +2%; C3's 1/8
-  // tile share: 63, its kernel -3.3%, profiles/r03x); with few (C2: ~30) the coarser tail costs
-  // more (-11%). DT_BATCH_ITEMS: the items per wave from which DT_BATCH_SIZE (2) are dequeued at once
+  // the launch policy (host_launch.h): items per queue atomic, queue segments, priority steps
   dtd::DParams PL = P;
-  const char* bi = getenv("DT_BATCH_ITEMS");
-  const char* bs = getenv("DT_BATCH_SIZE");
-  const int64_t batch_from = bi && atoi(bi) > 0 ? atoi(bi) : 32;
-  // Items of several 64-sample chunks (spp > 64: C4's 256) take one per atomic: their dequeues are
-  // rare already, and two consecutive pixels per wave cost C4 2.7% (profiles/r04zl_c4_batch.log)
-  // Three per atomic once every wave takes 256 or more (a whole C3 frame: ~405 per wave, +0.6%,
-  // profiles/r05q_ab_switches.txt); the 1/8 shares (~50 per wave) keep two, where three cost their
-  // bound 2.5% in round 4 (r04zj_ab_batch_policies.log)
-  PL.item_batch = n_queue >= batch_from * grid && (PL.chunks == 1 || (bs && atoi(bs) > 0))
-                      ? (bs && atoi(bs) > 0 ? atoi(bs) : (n_queue >= 256 * grid ? 3 : 2)) : 1;
-  // The queue in 8 contiguous segments, each with its own counter, wave b's home segment b % 8 (the
-  // XCD workgroup b runs on), a drained segment sending its waves on to the next (dt_kernels.hip),
-  // for a rank's share of a split frame of one-chunk items: C3's world-8 shares 4.46 against 4.54 ms
-  // (bound 0.933 against 0.921, profiles/r05zg_rank_balance_segs_default.log), C2's 0.569 against
-  // 0.591. A whole frame keeps one counter (C3 -1.4%, C4 -3.4%, C2 -0.5% with eight), and so do
-  // pixels of several chunks in one item (C4's world-8 shares 49.4 against 47.1 ms with eight,
-  // profiles/r05zi_*). Chunk items take eight: C4's slowest world-8 share 43.97 against 45.77 ms
-  // (profiles/r06c_rb_m1s8.log, r06c_rb_m1.log). DT_QUEUE_SEGS=<n> (1..8) overrides.
-  const char* qs = getenv("DT_QUEUE_SEGS");
-  PL.queue_segs = qs ? std::max(1, std::min(atoi(qs), DT_QSEG_MAX))
-                     : (PL.world > 1 && (PL.chunks == 1 || PL.chunk_items) ? DT_QSEG_MAX : 1);
-  // deep-cascade waves raise their priority (dt_kernels.hip, DT_PRIO_STEPS) when the frame is split
-  // over ranks, where one such wave bounds a rank's kernel, and after 2 DFS steps in whole frames of
-  // several pixels per wave (spp < 64: C2, whose frame is bounded by a column of 30x-mean glossy items,
-  // profiles/r06h_tail_c2.log): C2 +0.9%, C3 +0.1%, C4 -0.4% (so not there; profiles/r06o_ab.txt).
-  // DT_PRIO_STEPS=<n> overrides (0: off)
-  const char* ps = getenv("DT_PRIO_STEPS");
-  PL.prio_steps = ps ? atoi(ps) : (PL.world > 1 ? 8 : PL.ppw > 1 ? 2 : 0);
+  const LaunchPolicy pol = launch_policy(P, chunk_items, n_queue, grid);
+  PL.item_batch = pol.item_batch;
+  PL.queue_segs = pol.queue_segs;
+  PL.prio_steps = pol.prio_steps;
   // 1 spp (C5's cloud frames, n >= 244: nearly every pixel is sky): the trace kernel only flags
   // the missed pixels and dt_sky_miss_kernel marches their sky one pixel per lane, instead of the
   // wave marching each of its 64 pixels cooperatively in turn. DT_SKY_DEFER=0 disables it.
   const bool defer_on = !(getenv("DT_SKY_DEFER") && getenv("DT_SKY_DEFER")[0] == '0');
   const int64_t n_px = PL.n_items * PL.ppw;
   PL.sky_defer = 0;
-  hs.sky_miss = nullptr;
   // (not for a window launch: dt_sky_miss_kernel stores pixels, so the trace or sky-item launch
   // computes the sky and the accumulator takes it like any sample colour)
   if (defer_on && !win && PL.spp == 1 && PL.perlin_cloud && n_px > 0) {
-    if (n_px > sc->sky_miss_cap) {
-      HIPCHK(hipStreamSynchronize(st));
-      if (sc->d_sky_miss) (void)hipFree(sc->d_sky_miss);
-      sc->d_sky_miss = nullptr;
-      HIPCHK(hipMalloc((void**)&sc->d_sky_miss, n_px));
-      HIPCHK(hipMemsetAsync(sc->d_sky_miss, 0, n_px, st));
-      sc->sky_miss_cap = n_px;
+    bool grew = false;
+    HIPCHK(reserve(sc->sky_miss, (size_t)n_px, st, &grew));
+    // (new flags start at zero; later the kernel that reads them clears them)
+    if (grew && hipMemsetAsync(sc->sky_miss.p, 0, (size_t)n_px, st) != hipSuccess) {
+      sc->sky_miss.release();
+      return fail(DT_E_NO_DEVICE, "hipMemsetAsync(sky_miss)");
     }
     PL.sky_defer = 1;
-    hs.sky_miss = sc->d_sky_miss;
+    hs.sky_miss = sc->sky_miss.as<uint8_t>();
   }
   // DT_GENERAL_WALKS=1: every wave takes the exact reference-tree walks that axis-parallel rays
   // take (the tests' check of those rare, out-of-line paths against the product walks)
@@ -1162,41 +1110,10 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
   // dt_collect_stats adds the two up.
   const bool again = (kb.traits() & 1) && PL.perlin_cloud && !PL.sky_defer;
   PL.sky_again = again ? 1 : 0;
-  hs.again_list = nullptr;
-  hs.again_n = nullptr;
   if (again) {
-    if (!sc->d_stats2 || !sc->d_launch2 || !sc->h_launch2) {
-      // all three or none: allocated into temporaries, committed together, freed on a failure
-      unsigned long long* st2 = nullptr;
-      void* dl2 = nullptr;
-      uint8_t* hl2 = nullptr;
-      hipError_t e = hipMalloc((void**)&st2, sizeof(unsigned long long) * 2 * STATS2);
-      if (e == hipSuccess) e = hipMemsetAsync(st2, 0, sizeof(unsigned long long) * 2 * STATS2, st);
-      if (e == hipSuccess) e = hipMalloc(&dl2, 2 * dt_launch_size());
-      if (e == hipSuccess) e = hipHostMalloc((void**)&hl2, dt_launch_size(), hipHostMallocDefault);
-      if (e != hipSuccess) {
-        if (st2) (void)hipFree(st2);
-        if (dl2) (void)hipFree(dl2);
-        if (hl2) (void)hipHostFree(hl2);
-        return fail(DT_E_NO_DEVICE, std::string("sky-item launch buffers: ") + hipGetErrorString(e));
-      }
-      if (sc->d_stats2) (void)hipFree(sc->d_stats2);
-      if (sc->d_launch2) (void)hipFree(sc->d_launch2);
-      if (sc->h_launch2) (void)hipHostFree(sc->h_launch2);
-      sc->d_stats2 = st2;
-      sc->d_launch2 = dl2;
-      sc->h_launch2 = hl2;
-      sc->rec2_last[0].clear();
-      sc->rec2_last[1].clear();
-    }
-    if (n_queue > sc->again_cap) {   // (a listed item: its queue code, dt_kernels.hip)
-      HIPCHK(hipStreamSynchronize(st));
-      if (sc->d_again) (void)hipFree(sc->d_again);
-      sc->d_again = nullptr;
-      HIPCHK(hipMalloc((void**)&sc->d_again, sizeof(uint32_t) * n_queue));
-      sc->again_cap = n_queue;
-    }
-    hs.again_list = sc->d_again;
+    if (int rc = sky_item_buffers(sc, st)) return rc;
+    HIPCHK(reserve(sc->again, sizeof(uint32_t) * (size_t)n_queue, st));   // (a listed item: its queue code, dt_kernels.hip)
+    hs.again_list = sc->again.as<uint32_t>();
     hs.again_n = (unsigned int*)(sc->d_stats2 + par * STATS2 + ST_N + 1);
   }
   if (sc->d_stats2) {   // the sky-item counters of the next launch, whether or not it runs one
@@ -1211,38 +1128,12 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
   memcpy(sc->h_launch + dt_scene_struct_offset(), &hs, sizeof(hs));   // after every hs field is set
   memcpy(sc->h_launch + dt_params_struct_offset(), &PL, sizeof(PL));
   // the z table too only when it changed (the same for every frame of a scene's sky)
-  if (nz && (sc->zs_last.size() != nz || memcmp(sc->zs_last.data(), sc->h_zs, nz * sizeof(float)) != 0)) {
-    HIPCHK(hipMemcpyAsync(sc->d_zs, sc->h_zs, nz * sizeof(float), hipMemcpyHostToDevice, st));
-    sc->zs_last.assign(sc->h_zs, sc->h_zs + nz);
-  }
+  if (nz) HIPCHK(upload_if_changed(sc->zs.p, sc->h_zs, nz * sizeof(float), sc->zs_last, st));
   const size_t rec_size = dt_launch_size();
   uint8_t* const d_rec = (uint8_t*)sc->d_launch + par * rec_size;
-  if (sc->rec_last[par].size() != rec_size || memcmp(sc->rec_last[par].data(), sc->h_launch, rec_size) != 0) {
-    HIPCHK(hipMemcpyAsync(d_rec, sc->h_launch, rec_size, hipMemcpyHostToDevice, st));
-    sc->rec_last[par].assign(sc->h_launch, sc->h_launch + rec_size);
-  }
+  HIPCHK(upload_if_changed(d_rec, sc->h_launch, rec_size, sc->rec_last[par], st));
   uint8_t* const d_rec2 = sc->d_launch2 ? (uint8_t*)sc->d_launch2 + par * rec_size : nullptr;
-  if (again) {   // the second launch: the listed items, counters of its own
-    HScene hs2 = hs;
-    hs2.stats = sc->d_stats2 + par * STATS2;
-    hs2.queue = hs2.stats + ST_N;
-    hs2.clear0 = nullptr;   // the first launch cleared them
-    hs2.n_clear0 = 0;
-    hs2.clear1 = nullptr;
-    hs2.n_clear1 = 0;
-    dtd::DParams PL2 = PL;
-    PL2.sky_again = 2;
-    PL2.item_batch = 1;
-    PL2.queue_segs = 1;
-    PL2.prio_steps = 0;
-    memset(sc->h_launch2, 0, dt_launch_size());
-    memcpy(sc->h_launch2 + dt_scene_struct_offset(), &hs2, sizeof(hs2));
-    memcpy(sc->h_launch2 + dt_params_struct_offset(), &PL2, sizeof(PL2));
-    if (sc->rec2_last[par].size() != rec_size || memcmp(sc->rec2_last[par].data(), sc->h_launch2, rec_size) != 0) {
-      HIPCHK(hipMemcpyAsync(d_rec2, sc->h_launch2, rec_size, hipMemcpyHostToDevice, st));
-      sc->rec2_last[par].assign(sc->h_launch2, sc->h_launch2 + rec_size);
-    }
-  }
+  if (again) HIPCHK(sky_item_record(sc, hs, PL, par, d_rec2, st));   // the second launch: the listed items
   HIPCHK(hipEventRecord(sc->ev_copy, st));
   sc->copy_pending = true;
   HIPCHK(hipEventRecord(sc->ev0, st));
@@ -1250,20 +1141,13 @@ static int enqueue_render(dt_scene* sc, dtd::DParams P, const std::vector<float>
     // the selection writes the list this launch's queue runs over and its length, read by the trace
     // kernel as the sky-item launch reads *again_n: stream order, no host synchronisation
     if (P.n_items > 0) HIPCHK(dt_launch_adapt_select(d_rec, P.n_items, st));
-    else HIPCHK(hipMemsetAsync(sc->d_adapt, 0, sizeof(uint32_t), st));
+    else HIPCHK(hipMemsetAsync(sc->adapt.p, 0, sizeof(uint32_t), st));
     HIPCHK(hipEventRecord(sc->ev_sel, st));
   }
   HIPCHK(kb.launch(d_rec, out_dev, (int)grid, st));
   sc->last_parity = par;
   sc->n_launch++;
-  if (again) {
-    if (!kb2.resident) kb2.resident = max_resident_waves(kb2.ptr(), 64);
-    // a few listed items in the scenes that use it (room frames: none to a handful): 512 waves
-    // start and drain faster than a full persistent grid
-    int64_t g2 = grid < kb2.resident ? grid : kb2.resident;
-    g2 = g2 < 512 ? g2 : 512;
-    HIPCHK(kb2.launch(d_rec2, out_dev, (int)g2, st));
-  }
+  if (again) HIPCHK(sky_item_launch(kb2, d_rec2, out_dev, grid, st));
   sc->again_used = again;
   if (PL.sky_defer) HIPCHK(dt_launch_sky_miss(d_rec, out_dev, n_px, st));
   // chunk items: every pixel's sample colours added up in sample order, once both launches stored theirs
@@ -1321,7 +1205,7 @@ int dt_collect_stats(const dt_scene* sc_c, void* stream, dt_stats* stats)
   // an adaptive window launch of one-pixel items (spp >= 64): the pixels it traced are the selection's list
   if (sc->last_adaptive && P.spp >= 64) {
     uint32_t n_act = 0;
-    HIPCHK(hipMemcpy(&n_act, sc->d_adapt, sizeof(n_act), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&n_act, sc->adapt.p, sizeof(n_act), hipMemcpyDeviceToHost));
     px = n_act;
   }
   stats->pixels = px;
@@ -2183,11 +2067,11 @@ extern "C" int dt_debug_counters(const dt_scene* sc, uint64_t* out, int32_t n)
 extern "C" int64_t dt_debug_item_costs(const dt_scene* sc, uint32_t* out, int64_t n)
 {
   if (!sc || (n > 0 && !out) || n < 0) return (int64_t)fail(DT_E_INVALID, "bad arguments");
-  if (!sc->d_item_cost || sc->item_cost_n == 0) return 0;
+  if (!sc->item_cost.p || sc->item_cost_n == 0) return 0;
   const int64_t m = n < sc->item_cost_n ? n : sc->item_cost_n;
   if (m > 0) {
     if (hipDeviceSynchronize() != hipSuccess) return (int64_t)fail(DT_E_NO_DEVICE, "hipDeviceSynchronize");
-    if (hipMemcpy(out, sc->d_item_cost, sizeof(uint32_t) * (size_t)m, hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(out, sc->item_cost.p, sizeof(uint32_t) * (size_t)m, hipMemcpyDeviceToHost) != hipSuccess)
       return (int64_t)fail(DT_E_NO_DEVICE, "hipMemcpy");
   }
   return sc->item_cost_n;

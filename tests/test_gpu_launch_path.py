@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 
 KEYS = ("pixels", "samples", "rays", "shadow_rays", "sky_pixels", "nan_pixels", "tex_fetches",
         "stack_overflows", "uv_out_of_range", "glossy_exhausted", "reflect_errors")
+SCENES = [(240, 4, False), (1440, 4, True), (2000, 1, True)]
 
 
 def _globals(frame, res, spp):
@@ -36,18 +37,14 @@ def _fresh(b, g, frame, tile):
     return out.cpu().numpy(), {k: getattr(st, k) for k in KEYS}
 
 
-@pytest.mark.parametrize("built_frame,spp,sky", [(240, 4, False), (1440, 4, True), (2000, 1, True)])
-def test_reused_scene_matches_fresh_renders(cuda, built_frame, spp, sky):
-    """buildFinal(240): a still room frame (the still builds, their sky-item launch); 1440: a tunnel
-    frame with motion blur and sky (the z table); 2000: a 1-spp cloud frame (the deferred sky, whose
-    kernel reads the record's device copy). One scene object renders a sequence that changes the
-    frame number, the resolution, the sample count and the tiling and comes back to earlier
-    settings; each render must equal a fresh scene's, image and counters."""
+def _slab_tiling():
+    return dt.tiles(tile_w=8, tile_h=8, rank=1, world=4, layout=dt.DT_OUT_SLAB)
+
+
+def _check_sequence(built_frame, spp, sky, seq):
+    """One scene object renders seq (frame offset, resolution, samples, tiling); each render must
+    equal a fresh scene's, image and counters."""
     g0, b = _globals(built_frame, (160, 96), spp)
-    seq = [(0, (160, 96), spp, None), (0, (160, 96), spp, None), (8, (160, 96), spp, None),
-           (0, (160, 96), 4 * spp, None),
-           (0, (160, 96), spp, dt.tiles(tile_w=8, tile_h=8, rank=1, world=4, layout=dt.DT_OUT_SLAB)),
-           (0, (96, 64), spp, None), (0, (160, 96), spp, None), (8, (160, 96), spp, None)]
     scene = dt.Scene(b, g0)
     for i, (df, res, ns, tile) in enumerate(seq):
         g = dt.globals_default()
@@ -67,6 +64,30 @@ def test_reused_scene_matches_fresh_renders(cuda, built_frame, spp, sky):
         if sky and tile is None:
             assert st.sky_pixels > 0
     scene.close()
+
+
+@pytest.mark.parametrize("built_frame,spp,sky", SCENES)
+def test_reused_scene_matches_fresh_renders(cuda, built_frame, spp, sky):
+    """buildFinal(240): a still room frame (the still builds, their sky-item launch); 1440: a tunnel
+    frame with motion blur and sky (the z table); 2000: a 1-spp cloud frame (the deferred sky, whose
+    kernel reads the record's device copy). One scene object renders a sequence that changes the
+    frame number, the resolution, the sample count and the tiling and comes back to earlier
+    settings; each render must equal a fresh scene's, image and counters."""
+    _check_sequence(built_frame, spp, sky,
+                    [(0, (160, 96), spp, None), (0, (160, 96), spp, None), (8, (160, 96), spp, None),
+                     (0, (160, 96), 4 * spp, None), (0, (160, 96), spp, _slab_tiling()),
+                     (0, (96, 64), spp, None), (0, (160, 96), spp, None), (8, (160, 96), spp, None)])
+
+
+@pytest.mark.parametrize("built_frame,spp,sky", SCENES)
+def test_reused_scene_growing_buffers(cuda, built_frame, spp, sky):
+    """The sequence above starts at its largest size, so no lazily grown buffer of the scene (DESIGN.md
+    §7) is ever replaced under it. This one goes up and comes back: the second render needs larger
+    buffers than the first (the sky-item list on the frame-240 scene; the missed-pixel flags, zeroed
+    when reallocated, on the frame-2000 scene), the fourth and fifth use the head of them."""
+    _check_sequence(built_frame, spp, sky,
+                    [(0, (96, 64), spp, None), (0, (160, 96), spp, None), (0, (160, 96), 4 * spp, None),
+                     (0, (96, 64), spp, None), (0, (160, 96), spp, _slab_tiling()), (0, (160, 96), spp, None)])
 
 
 def test_two_scenes_alternating_streams(cuda):
