@@ -15,7 +15,7 @@ an error (there is no CPU path in this package).
 import ctypes
 
 from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT, DT_OUT_IMAGE, DT_OUT_SLAB, AccelInfo, BVHNode, Camera, DenoiseParams, DenoiseVarParams, DTError, Globals, SceneDesc,
-                   Stats, TemporalParams, Tiles, UpsampleParams, check, lib)
+                   OcclusionParams, Stats, TemporalParams, Tiles, UpsampleParams, check, lib)
 
 __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_scene", "Scene",
            "render", "render_sky", "renderImage", "renderImageCloud", "write_ppm", "DATA_DIR",
@@ -29,7 +29,9 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "Camera", "camera", "TemporalParams", "temporal_params_default", "reproject", "TemporalAccumulator",
            "trace_rays", "rays_occluded", "RAY_PLANES",
            "render_mattes", "matte_mask", "shape_groups", "MATTE_PLANES",
-           "UpsampleParams", "upsample_params_default", "upsample", "low_res_globals"]
+           "UpsampleParams", "upsample_params_default", "upsample", "low_res_globals",
+           "OcclusionParams", "occlusion_params_default", "render_occlusion", "occlusion_ao_ray", "occlusion_light_ray",
+           "occlusion_images"]
 
 
 def globals_default():
@@ -289,6 +291,102 @@ def render_features(scene, g, frame, n_samples=None, tile=None, stream=None, pla
     check(lib.dt_render_features(scene.handle, ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None, n,
                                  ctypes.byref(f), side or 0, ctypes.c_void_p(stream) if stream else None,
                                  ctypes.byref(st)), "dt_render_features")
+    return out
+
+
+def occlusion_params_default():
+    """dt_occlusion_params_default: ao_rays 4, ao_radius 1.0 (one world unit), no lights"""
+    p = OcclusionParams()
+    lib.dt_occlusion_params_default(ctypes.byref(p))
+    return p
+
+
+def occlusion_ao_ray(g, frame, pixel, sample, r, ao_radius, point, normal):
+    """The direction of ambient-occlusion probe r of sample `sample` of pixel `pixel` (y*xRes + x) from a hit
+    with the fixNorm'ed normal `normal` (include/dt.h dt_occlusion_ao_ray), as a tuple of 3 floats"""
+    D3 = ctypes.c_double * 3
+    out = D3()
+    check(lib.dt_occlusion_ao_ray(g.seed, int(frame), int(pixel), int(sample), int(r), float(ao_radius),
+                                  D3(*[float(v) for v in point]), D3(*[float(v) for v in normal]), out),
+          "dt_occlusion_ao_ray")
+    return tuple(out)
+
+
+def occlusion_light_ray(g, frame, pixel, sample, j, light, point):
+    """The direction of the probe of light slot j towards `light` (a LightDesc) from `point`
+    (include/dt.h dt_occlusion_light_ray), as a tuple of 3 floats"""
+    D3 = ctypes.c_double * 3
+    out = D3()
+    check(lib.dt_occlusion_light_ray(g.seed, int(frame), int(pixel), int(sample), int(j), ctypes.byref(light),
+                                     D3(*[float(v) for v in point]), out), "dt_occlusion_light_ray")
+    return tuple(out)
+
+
+def render_occlusion(scene, g, frame, n_samples=None, ao_rays=4, ao_radius=None, lights=(), tile=None, stream=None,
+                     out=None):
+    """Occlusion feature buffers of the leading n_samples samples (None: spp) of every owned pixel
+    (include/dt.h dt_render_occlusion): (dict(ao=..., light=...), stats). `ao` (one float32 per pixel, entry q as
+    render_features' depth; only with ao_rays > 0) is the fraction of ambient-occlusion probes that found the
+    ball of radius ao_radius resting on the surface visible (None: occlusion_params_default's constant, one
+    world unit: a property of the shipped scenes' human scale, so a scene in other units needs ao_radius set
+    explicitly); `light`
+    (len(lights) per pixel, entry len(lights)*q + j; only with lights) the fraction of samples from which light
+    lights[j] of the scene was visible. Both are premultiplied by coverage. `out`: a dict of the planes to write
+    into, all CUDA torch tensors or all host arrays (numpy, CPU tensors), where only owned pixels are written;
+    without it, new zeroed CUDA tensors."""
+    from ._lib import Occlusion
+    n1 = accum_doubles(g, tile) // 3
+    n = _spp(g) if n_samples is None else int(n_samples)
+    p = OcclusionParams()
+    p.ao_rays, p.n_lights = int(ao_rays), len(lights)
+    if len(lights) > len(p.lights):
+        raise DTError("render_occlusion: %d lights, at most %d" % (len(lights), len(p.lights)))
+    for j, l in enumerate(lights):
+        p.lights[j] = int(l)
+    if p.ao_rays > 0:
+        p.ao_radius = occlusion_params_default().ao_radius if ao_radius is None else float(ao_radius)
+    need = {"ao": n1, "light": n1 * len(lights)}
+    if out is None:
+        import torch
+        out = {}
+        if p.ao_rays > 0:
+            out["ao"] = torch.zeros(n1, dtype=torch.float32, device="cuda")
+        if lights:
+            out["light"] = torch.zeros(n1 * len(lights), dtype=torch.float32, device="cuda")
+    o = Occlusion()
+    side = None
+    for name, a in out.items():
+        if name not in need:
+            raise DTError("render_occlusion: unknown plane %r" % (name,))
+        ptr, dev = _ptr(a)
+        have = a.numel() if hasattr(a, "numel") else a.size
+        if have != need[name] and need[name] > 0:
+            raise DTError("render_occlusion: plane %s holds %d elements, (g, tile, lights) need %d"
+                          % (name, have, need[name]))
+        if side is not None and dev != side:
+            raise DTError("render_occlusion: the planes must all be on the same side")
+        side = dev
+        setattr(o, name, ptr)
+    st = Stats()
+    check(lib.dt_render_occlusion(scene.handle, ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None, n,
+                                  ctypes.byref(p), ctypes.byref(o), side or 0,
+                                  ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)), "dt_render_occlusion")
+    return out, st
+
+
+def occlusion_images(g, planes):
+    """The images `dtrender --occlusion P` writes, as float32 arrays for write_png: {"ao": ..., "light<j>": ...},
+    each plane times 255 in all three channels. planes: full-frame image-layout planes of render_occlusion
+    (numpy)."""
+    import numpy as np
+    n1 = g.xRes * g.yRes
+    out = {}
+    if "ao" in planes:
+        out["ao"] = np.repeat(np.asarray(planes["ao"], np.float32).reshape(n1) * np.float32(255), 3)
+    if "light" in planes:
+        v = np.asarray(planes["light"], np.float32).reshape(n1, -1)
+        for j in range(v.shape[1]):
+            out["light%d" % j] = np.repeat(np.ascontiguousarray(v[:, j]) * np.float32(255), 3)
     return out
 
 
@@ -982,6 +1080,14 @@ class Progressive:
         return render_features(self.scene, self.g, self.frame, self.samples_done, self.tile, planes=planes,
                                specular_bounces=specular_bounces)
 
+    def occlusion(self, ao_rays=4, ao_radius=None, lights=()):
+        """The occlusion feature buffers of the samples rendered so far (render_occlusion of the leading
+        samples_done samples of every owned pixel, in the accumulator's layout), as features() covers them:
+        (planes, stats)."""
+        if self.samples_done < 1:
+            raise DTError("Progressive.occlusion: no window rendered yet")
+        return render_occlusion(self.scene, self.g, self.frame, self.samples_done, ao_rays, ao_radius, lights, self.tile)
+
     def mattes(self, groups=None, layers=4):
         """The object mattes of the samples rendered so far (render_mattes of the leading samples_done
         samples of every owned pixel, in the accumulator's layout), as features() covers them."""
@@ -1292,7 +1398,8 @@ def _render_image_upsampled(filename, frame, built, g, how, denoise, guide_bounc
 
 
 def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progressive=None, adaptive=None,
-                features=None, denoise=None, upsample=None, guide_bounces=0):
+                features=None, denoise=None, upsample=None, guide_bounces=0, occlusion=None, ao_rays=4,
+                ao_radius=None, occlusion_lights=()):
     """render_final_project.cpp:965: build (sceneBuilder names a scene.h builder), render the
     frame on the current GPU, write the PPM. Returns (image, stats). progressive=callback renders in
     one-chunk sample windows (Progressive) and calls callback(image, samples_done) with the resolved
@@ -1315,15 +1422,18 @@ def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progr
     progressive, adaptive, features or denoising by variance (DTError). Without upsample nothing changes.
     guide_bounces=K (1..8) takes the specular-path feature buffers (render_features(specular_bounces=K)) for
     the feature images, both denoisers and the upsampler, as `dtrender --guide-bounces K` does: the guides
-    then describe what mirrors and glass show. With 0 nothing changes."""
+    then describe what mirrors and glass show. With 0 nothing changes.
+    occlusion=prefix also writes the occlusion feature images of all spp samples (render_occlusion with ao_rays,
+    ao_radius and occlusion_lights; occlusion_images), prefix.ao.png and prefix.light<j>.png, as
+    `dtrender --occlusion` does; not with upsample (DTError). The frame file's bytes are unchanged."""
     import numpy as np
     by_variance = isinstance(denoise, DenoiseVarParams) or (isinstance(denoise, str) and denoise == "variance")
     if by_variance and adaptive is None:
         raise DTError("renderImage: denoise by variance needs adaptive=tol (the sums of squares are adaptive sampling's)")
     g = g if g is not None else globals_default()
-    if upsample and (progressive is not None or adaptive is not None or features or by_variance):
+    if upsample and (progressive is not None or adaptive is not None or features or by_variance or occlusion):
         raise DTError("renderImage: upsample renders one low-resolution frame: not with progressive, adaptive, "
-                      "features or denoising by variance")
+                      "features, occlusion or denoising by variance")
     built = build_scene(sceneBuilder, frame if builder_frame is None else builder_frame, g)
     if upsample:
         return _render_image_upsampled(filename, frame, built, g, upsample, denoise, guide_bounces)
@@ -1351,6 +1461,10 @@ def renderImage(filename, frame, sceneBuilder, g=None, builder_frame=None, progr
                                  specular_bounces=guide_bounces)
         for name, v in feature_images(g, {k: t.cpu().numpy() for k, t in planes.items()}).items():
             write_png("%s.%s.png" % (features, name), g, v)
+    if occlusion:
+        planes, _ = render_occlusion(scene, g, frame, ao_rays=ao_rays, ao_radius=ao_radius, lights=occlusion_lights)
+        for name, v in occlusion_images(g, {k: t.cpu().numpy() for k, t in planes.items()}).items():
+            write_png("%s.%s.png" % (occlusion, name), g, v)
     if denoise and filename:
         import torch
         n = p.samples_done if adaptive is not None else None

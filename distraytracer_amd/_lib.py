@@ -110,6 +110,20 @@ class Mattes(ctypes.Structure):
     _fields_ = [("id", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("distinct", ctypes.c_void_p)]
 
 
+class OcclusionParams(ctypes.Structure):
+    """dt_occlusion_params: ao_rays 0..16 probes per hitting sample, ao_radius (finite, > 0, world units), n_lights
+    0..8 and their indices into the scene's lights"""
+    _fields_ = [("ao_rays", c_int32), ("ao_radius", c_float), ("n_lights", c_int32), ("lights", c_int32 * 8)]
+
+
+class Occlusion(ctypes.Structure):
+    """dt_occlusion: the planes of dt_render_occlusion (a null pointer: not wanted)"""
+    _fields_ = [("ao", ctypes.c_void_p), ("light", ctypes.c_void_p)]
+
+
+DT_OCCL_MAX_AO_RAYS = 16
+DT_OCCL_MAX_LIGHTS = 8
+DT_OCCL_TRIES = 16
 DT_MATTE_TABLE = 64       # distinct groups a pixel's histogram holds
 DT_MATTE_MAX_LAYERS = 8
 
@@ -188,7 +202,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_camera_get", "dt_temporal_params_default", "dt_reproject",
            "dt_trace_rays", "dt_rays_occluded", "dt_render_mattes", "dt_matte_mask",
            "dt_upsample_params_default", "dt_upsample",
-           "dt_guide_bounce", "dt_render_features_path"]
+           "dt_guide_bounce", "dt_render_features_path",
+           "dt_occlusion_params_default", "dt_render_occlusion", "dt_occlusion_ao_ray", "dt_occlusion_light_ray"]
 
 
 class DTError(RuntimeError):
@@ -273,6 +288,13 @@ def _load():
                                       P(c_double), P(c_double)]),
         "dt_render_features_path": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, c_int32,
                                               P(Features), ctypes.c_void_p, c_int32, ctypes.c_void_p, P(Stats)]),
+        "dt_occlusion_params_default": (None, [P(OcclusionParams)]),
+        "dt_render_occlusion": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, P(OcclusionParams),
+                                          P(Occlusion), c_int32, ctypes.c_void_p, P(Stats)]),
+        "dt_occlusion_ao_ray": (c_int32, [ctypes.c_uint32, c_int32, ctypes.c_uint32, ctypes.c_uint32, c_int32, c_float,
+                                          P(c_double), P(c_double), P(c_double)]),
+        "dt_occlusion_light_ray": (c_int32, [ctypes.c_uint32, c_int32, ctypes.c_uint32, ctypes.c_uint32, c_int32,
+                                             P(LightDesc), P(c_double), P(c_double)]),
         "dt_trace_rays": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p, P(RayHits),
                                     c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_rays_occluded": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p,

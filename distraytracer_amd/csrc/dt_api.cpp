@@ -15,6 +15,7 @@
 
 #include "dt_adapt.h"
 #include "dt_guide.h"
+#include "dt_occl.h"
 #include "host_internal.h"
 #include "host_launch.h"
 
@@ -77,6 +78,9 @@ extern "C" hipError_t dt_launch_mattes(const void* dev_launch, int n_samples, co
                                        float* weight, int32_t* distinct, unsigned long long* overflow, int grid,
                                        hipStream_t stream);
 extern "C" const void* dt_mattes_kernel_ptr(void);
+extern "C" hipError_t dt_launch_occlusion(const void* dev_launch, int n_samples, int ao_rays, float ao_radius, int n_lights,
+                                          const void* lights, float* ao, float* light, int grid, hipStream_t stream);
+extern "C" const void* dt_occlusion_kernel_ptr(void);
 
 namespace {
 
@@ -1890,6 +1894,122 @@ int dt_rays_occluded(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, 
     stats->shadow_rays = aux.h[ST_SHADOW];
     stats->kernel_ms = aux.kernel_ms;
   }
+  return DT_OK;
+}
+
+// Occlusion feature buffers: dt_occlusion_kernel over the samples 0 .. n_samples-1 of every owned pixel. As
+// dt_render_features it shares only the scene's primary-ray lists. Every argument check, the light indices
+// included, comes before any device work. The lights' records (dt_occl.h OcclLight, from the scene's flattened
+// lights) travel with the launch.
+void dt_occlusion_params_default(dt_occlusion_params* p)
+{
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->ao_rays = 4;
+  p->ao_radius = 1.0f;   // one world unit (include/dt.h: a choice, not a measurement)
+}
+
+int dt_render_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t n_samples,
+                        const dt_occlusion_params* params, const dt_occlusion* out, int32_t out_on_device, void* stream,
+                        dt_stats* stats)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  const std::string who = "dt_render_occlusion: ";
+  if (!sc) return fail(DT_E_INVALID, who + "null scene");
+  if (!g) return fail(DT_E_INVALID, who + "null globals");
+  if (!params) return fail(DT_E_INVALID, who + "null params");
+  if (!out) return fail(DT_E_INVALID, who + "null out");
+  if (int rc = dt_window_check(g, 0, n_samples)) return fail(rc, who + "n_samples: " + g_err);
+  if (params->ao_rays < 0 || params->ao_rays > DT_OCCL_MAX_AO_RAYS)
+    return fail(DT_E_INVALID, who + "ao_rays " + std::to_string(params->ao_rays) + " outside 0.." +
+                                  std::to_string(DT_OCCL_MAX_AO_RAYS));
+  if (params->n_lights < 0 || params->n_lights > DT_OCCL_MAX_LIGHTS)
+    return fail(DT_E_INVALID, who + "n_lights " + std::to_string(params->n_lights) + " outside 0.." +
+                                  std::to_string(DT_OCCL_MAX_LIGHTS));
+  if (params->ao_rays > 0 && !(std::isfinite(params->ao_radius) && params->ao_radius > 0))
+    return fail(DT_E_INVALID, who + "ao_radius must be finite and > 0");
+  if (out->ao && params->ao_rays == 0) return fail(DT_E_INVALID, who + "out->ao given with ao_rays == 0");
+  if (out->light && params->n_lights == 0) return fail(DT_E_INVALID, who + "out->light given with n_lights == 0");
+  if (!out->ao && !out->light) return fail(DT_E_INVALID, who + "out wants no plane (every pointer is null)");
+  // (the scene is looked at only from here on)
+  const int32_t scene_lights = (int32_t)sc->flat.lights.size();
+  for (int32_t j = 0; j < params->n_lights; ++j)
+    if (params->lights[j] < 0 || params->lights[j] >= scene_lights)
+      return fail(DT_E_INVALID, who + "lights[" + std::to_string(j) + "] = " + std::to_string(params->lights[j]) +
+                                    ", the scene has " + std::to_string(scene_lights) + " lights");
+  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, who + "scenes with a RectPrismWithCylinder");
+  // a plane that is not wanted costs no probes
+  const int ao_rays = out->ao ? params->ao_rays : 0, n_lights = out->light ? params->n_lights : 0;
+  dtd::DParams P;
+  std::vector<float> zs;
+  if (int rc = prepare_render(sc, g, frame, tiles, P, zs)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, true)) return rc;
+  dtd::OcclLight recs[DT_OCCL_MAX_LIGHTS];
+  memset(recs, 0, sizeof(recs));
+  for (int j = 0; j < n_lights; ++j) {
+    const dtd::DLight& L = sc->flat.lights[params->lights[j]];
+    dtd::OcclLight& o = recs[j];
+    o.type = L.type;
+    o.shape_index = L.shape_index;
+    o.radius = L.radius;
+    for (int k = 0; k < 3; ++k) { o.center[k] = L.center[k]; o.A[k] = L.A[k]; o.B[k] = L.B[k]; o.D[k] = L.D[k]; }
+  }
+  void* dlights = nullptr;
+  if (n_lights > 0)
+    if (int rc = aux.plane(recs, sizeof(recs), false, true, false, &dlights)) return rc;
+  // the planes, staged as dt_render_features stages its own
+  const size_t n1 = P.layout == DT_OUT_SLAB ? (size_t)(P.n_owned_tiles * P.tw * P.th) : (size_t)P.xRes * P.yRes;
+  void *dao = nullptr, *dlight = nullptr;
+  if (int rc = aux.plane(out->ao, n1 * sizeof(float), out_on_device, true, true, &dao)) return rc;
+  if (int rc = aux.plane(out->light, n1 * (size_t)params->n_lights * sizeof(float), out_on_device, true, true, &dlight))
+    return rc;
+  static int resident = 0;
+  const int grid = aux_grid(dt_occlusion_kernel_ptr(), resident, P.n_items);
+  if (int rc = aux.start()) return rc;
+  if (int rc = aux.finish(dt_launch_occlusion(aux.launch, n_samples, ao_rays, params->ao_radius, n_lights, dlights,
+                                              (float*)dao, (float*)dlight, grid, aux.st)))
+    return rc;
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+    stats->pixels = owned_pixels(P);
+    stats->samples = stats->pixels * (uint64_t)n_samples;
+    stats->rays = stats->samples;
+    stats->shadow_rays = aux.h[ST_SHADOW];
+    stats->prism_norm_fallback = aux.h[ST_PRISM];
+    stats->kernel_ms = aux.kernel_ms;
+  }
+  return DT_OK;
+}
+
+// The two probe generators of dt_render_occlusion for one hit (dt_occl.h), for tests and callers.
+int dt_occlusion_ao_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint32_t sample, int32_t r, float ao_radius,
+                        const double p[3], const double n[3], double dir[3])
+{
+  if (!p || !n || !dir) return fail(DT_E_INVALID, "dt_occlusion_ao_ray: null argument");
+  if (r < 0 || r >= DT_OCCL_MAX_AO_RAYS)
+    return fail(DT_E_INVALID, "dt_occlusion_ao_ray: r " + std::to_string(r) + " outside 0.." +
+                                  std::to_string(DT_OCCL_MAX_AO_RAYS - 1));
+  const dtm::V3 d = dtd::occl_ao_dir(seed, frame, pixel, sample, r, ao_radius, dtm::v3a(n));
+  dir[0] = d.x; dir[1] = d.y; dir[2] = d.z;
+  return DT_OK;
+}
+
+int dt_occlusion_light_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint32_t sample, int32_t j,
+                           const dt_light_desc* light, const double p[3], double dir[3])
+{
+  if (!light || !p || !dir) return fail(DT_E_INVALID, "dt_occlusion_light_ray: null argument");
+  if (j < 0 || j >= DT_OCCL_MAX_LIGHTS)
+    return fail(DT_E_INVALID, "dt_occlusion_light_ray: j " + std::to_string(j) + " outside 0.." +
+                                  std::to_string(DT_OCCL_MAX_LIGHTS - 1));
+  dtd::OcclLight o;
+  memset(&o, 0, sizeof(o));
+  o.type = light->type;
+  o.shape_index = light->shape_index;
+  o.radius = (double)light->radius;
+  for (int k = 0; k < 3; ++k) { o.center[k] = light->center[k]; o.A[k] = light->A[k]; o.B[k] = light->B[k]; o.D[k] = light->D[k]; }
+  const dtm::V3 d = dtd::occl_light_dir(seed, frame, pixel, sample, j, o, dtm::v3a(p));
+  dir[0] = d.x; dir[1] = d.y; dir[2] = d.z;
   return DT_OK;
 }
 

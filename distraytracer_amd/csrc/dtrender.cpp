@@ -43,6 +43,11 @@
 //                     planes at both resolutions, and dt_upsample with the default parameters on the device,
 //                     written to <stem>.upsampled.<ext> beside the frame at the full resolution. The frame
 //                     file is the same bytes as without the flag.
+//   --occlusion PREFIX  after the frame, the occlusion feature buffers of all spp samples (dt_render_occlusion)
+//                     as grey 8-bit PNGs, value*255: PREFIX.ao.png (--ao-rays K probes per hitting sample,
+//                     0..16, default 4; --ao-radius R world units, default 1.0) and PREFIX.light<j>.png for
+//                     the j-th light of --occlusion-lights 0,1,... (indices into the scene's lights, at most 8;
+//                     default none). The frame file is the same bytes as without the flag.
 //   --guide-bounces K the feature buffers of --features, --denoise, --denoise-variance and --upsample are the
 //                     specular-path ones (dt_render_features_path, K = 1..8 perfect specular bounces): the
 //                     guides describe what mirrors and glass show, not the reflector. Without it (or with 0)
@@ -203,6 +208,9 @@ int main(int argc, char** argv)
   double adaptive = -1.0;
   std::string counts_file, features_prefix, mattes_prefix;
   int matte_layers = 4, nogloss = 0;
+  std::string occl_prefix, occl_lights;
+  int ao_rays = 4;
+  double ao_radius = -1.0;   // < 0: dt_occlusion_params_default's
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     if (a == "--out" && i + 1 < argc) out = argv[++i];
@@ -224,6 +232,10 @@ int main(int argc, char** argv)
     else if (a == "--upsample" && i + 1 < argc) upsample = atoi(argv[++i]);
     else if (a == "--guide-bounces" && i + 1 < argc) guide_bounces = atoi(argv[++i]);
     else if (a == "--nogloss") nogloss = 1;
+    else if (a == "--occlusion" && i + 1 < argc) occl_prefix = argv[++i];
+    else if (a == "--ao-rays" && i + 1 < argc) ao_rays = atoi(argv[++i]);
+    else if (a == "--ao-radius" && i + 1 < argc) ao_radius = atof(argv[++i]);
+    else if (a == "--occlusion-lights" && i + 1 < argc) occl_lights = argv[++i];
   }
   if (guide_bounces < 0 || guide_bounces > DT_GUIDE_MAX_BOUNCES) {
     fprintf(stderr, "usage: --guide-bounces K needs K in 0..%d\n", DT_GUIDE_MAX_BOUNCES);
@@ -482,6 +494,44 @@ int main(int argc, char** argv)
     if (rc) return die("dt_write_png (mattes)", rc);
     printf("mattes: %llu pixels, %d groups, %d layers, %llu overflow pixels in %.3f ms (kernel) -> %s\n",
            (unsigned long long)mst.pixels, (int)seen.size(), L, (unsigned long long)over, mst.kernel_ms, pf.c_str());
+  }
+  if (!occl_prefix.empty()) {
+    dt_occlusion_params op;
+    dt_occlusion_params_default(&op);
+    op.ao_rays = ao_rays;
+    for (const char* c = occl_lights.c_str(); *c;) {
+      char* end = nullptr;
+      const long l = strtol(c, &end, 10);
+      if (end == c || op.n_lights >= DT_OCCL_MAX_LIGHTS) {
+        fprintf(stderr, "usage: --occlusion-lights takes at most %d comma-separated light indices\n", DT_OCCL_MAX_LIGHTS);
+        return 2;
+      }
+      op.lights[op.n_lights++] = (int32_t)l;
+      c = *end == ',' ? end + 1 : end;
+    }
+    if (ao_radius >= 0.0) op.ao_radius = (float)ao_radius;
+    const int n = (int)sqrt((double)g.antialias_samples);
+    const size_t n_px = (size_t)g.xRes * g.yRes;
+    std::vector<float> ao(n_px, 0.0f), lv(n_px * (size_t)(op.n_lights > 0 ? op.n_lights : 1), 0.0f), pix(3 * n_px);
+    dt_occlusion o;
+    memset(&o, 0, sizeof o);
+    if (op.ao_rays != 0) o.ao = ao.data();
+    if (op.n_lights > 0) o.light = lv.data();
+    dt_stats ost;
+    rc = dt_render_occlusion(s, &g, frame, nullptr, n * n, &op, &o, 0, nullptr, &ost);
+    if (rc) return die("dt_render_occlusion", rc);
+    for (int plane = o.ao ? -1 : 0; plane < op.n_lights; ++plane) {
+      for (size_t q = 0; q < n_px; ++q) {
+        const float v = (plane < 0 ? ao[q] : lv[(size_t)op.n_lights * q + plane]) * 255.0f;
+        pix[3 * q] = pix[3 * q + 1] = pix[3 * q + 2] = v;
+      }
+      const std::string pf = occl_prefix + (plane < 0 ? std::string(".ao") : ".light" + std::to_string(plane)) + ".png";
+      rc = dt_write_png(pf.c_str(), g.xRes, g.yRes, pix.data());
+      if (rc) return die("dt_write_png (occlusion)", rc);
+    }
+    printf("occlusion: %llu pixels, %llu probes (%d ao rays of radius %g, %d lights) in %.3f ms (kernel) -> %s.*.png\n",
+           (unsigned long long)ost.pixels, (unsigned long long)ost.shadow_rays, op.ao_rays, (double)op.ao_radius,
+           op.n_lights, ost.kernel_ms, occl_prefix.c_str());
   }
   double msps = st.samples / (st.kernel_ms * 1e-3) / 1e6;
   printf("Rendered %s frame %d: %dx%d, %d spp, depth %d in %.2f ms (kernel, %.1f Mpixel-samples/s) -> %s\n",

@@ -67,6 +67,9 @@ extern "C" {
  *    its dt_upsample_params -- guided upsampling of previews) */
 /* (still 8, new exports only, no struct changed: dt_guide_bounce, dt_render_features_path -- specular-path
  *    feature buffers: guides seen through mirrors and glass) */
+/* (still 8, new exports and two new structs, no struct changed: dt_occlusion_params_default,
+ *    dt_render_occlusion and its dt_occlusion_params and dt_occlusion, dt_occlusion_ao_ray,
+ *    dt_occlusion_light_ray -- occlusion feature buffers: ambient occlusion and per-light visibility) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -685,6 +688,94 @@ int dt_trace_rays(const dt_scene* s, const dt_globals* g, int64_t n_rays, const 
 int dt_rays_occluded(const dt_scene* s, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
                      const int32_t* skip_shape /* optional, n_rays; -1: none */, uint8_t* occluded,
                      int32_t on_device, void* stream, dt_stats* stats);
+
+/* ---- occlusion feature buffers: ambient occlusion and per-light visibility ----
+ * No reference counterpart. The guides of dt_render_features say what a surface is; these say how exposed it
+ * is: an ambient-occlusion plane and one visibility ("shadow") plane per chosen light, at the render's own
+ * samples. The standard compositor companions of the feature planes and the mattes; a guide that tells a
+ * soft shadow on a flat, single-coloured floor from noise.
+ *
+ * Samples, rays, slots q, layouts, sides, staging, the n_samples window rule and "only owned pixels are
+ * written" are exactly dt_render_features's. Per sample i of pixel (x, y) the primary ray is traced to its
+ * closest hit exactly as dt_render_features traces it (shift 0 on every frame). A miss adds nothing; a hit
+ * gives p = eye_sample + (double)t * ray and n = fixNorm(normalized(ray), getNorm(p)). H counts the hitting
+ * samples of the pixel.
+ *
+ * RNG: Philox4x32-10, key (g->seed, (uint32_t)frame), counter (pixel = y*xRes + x, sample = i, node = 0,
+ * (purpose << 24) | sub) with the two purposes P_AO = 6 and P_OLIGHT = 7; the render's own draws at node 0
+ * use purposes 1..5, so no stream is shared. u01(w0, w1) is the render's: ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.
+ *
+ * Ball point v(purpose, base): for a = 0 .. DT_OCCL_TRIES-1 draw the words o at sub = base*16 + a,
+ *   x = (double)o[0] * 2^-31 - 1.0, y and z likewise from o[1], o[2] (all exact in f64),
+ *   s = (x*x + y*y) + z*z;
+ * the first a with s <= 1.0 gives v = (x, y, z); none: v = (0, 0, 0). No normalisation, no libm.
+ *
+ * Ambient occlusion: probe r = 0 .. ao_rays-1 of a hitting sample has v = v(P_AO, r) and
+ *   dir[k] = R * (n[k] + v[k]),  R = (double)ao_radius                (each operation one rounded f64 one):
+ * "is a point of the ball of radius R resting on the surface at p visible from p?", answered exactly as
+ * dt_rays_occluded(start = p, dir, skip_shape = -1) answers it, its void-ray rule included (v = -n gives a
+ * zero dir: not traced, not occluded). With V the unoccluded probes of the pixel,
+ *   ao[q] = (float)((double)V / ((double)n_samples * (double)ao_rays)),
+ * premultiplied by coverage like albedo and normal (sky: 0; divide by the coverage plane to un-premultiply).
+ *
+ * Light visibility: slot j selects light L = lights[j] of the scene, with the target T
+ *   DT_LIGHT_POINT:  T = center
+ *   DT_LIGHT_RECT:   the words o at (P_OLIGHT, sub = j*16), u0 = u01(o[0], o[1]), u1 = u01(o[2], o[3]),
+ *                    T = (A + u0*(B-A)) + u1*(D-A)
+ *   DT_LIGHT_SPHERE: T = center + (double)radius * v(P_OLIGHT, j): a point of the light's volume (the light's
+ *                    own shape is skipped, so no far-side rule is needed)
+ * and dir = T - p, answered as dt_rays_occluded(start = p, dir, skip_shape = L.shape_index). There is no
+ * facing test: a surface turned away from the light is shadowed by its own geometry through the 1e-3
+ * offset, as in the light loop. With V_j the unoccluded probes,
+ *   light[n_lights*q + j] = (float)((double)V_j / (double)n_samples).
+ * All sums are integers: the planes do not depend on any summation order.
+ *
+ * First hits only: a probe starts on the first surface a sample sees, a mirror's or a pane's own, and a
+ * probe does not pass through glass (a glass shape occludes, as in the light loop's shadow test).
+ *
+ * stats (optional): pixels, samples = rays = pixels * n_samples, shadow_rays = the probes tested (the
+ * non-void ones), prism_norm_fallback, kernel_ms; everything else 0. A plane that is not wanted (NULL while
+ * ao_rays > 0 or n_lights > 0) costs no probes: its probes are neither generated nor counted.
+ * Errors, with a dt_last_error starting "dt_render_occlusion: " and naming the argument: DT_E_INVALID for a
+ * null scene, globals, params or out, a bad n_samples, ao_rays outside 0..DT_OCCL_MAX_AO_RAYS, n_lights
+ * outside 0..DT_OCCL_MAX_LIGHTS, a non-finite or non-positive ao_radius while ao_rays > 0, a light index
+ * outside the scene, out->ao given with ao_rays == 0, out->light given with n_lights == 0, every plane
+ * NULL; DT_E_UNSUPPORTED for a scene with a RectPrismWithCylinder; all before any device work.
+ * Synchronous, with a launch record, counters and events of its own; it shares only the scene's
+ * primary-ray lists, and a render of the scene afterwards is unaffected.
+ *
+ * dt_occlusion_params_default: ao_rays 4, n_lights 0, ao_radius 1.0. The radius is a choice, not a
+ * measurement: a plain constant, one world unit, which the Python wrapper and the CLI take as well. The
+ * shipped scenes are built to human scale (the room of `final` is 20 units wide, its steps and furniture 0.5
+ * to 2), and ambient occlusion is meant to show contact and corner darkening at the scale of the objects,
+ * not the room's own walls. A fraction of the scene's BVH root box is not used although the call's wrappers
+ * have the scene: the builders put far geometry into it (the root box of `final` has a diagonal of 2000
+ * units, so 5% of it, 100 units, finds every probe of the room occluded: a mean ao of 0.0014 on C3). */
+#define DT_OCCL_MAX_AO_RAYS 16
+#define DT_OCCL_MAX_LIGHTS   8
+#define DT_OCCL_TRIES       16
+typedef struct dt_occlusion_params {
+  int32_t ao_rays;      /* 0..DT_OCCL_MAX_AO_RAYS occlusion rays per hitting sample; 0: no ao plane */
+  float   ao_radius;    /* finite, > 0: the radius R of the probe ball, world units */
+  int32_t n_lights;     /* 0..DT_OCCL_MAX_LIGHTS */
+  int32_t lights[DT_OCCL_MAX_LIGHTS]; /* indices into the scene's lights, each 0 <= l < the scene's n_lights */
+} dt_occlusion_params;
+typedef struct dt_occlusion {   /* each plane optional; all on one side */
+  float* ao;      /* 1 per pixel, entry q            (needs ao_rays > 0) */
+  float* light;   /* n_lights per pixel, entry n_lights*q + j (needs n_lights > 0) */
+} dt_occlusion;
+void dt_occlusion_params_default(dt_occlusion_params* p);
+int  dt_render_occlusion(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                         int32_t n_samples, const dt_occlusion_params* params, const dt_occlusion* out,
+                         int32_t out_on_device, void* stream, dt_stats* stats);
+/* The two probe generators for one hit (csrc/dt_occl.h, one definition for host and kernel), for tests and
+ * callers: dir of AO probe r (0..15) from the fixNorm'ed normal n, and of the probe of slot j (0..7) towards
+ * `light` from p. No device work. DT_OK; a null argument or an index outside its range: DT_E_INVALID.
+ * (p is not read by the AO rule; it is part of the signature for symmetry and must not be null.) */
+int dt_occlusion_ao_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint32_t sample, int32_t r, float ao_radius,
+                        const double p[3], const double n[3], double dir[3]);
+int dt_occlusion_light_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint32_t sample, int32_t j,
+                           const dt_light_desc* light, const double p[3], double dir[3]);
 
 /* ---- feature-guided denoising of previews: an edge-avoiding a-trous filter ----
  * No reference counterpart. The consumer of the feature buffers: (preview, albedo, normal, depth) ->
