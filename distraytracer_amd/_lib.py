@@ -192,7 +192,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_scene_bvh", "dt_bvh_build", "dt_accel_info_build", "dt_trace_build", "dt_slab_floats", "dt_slab_floats_max",
            "dt_render", "dt_render_async", "dt_collect_stats", "dt_debug_counters", "dt_debug_item_costs", "dt_render_sky",
            "dt_unpack_slabs", "dt_build_scene", "dt_scene_desc_free", "dt_write_ppm", "dt_write_png",
-           "dt_mocap_bone_table", "dt_debug_normalize", "dt_debug_vdiv", "dt_intersect_primary",
+           "dt_mocap_bone_table", "dt_debug_normalize", "dt_debug_vdiv", "dt_debug_vnorm", "dt_debug_light_edges",
+           "dt_intersect_primary",
            "dt_debug_load_obj",
            "dt_accum_doubles", "dt_window_check", "dt_render_window", "dt_render_window_async", "dt_resolve",
            "dt_adapt_converged", "dt_render_window_adaptive", "dt_render_window_adaptive_async",
@@ -278,6 +279,8 @@ def _load():
         "dt_debug_item_costs": (c_int64, [ctypes.c_void_p, P(ctypes.c_uint32), c_int64]),
         "dt_debug_normalize": (c_int32, [P(c_double), P(c_double), c_int64]),
         "dt_debug_vdiv": (c_int32, [P(c_double), P(c_double), P(c_double), P(c_uint64), c_int64]),
+        "dt_debug_vnorm": (c_int32, [P(c_double), P(c_double), P(c_uint64), c_int64]),
+        "dt_debug_light_edges": (c_int32, [P(SceneDesc), P(Globals), P(c_double), c_int32]),
         "dt_render_sky": (c_int32, [P(Globals), c_float, P(Tiles), ctypes.c_void_p, c_int32, ctypes.c_void_p,
                                     P(Stats)]),
         "dt_intersect_primary": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, c_int64, c_int64, ctypes.c_void_p,

@@ -33,6 +33,8 @@ extern "C" hipError_t dt_launch_unpack(const void* dev_launch, int world, int64_
 extern "C" hipError_t dt_launch_normalize(const double* in, double* out, int64_t n, hipStream_t stream);
 extern "C" hipError_t dt_launch_vdiv(const double* in, const double* den, double* out, unsigned long long* fallback,
                                      int64_t n, hipStream_t stream);
+extern "C" hipError_t dt_launch_vnorm(const double* in, double* out, unsigned long long* fallback, int64_t n,
+                                      hipStream_t stream);
 // The trace-kernel builds, named once (dt_kernels.hip DT_TRACE_KERNEL, Makefile TRACE_BUILDS, in its
 // order): per wave count (4, then 5) room, mesh, full (still frames), tunnel, blur (motion-blur frames)
 // and sky; then the work-sharing and the RectPrismWithCylinder build. Each exists in three modes: the
@@ -2240,5 +2242,50 @@ extern "C" int dt_debug_vdiv(const double* in, const double* den, double* out, u
   if (e == hipSuccess) e = hipMemcpy(fallback, dfb, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost);
   (void)hipFree(d);
   if (e != hipSuccess) return fail(DT_E_NO_DEVICE, std::string("HIP: ") + hipGetErrorString(e));
+  return DT_OK;
+}
+
+extern "C" int dt_debug_vnorm(const double* in, double* out, uint64_t* fallback, int64_t n)
+{
+  if (!in || !out || !fallback || n < 0 || n > (int64_t)1 << 24) return fail(DT_E_INVALID, "bad arguments");
+  fallback[0] = 0;
+  if (n == 0) return DT_OK;
+  int dev_count = 0;
+  if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count < 1) return fail(DT_E_NO_DEVICE, "no HIP device");
+  // one allocation: the vectors (3n), the two result blocks (8n), the counter
+  const size_t nd = (size_t)n * 11;
+  double* d = nullptr;
+  if (hipMalloc((void**)&d, (nd + 1) * sizeof(double)) != hipSuccess) return fail(DT_E_OOM, "hipMalloc");
+  double *din = d, *dout = d + 3 * n;
+  unsigned long long* dfb = (unsigned long long*)(d + nd);
+  hipError_t e = hipMemcpy(din, in, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(dfb, 0, sizeof(unsigned long long));
+  if (e == hipSuccess) e = dt_launch_vnorm(din, dout, dfb, n, nullptr);
+  if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(fallback, dfb, sizeof(uint64_t), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(DT_E_NO_DEVICE, std::string("HIP: ") + hipGetErrorString(e));
+  return DT_OK;
+}
+
+extern "C" int dt_debug_light_edges(const dt_scene_desc* desc, const dt_globals* g, double* out, int32_t cap)
+{
+  if (!desc || !g || !out || cap < 0) return fail(DT_E_INVALID, "bad arguments");
+  if (desc->n_shapes < 0 || (desc->n_shapes > 0 && !desc->shapes)) return fail(DT_E_INVALID, "invalid descriptor");
+  if (desc->n_lights > cap) return fail(DT_E_INVALID, "out holds fewer lights than the scene has");
+  FlatScene f;
+  std::string err;
+  int rc = flatten_scene(*desc, *g, f, err);
+  if (rc) return fail(rc, err);
+  for (size_t i = 0; i < f.lights.size(); ++i) {
+    const dtd::DLight& L = f.lights[i];
+    for (int k = 0; k < 3; ++k) {
+      out[15 * i + k] = L.A[k];
+      out[15 * i + 3 + k] = L.B[k];
+      out[15 * i + 6 + k] = L.D[k];
+      out[15 * i + 9 + k] = L.AB[k];
+      out[15 * i + 12 + k] = L.AD[k];
+    }
+  }
   return DT_OK;
 }

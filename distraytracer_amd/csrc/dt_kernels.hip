@@ -2447,7 +2447,8 @@ __device__ __forceinline__ V3 light_sample(const Ctx& c, const DT_CAS DLight& L,
       w1 = odd ? o[3] : o[1];
       if (pair && !odd) { pair[0] = o[2]; pair[1] = o[3]; pair[2] = (uint32_t)li + 1u; }
     }
-    return sub(rect_sample_f(v3a(L.A), v3a(L.B), v3a(L.D), f01(w0), f01(w1)), point);
+    // rect_sample_f with the light's own B - A and D - A (DLight::AB, AD: the same subtractions, once)
+    return sub(add(add(v3a(L.A), mul(f01(w0), v3a(L.AB))), mul(f01(w1), v3a(L.AD))), point);
   }
   DT_NEED(DT_FEAT_SPHL);
   return sphere_light_sample(c, L, li, point, node, st_sphl);
@@ -3104,8 +3105,9 @@ __device__ __forceinline__ void run_pass(const Ctx& c_in, bool active, V3 ray0, 
         if (ws) {
           DT_WK(DT_WK_LIGHT, true);
           sray = light_sample(c, L, li, isectP, node, cnt.wc + WC_SPHL, pair);
-          t_max = (float)norm(sray);
-          sn = normalized(sray);
+          double len;
+          sn = normalized_len(sray, len);
+          t_max = (float)len;
         }
         DT_WCNT(WC_SHADOW, walk);
         DT_T(t4);
@@ -4896,7 +4898,44 @@ dt_vdiv_kernel(const double* __restrict__ in, const double* __restrict__ den, do
   }
 }
 
+// dt_math.h's fused length and normalisation (vnorm_fused) on n vectors in[3i..3i+2] against plain sqrt and
+// three plain divisions, whatever DT_VNORM this build has: out's two blocks of 4n doubles hold (s, v / s) fused
+// and plain. fallback[0]: the lanes whose fused call took the plain branch (tests/test_gpu_vnorm.py).
+extern "C" __global__ void __launch_bounds__(256)
+dt_vnorm_kernel(const double* __restrict__ in, double* __restrict__ out, unsigned long long* __restrict__ fallback,
+                int64_t n)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool fb = false;
+  if (i < n) {
+    const V3 a = v3(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
+    const double d = dot(a, a);
+    double s[2];
+    V3 r[2];
+    bool fused = true;
+    r[0] = vnorm_fused(a, d, s[0], fused);
+    fb = !fused;
+    s[1] = sqrt(d);
+    r[1] = d > 0 ? divs_plain(a, s[1]) : a;
+    for (int k = 0; k < 2; ++k) {
+      double* __restrict__ o = out + (int64_t)k * 4 * n + 4 * i;
+      o[0] = s[k];
+      o[1] = r[k].x;
+      o[2] = r[k].y;
+      o[3] = r[k].z;
+    }
+  }
+  const unsigned long long n_fb = __popcll(__ballot(fb));
+  if ((threadIdx.x & 63) == 0 && n_fb) atomicAdd(fallback, n_fb);
+}
+
 // ---- host-side launch wrappers ---------------------------------------------------------
+extern "C" hipError_t dt_launch_vnorm(const double* in, double* out, unsigned long long* fallback, int64_t n,
+                                      hipStream_t stream)
+{
+  hipLaunchKernelGGL(dt_vnorm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, out, fallback, n);
+  return hipGetLastError();
+}
 extern "C" hipError_t dt_launch_vdiv(const double* in, const double* den, double* out, unsigned long long* fallback,
                                      int64_t n, hipStream_t stream)
 {

@@ -86,11 +86,91 @@ DT_HD V3 cross(V3 a, V3 b)
   return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
 }
 DT_HD double norm(V3 a) { return sqrt(dot(a, a)); }
+// DT_VNORM=1 (default): device code takes a vector's length and its normalisation from one square-root
+// refinement (DT_VNORM=0: sqrt, then a division that starts again from v_rcp_f64, as the host always does).
+#ifndef DT_VNORM
+#define DT_VNORM 1
+#endif
+#if defined(__HIPCC__)
+// The compiler's sqrt(d) for f64 on gfx950, in its order (read off the ISA of the builds without this):
+//   sc = d < 2^-767; x = ldexp(d, sc ? 256 : 0); y = rsq(x); g = x * y; h = y * 0.5; r = fma(-h, g, 0.5);
+//   g = fma(g, r, g); h = fma(h, r, h); e = fma(-g, g, x); g = fma(e, h, g); e = fma(-g, g, x);
+//   g = fma(e, h, g); g = ldexp(g, sc ? -128 : 0); class(x, +-0 | +inf) ? x : g
+// In range (below) nothing is scaled and the class test fails, so s restates the middle of it operation
+// for operation: the bits of sqrt(d). h ends as 1 / (2 sqrt(d)) to about 2^-50, so 2h (exact) with one
+// Newton step against the rounded s is 1 / s to about 2^-100 before its rounding, which is what the
+// division's v_rcp_f64 and two steps arrive at; the quotients then take the division's own q = n * r,
+// t = fma(-s, q, n), fma(t, r, q), correctly rounded with either r.
+// In range: 2^-600 <= d < 2^600 (so 2^-300 <= s <= 2^300; false for NaN) and 2^-600 <= |n| for each
+// component n (|n| <= s always). Far inside every threshold of the plain sequences: sqrt scales below
+// d = 2^-767; v_div_scale_f64 leaves the divisor s and the numerator n as they are and vcc clear unless
+// n or s is 0, s is subnormal, 1 / s is (s >= 2^1022), n / s is (exponents more than 1022 apart, here at
+// most 900), the exponents are 768 or more apart the other way (|n| <= s) or n is below 2^-969;
+// v_div_fixup_f64 passes the quotient through unless an operand is 0, inf or NaN or the exponents are
+// more than 1075 apart. So div_scale, div_fmas' scaling and div_fixup are identities here and are left
+// out. Any other lane (zero or tiny components, huge, inf, NaN) takes sqrt and divs in a branch.
+__device__ __forceinline__ double vnorm_quot(double n, double s, double r)
+{
+  const double q = n * r;
+  const double t = __builtin_fma(-s, q, n);
+  return __builtin_fma(t, r, q);
+}
+__device__ __forceinline__ V3 vnorm_fused(V3 a, double d, double& s, bool& fused)
+{
+  // on the high words (sign, exponent field, 20 fraction bits), as integers: no f64 literal to materialise;
+  // d is +0 or more, or a NaN, whose high word lies above hi with either sign
+  const uint32_t lo = (1023u - 600u) << 20, hi = (1023u + 600u) << 20;
+  const uint32_t hd = (uint32_t)(__builtin_bit_cast(uint64_t, d) >> 32);
+  const uint32_t hx = (uint32_t)(__builtin_bit_cast(uint64_t, a.x) >> 32) & 0x7fffffffu;
+  const uint32_t hy = (uint32_t)(__builtin_bit_cast(uint64_t, a.y) >> 32) & 0x7fffffffu;
+  const uint32_t hz = (uint32_t)(__builtin_bit_cast(uint64_t, a.z) >> 32) & 0x7fffffffu;
+  const uint32_t hmin = hx < hy ? (hx < hz ? hx : hz) : (hy < hz ? hy : hz);
+  fused = hd - lo < hi - lo && hmin >= lo;
+  if (__builtin_expect(!fused, 0)) {
+    s = sqrt(d);
+    if (d > 0) return divs(a, s);
+    return a;
+  }
+  const double y = __builtin_amdgcn_rsq(d);
+  double g = d * y;
+  double h = y * 0.5;
+  const double r0 = __builtin_fma(-h, g, 0.5);
+  g = __builtin_fma(g, r0, g);
+  h = __builtin_fma(h, r0, h);
+  double e = __builtin_fma(-g, g, d);
+  g = __builtin_fma(e, h, g);
+  e = __builtin_fma(-g, g, d);
+  g = __builtin_fma(e, h, g);
+  s = g;
+  double r = h + h;
+  e = __builtin_fma(-g, r, 1.0);
+  r = __builtin_fma(r, e, r);
+  return v3(vnorm_quot(a.x, g, r), vnorm_quot(a.y, g, r), vnorm_quot(a.z, g, r));
+}
+#endif
+// normalized(a) and, in len, norm(a)
+DT_HD V3 normalized_len(V3 a, double& len)
+{
+  const double n = dot(a, a);
+#if defined(__HIP_DEVICE_COMPILE__) && DT_VNORM
+  bool fused;
+  return vnorm_fused(a, n, len, fused);
+#else
+  len = sqrt(n);
+  if (n > 0) return divs(a, len);
+  return a;
+#endif
+}
 DT_HD V3 normalized(V3 a)
 {
+#if defined(__HIP_DEVICE_COMPILE__) && DT_VNORM
+  double len;
+  return normalized_len(a, len);
+#else
   double n = dot(a, a);
   if (n > 0) return divs(a, sqrt(n));
   return a;
+#endif
 }
 DT_HD double dmin(double a, double b) { return (b < a) ? b : a; }   // std::min
 DT_HD double dmax(double a, double b) { return (a < b) ? b : a; }   // std::max

@@ -85,6 +85,7 @@ struct alignas(16) DLight {
   int32_t type, shape_index, use_baxis, _pad;
   double radius;
   double center[3], color[3], baxis[3], A[3], B[3], D[3];
+  double AB[3], AD[3];   // B - A and D - A, the edges sampleRay spans (host: the same f64 subtractions)
 };
 
 // ---- geometry record layouts (offsets in doubles) ----------------------------------------

@@ -310,6 +310,8 @@ int flatten_scene(const dt_scene_desc& d, const dt_globals& g, FlatScene& out, s
       o.A[k] = L.A[k];
       o.B[k] = L.B[k];
       o.D[k] = L.D[k];
+      o.AB[k] = L.B[k] - L.A[k];
+      o.AD[k] = L.D[k] - L.A[k];
     }
   }
   build_bvh(d, g, out.bvh);

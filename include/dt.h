@@ -463,6 +463,16 @@ int dt_debug_normalize(const double* in, double* out, int64_t n);
  * vectors whose shared a / den and whose shared normalisation divided plainly after all (their three
  * scaled divisors differ). Host arrays; synchronous. A diagnostic added under ABI 8. */
 int dt_debug_vdiv(const double* in, const double* den, double* out, uint64_t* fallback, int64_t n);
+/* numerics check of the device kernels' fused length and normalisation (dt_math.h vnorm_fused): n vectors
+ * in[3i..3i+2]; out: two blocks of 4n doubles, (|a|, a / |a|) per vector by the fused path and by plain
+ * sqrt and three plain divisions (a itself where dot(a, a) > 0 does not hold); fallback[0]: the vectors
+ * whose fused call took the plain branch (out of range). Host arrays; synchronous. A diagnostic added
+ * under ABI 8. */
+int dt_debug_vnorm(const double* in, double* out, uint64_t* fallback, int64_t n);
+/* the device light records' sampling frame for (desc, g), on the host only (no device): per light 15
+ * doubles A, B, D, B - A, D - A as the kernels read them; cap: the lights out has room for. A diagnostic
+ * added under ABI 8. */
+int dt_debug_light_edges(const dt_scene_desc* desc, const dt_globals* g, double* out, int32_t cap);
 
 /* Intersection micro-benchmark (2^24 primary rays of the C3 camera). rayColor's first
  * step (render_final_project.cpp:491-538: BVH gather + closest hit) for primary rays of the globals'
