@@ -21,8 +21,10 @@
  *     Not compared (no restatement here, or no reference answer): intersectMax, buildCOB on its own,
  *     shortestLine's coefficients, lineIntersect, RectPrism / RectPrismWithHoles, and
  *     RectPrismWithCylinder::getNorm where the reference throws or answers from a stale lastHit.
- *   - render_final_project.cpp and helpers.h (shading, refraction, BVH build) drag in the skeleton code
- *     and ~60 globals: "parity unpinned" beyond analytic anchors (tests/test_oracle_*.py).
+ *   - render_final_project.cpp and helpers.h: rayColor and generateBVH are pinned ray by ray against the
+ *     reference's own, included unmodified by oracle/ref/shade_harness.cpp (-> oracle/_ref/libref_shade_cr.so
+ *     -> tests/golden/shade_ref.npz, tests/test_oracle_shade.py). Not pinned: glossy and area-light
+ *     sampling, the motion-blur re-trace, DoF and jitter generation (the reference's RNG, renderImage).
  *
  * RNG: the reference draws from random_device-seeded mt19937 (F7) and cannot be
  * reproduced; oracle and device share the counter-based stream documented in

@@ -1,0 +1,260 @@
+"""TEST INFRASTRUCTURE ONLY -- the shaded-ray parity vectors: the reference's own rayColor and generateBVH
+(oracle/_ref/libref_shade.so and libref_shade_cr.so, oracle/ref/shade_harness.cpp; absent where the
+reference is) on the project's primary rays, and the project's side of the comparison.
+
+tools/gen_golden_shade.py builds the scenes of tests/scene_gen.py SHADE_SCENES, lets RefShade answer their
+rays and writes tests/golden/shade_ref.npz; tests/test_oracle_shade.py and tests/test_gpu_shade.py read the
+fixture only. The fixture holds data: shape, light and globals records, rays, colours, flags, BVH lists."""
+import ctypes
+import os
+import tempfile
+
+import numpy as np
+
+from distraytracer_amd._lib import DATA_DIR, BVHNode, Globals, LightDesc, SceneDesc, ShapeDesc, TextureDesc
+
+from . import HERE, oracle
+from . import geom as G
+
+REF_SHADE_SO = os.path.join(HERE, "_ref", "libref_shade.so")
+REF_SHADE_CR_SO = os.path.join(HERE, "_ref", "libref_shade_cr.so")
+LIGHT_DT = np.dtype(LightDesc)
+BVH_DT = np.dtype(BVHNode)
+GOLD = os.path.join(os.path.dirname(HERE), "tests", "golden", "shade_ref.npz")
+
+P = ctypes.POINTER
+_D = P(ctypes.c_double)
+
+
+def read_rgb(rel):
+    """(pixels bytes, width, height) of a committed decoded texture under DATA_DIR ("DTRGB w h 3\\n" + bytes)"""
+    with open(os.path.join(DATA_DIR, rel), "rb") as fh:
+        head = fh.readline().split()
+        assert head[0] == b"DTRGB" and head[3] == b"3", head
+        w, h = int(head[1]), int(head[2])
+        px = fh.read()
+    assert len(px) == 3 * w * h
+    return px, w, h
+
+
+def build(name, sg):
+    """(desc, g, keepalive, texture or None) of a SHADE_SCENES class or "textured"; sg: tests/scene_gen.py,
+    imported by the caller"""
+    if name == "textured":
+        px, w, h = read_rgb(sg.SHADE_TEXTURE)
+        desc, g, keep = sg.shade_textured(px, w, h)
+        return desc, g, keep, (sg.SHADE_TEXTURE, px, w, h)
+    desc, g, keep = sg.SHADE_SCENES[name]()
+    return desc, g, keep, None
+
+
+def light_records(desc):
+    n = desc.n_lights
+    if n <= 0:
+        return np.zeros(0, dtype=LIGHT_DT)
+    return np.frombuffer(ctypes.string_at(desc.lights, n * ctypes.sizeof(LightDesc)), dtype=LIGHT_DT).copy()
+
+
+def desc_from_records(shape_rec, light_rec, texture=None):
+    """(SceneDesc, keepalive) from stored records; texture: the relative path of a committed decoded one"""
+    shapes = G.shapes_from_records(shape_rec)
+    light_rec = np.ascontiguousarray(light_rec, dtype=LIGHT_DT)
+    lights = (LightDesc * max(len(light_rec), 1))()
+    ctypes.memmove(lights, light_rec.ctypes.data, light_rec.nbytes)
+    d = SceneDesc(len(shape_rec), len(light_rec), 0, 0, shapes, lights, None, 0, 0, None)
+    keep = [shapes, lights]
+    if texture:
+        px, w, h = read_rgb(texture)
+        buf = (ctypes.c_uint8 * len(px)).from_buffer_copy(px)
+        tex = (TextureDesc * 1)()
+        tex[0].width, tex[0].height, tex[0].channels = w, h, 3
+        tex[0].pixels = ctypes.cast(buf, P(ctypes.c_uint8))
+        d.n_textures, d.textures = 1, tex
+        keep += [buf, tex]
+    return d, keep
+
+
+def spp(g):
+    n = int(np.sqrt(g.antialias_samples))
+    return n * n
+
+
+def ray_index(g):
+    """or_primary_ray's number of (pixel y * xRes + x, sample i), as an array [pixel, sample] (include/dt.h
+    dt_intersect_primary: ray r -> q = r / 8, pixel q mod W*H, sample r mod 8 + 8 (q div W*H))"""
+    npx = g.xRes * g.yRes
+    i = np.arange(spp(g))[None, :]
+    p = np.arange(npx)[:, None]
+    return ((i // 8) * npx + p) * 8 + i % 8
+
+
+def primary_rays(g):
+    """(start, dir) [pixel, sample, 3] of every sample of every pixel, frame 0"""
+    n = g.xRes * g.yRes * max(8, -(-spp(g) // 8) * 8)
+    start, d = G.or_primary_ray(g, 0, 0, n)
+    r = ray_index(g)
+    return start[r], d[r]
+
+
+def oracle_colors(desc, g):
+    """or_sample_color over every sample: (colour [pixel, sample, 3] f64, hit [pixel, sample] int32)"""
+    o = oracle()
+    n, W = spp(g), g.xRes
+    col = np.zeros((g.xRes * g.yRes, n, 3))
+    hit = np.zeros((g.xRes * g.yRes, n), dtype=np.int32)
+    c, h = (ctypes.c_double * 3)(), ctypes.c_int()
+    dp = ctypes.pointer(desc)
+    for p in range(g.xRes * g.yRes):
+        for i in range(n):
+            rc = o.or_sample_color(dp, ctypes.byref(g), 0, p % W, p // W, i, c, ctypes.byref(h))
+            if rc:
+                raise RuntimeError("or_sample_color failed %d" % rc)
+            col[p, i] = c[0], c[1], c[2]
+            hit[p, i] = h.value
+    return col, hit
+
+
+def image_from_colors(g, col):
+    """renderImage's epilogue on per-sample colours [pixel, sample, 3]: color += tmp in sample order,
+    color /= n in double, clamp((float)c) * 255.0f into the ppmOut layout (cpp:1212-1217)"""
+    n = col.shape[1]
+    acc = np.zeros((col.shape[0], 3))
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            acc = acc + col[:, i]
+        acc = acc / float(n)
+        f = acc.astype(np.float32)
+        # helpers.h clamp: value < 0 -> 0, value > 1 -> 1, anything else (a NaN) unchanged
+        f = np.where(f < 0, np.float32(0), np.where(f > 1, np.float32(1), f)) * np.float32(255.0)
+    W, H = g.xRes, g.yRes
+    out = np.zeros((H, W, 3), dtype=np.float32)
+    out[H - 1 - np.arange(W * H) // W, np.arange(W * H) % W] = f
+    return out.reshape(-1)
+
+
+def pixel_mask_to_channels(g, pixel_mask):
+    """a per-pixel mask [y * W + x] -> the ppmOut layout's channels"""
+    W, H = g.xRes, g.yRes
+    m = np.zeros((H, W, 3), dtype=bool)
+    m[H - 1 - np.arange(W * H) // W, np.arange(W * H) % W] = np.asarray(pixel_mask, dtype=bool)[:, None]
+    return m.reshape(-1)
+
+
+def bvh_arrays(nodes, idx):
+    rec = np.zeros(len(nodes), dtype=BVH_DT)
+    if len(nodes):
+        arr = (BVHNode * len(nodes))(*nodes)
+        rec = np.frombuffer(bytes(arr), dtype=BVH_DT).copy()
+    return rec, np.array(idx, dtype=np.int32)
+
+
+BVH_FIELDS = ("first_child", "n_children", "first_index", "n_indices", "leaf", "depth", "lbound", "ubound")
+
+
+def bvh_differs(a, b):
+    """None, or what differs first between two BVH node record arrays (integers as integers, bounds by bits)"""
+    if len(a) != len(b):
+        return "%d nodes against %d" % (len(a), len(b))
+    for f in BVH_FIELDS:
+        d = G.differs(np.ascontiguousarray(a[f]), np.ascontiguousarray(b[f]))
+        if d.any():
+            i = int(np.argmax(d))
+            return "node %d %s: %r against %r" % (i, f, a[f][i].tolist(), b[f][i].tolist())
+    return None
+
+
+class RefShade:
+    """One of the two reference builds with a scene set"""
+
+    @staticmethod
+    def available(cr=True):
+        return os.path.exists(REF_SHADE_CR_SO if cr else REF_SHADE_SO)
+
+    def __init__(self, cr=True):
+        self.r = r = ctypes.CDLL(REF_SHADE_CR_SO if cr else REF_SHADE_SO)
+        S, L = P(ShapeDesc), P(LightDesc)
+        r.ref_reset.restype = None
+        r.ref_load_texture.argtypes = [ctypes.c_char_p]
+        r.ref_scene_set.argtypes = [S, ctypes.c_int, S, L, ctypes.c_int, P(Globals)]
+        r.ref_ray_color.argtypes = [_D, _D, ctypes.c_int, ctypes.c_float, _D, P(ctypes.c_int), P(ctypes.c_int)]
+        r.ref_bvh.argtypes = [P(BVHNode), ctypes.c_int, P(ctypes.c_int), ctypes.c_int, P(ctypes.c_int), P(ctypes.c_int)]
+
+    def set(self, desc, g, texture=None):
+        """texture: (pixels, w, h), handed to the reference's loadTexture as a binary PPM"""
+        self.r.ref_reset()
+        if texture is not None:
+            px, w, h = texture
+            with tempfile.NamedTemporaryFile(suffix=".ppm", delete=False) as fh:
+                fh.write(b"P6\n%d %d\n255\n" % (w, h) + bytes(px))
+            try:
+                if self.r.ref_load_texture(fh.name.encode()):
+                    raise RuntimeError("loadTexture threw")
+            finally:
+                os.unlink(fh.name)
+        rc = self.r.ref_scene_set(desc.shapes, desc.n_shapes, desc.holes, desc.lights, desc.n_lights, ctypes.byref(g))
+        if rc:
+            raise RuntimeError("ref_scene_set failed %d" % rc)
+        self.depth = g.max_depth
+
+    def colors(self, start, d):
+        """rayColor(dir, start, max_depth) per ray: colour f64 [.., 3], hit, in_motion, threw int32 [..]"""
+        shp = start.shape[:-1]
+        s2, d2 = np.ascontiguousarray(start.reshape(-1, 3)), np.ascontiguousarray(d.reshape(-1, 3))
+        col = np.zeros_like(s2)
+        hit, mot, threw = (np.zeros(len(s2), dtype=np.int32) for _ in range(3))
+        h, m = ctypes.c_int(), ctypes.c_int()
+        for k in range(len(s2)):
+            threw[k] = self.r.ref_ray_color(d2[k].ctypes.data_as(_D), s2[k].ctypes.data_as(_D), self.depth, 1.0,
+                                            col[k].ctypes.data_as(_D), ctypes.byref(h), ctypes.byref(m))
+            hit[k], mot[k] = h.value, m.value
+        return col.reshape(shp + (3,)), hit.reshape(shp), mot.reshape(shp), threw.reshape(shp)
+
+    def bvh(self):
+        nn, ni = ctypes.c_int(), ctypes.c_int()
+        self.r.ref_bvh(None, 0, None, 0, ctypes.byref(nn), ctypes.byref(ni))
+        nodes = (BVHNode * max(nn.value, 1))()
+        idx = (ctypes.c_int * max(ni.value, 1))()
+        self.r.ref_bvh(nodes, nn.value, idx, ni.value, ctypes.byref(nn), ctypes.byref(ni))
+        return bvh_arrays(list(nodes)[:nn.value], list(idx)[:ni.value])
+
+
+def answer(name, sg):
+    """Everything the fixture stores for one class, from the two reference builds and the oracle:
+    a dict of arrays, and the per-vector comparison (differs: colour bits, hit or in_motion)"""
+    desc, g, keep, tex = build(name, sg)
+    start, d = primary_rays(g)
+    texture = None if tex is None else tex[1:]
+    cr, plain = RefShade(True), RefShade(False)
+    cr.set(desc, g, texture)
+    col, hit, mot, threw = cr.colors(start, d)
+    nodes, idx = cr.bvh()
+    plain.set(desc, g, texture)
+    pcol = plain.colors(start, d)[0]
+    ocol, ohit = oracle_colors(desc, g)
+    shape_rec, _ = G.records_from_desc(desc)
+    out = {"shapes": shape_rec, "lights": light_records(desc), "globals": G.record_from_globals(g),
+           "texture": np.array("" if tex is None else tex[0]), "start": start, "dir": d, "color": col,
+           "hit": hit, "in_motion": mot, "threw": threw, "bvh_nodes": nodes, "bvh_idx": idx}
+    out.update(plain_pack(col, pcol))
+    return out, (desc, g, keep), (ocol, ohit)
+
+
+def plain_pack(col, pcol):
+    """the plain-libm build's colours as the vectors on which they differ from the cr build's"""
+    d = G.differs(col.reshape(-1, 3), pcol.reshape(-1, 3))
+    return {"plain_index": np.nonzero(d)[0].astype(np.int32), "plain_color": pcol.reshape(-1, 3)[d]}
+
+
+def plain_unpack(col, index, values):
+    p = col.reshape(-1, 3).copy()
+    p[index] = values
+    return p.reshape(col.shape)
+
+
+def rel_diff(a, b):
+    """largest |a - b| / max(|a|, |b|) over the finite, unequal elements (0 where none)"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    ok = np.isfinite(a) & np.isfinite(b) & (a != b)
+    if not ok.any():
+        return 0.0
+    return float((np.abs(a[ok] - b[ok]) / np.maximum(np.abs(a[ok]), np.abs(b[ok]))).max())

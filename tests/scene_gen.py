@@ -222,3 +222,208 @@ def build(family, case):
     s, t = CASES[case]
     desc, g, keep = fn(s, t)
     return desc, g, keep, frame
+
+
+# ---------------------------------------------------------------------------------------------------
+# The shaded-ray scenes of tests/golden/shade_ref.npz (tools/gen_golden_shade.py): every one
+# deterministic once its primary rays are given -- point lights, or area lights without extent -- so that
+# the reference's own rayColor answers them without its unseeded RNG. 32 x 16 pixels at 1 spp, depth 4,
+# depth of field on, unless said otherwise; lights dim enough that few channels clamp.
+# ---------------------------------------------------------------------------------------------------
+F_TEXTURE, F_UV_VERTS = 4, 64   # include/dt.h DT_F_*
+SHADE_TEXTURE = "models/Column_LP_obj/Textures/Marble_Base_Color.jpg.rgb"   # under the package's DATA_DIR
+
+_MODEL_KW = {PHONG: {}, OREN_NAYAR: dict(roughness=0.3), COOK_TORRANCE: dict(roughness=0.4, refr=(2.75, 3.79)), RAW: {}}
+
+
+def _triangle(b, A, B, C, color, **kw):
+    cen = tuple(((A[a] + B[a]) + C[a]) / 3 for a in range(3))     # Triangle's constructor: (A + B + C) / 3
+    return b.shape(TRIANGLE, v=[A, B, C], color=color, center=cen, **kw)
+
+
+def _shade_globals(b, g, res=(32, 16), spp=1, depth=4):
+    g.xRes, g.yRes, g.antialias_samples, g.max_depth, g.brdf_samples = res[0], res[1], spp, depth, 2
+    desc, keep = b.desc()
+    return desc, g, keep
+
+
+def _two_lights(b):
+    """one point light above a hovering plate (its umbra covers part of the floor), one low at the side"""
+    _rect(b, (-3.5, 2.5, 2.0), (-1.0, 2.5, 2.0), (-1.0, 2.5, -1.0), (-3.5, 2.5, -1.0), (0.7, 0.7, 0.75), flags=0)
+    b.light(POINT_LIGHT, center=(-2.5, 3.5, 0.5), color=(0.45, 0.45, 0.45))
+    b.light(POINT_LIGHT, center=(3.0, 3.0, 3.0), color=(0.35, 0.35, 0.3))
+
+
+def shade_model(model, triangle=True, res=(32, 16), spp=1):
+    """A floor, a back wall, a standing cylinder and (triangle=True) a triangle of one shading model under
+    two point lights, one partly occluded by a plate: pixels lit by none, one and both. Without the triangle
+    the Phong and Cook-Torrance scenes hold room features only, with it (or with Oren-Nayar) mesh features."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    kw = dict(model=model, **_MODEL_KW[model])
+    _rect(b, (-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), (0.58, 0.82, 1.0), flags=0, **kw)
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 4, -4), (-4, 4, -4), (0.0, 0.81, 0.99), flags=0, **kw)
+    _cylinder(b, (0.25, 0, 0.5), (0.25, 2.0, 0.5), 1.0, (0.95, 0.64, 0.54), **kw)
+    if triangle:
+        _triangle(b, (-3.0, 0.25, 1.0), (-1.5, 0.25, 1.5), (-2.25, 2.0, 0.5), (0.2, 0.8, 0.3), **kw)
+    # a panel in the back wall's own plane, after it in the shape list: rays that hit both at the same float t
+    # keep the first of the gather order (the closest hit's strict <)
+    _rect(b, (1.5, 1.0, -4), (3.0, 1.0, -4), (3.0, 2.5, -4), (1.5, 2.5, -4), (0.9, 0.2, 0.2), flags=0, **kw)
+    # a panel 1.5e-3 above the second light: a shadow ray that starts 1e-3 along its direction reaches it
+    # beyond t_max whatever its angle, one that started 2e-3 along would reach it before t_max when steep
+    _rect(b, (1.5, 3.0015, 4.5), (4.5, 3.0015, 4.5), (4.5, 3.0015, 1.5), (1.5, 3.0015, 1.5), (0.7, 0.7, 0.75), flags=0)
+    _two_lights(b)
+    return _shade_globals(b, b.globals((0.5, 1.25, 6.5), (0.0, 0.75, 0.0), 0.0625, 6.0), res, spp)
+
+
+def shade_mirror(triangle=False):
+    """Steel, not glossy: a lying cylinder and a wall panel; the floor is glossy linoleum and nogloss = 1, so
+    it takes the mirror path too. Room features only; with a (steel) triangle, mesh features."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    if triangle:
+        _triangle(b, (-3.5, 0.25, 2.0), (-2.0, 0.25, 2.5), (-2.75, 1.75, 1.5), (0.8, 0.8, 0.8), material=STEEL)
+    _rect(b, (-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), (0.58, 0.82, 1.0), flags=F_GLOSSY, material=LINOLEUM,
+          roughness=0.6, refr=(1.543, 0.0))
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 4, -4), (-4, 4, -4), (0.0, 0.81, 0.99), flags=0)
+    _rect(b, (-3.0, 0.5, -3.5), (-0.5, 0.5, -3.0), (-0.5, 3.0, -3.0), (-3.0, 3.0, -3.5), (0.8, 0.8, 0.8), flags=0,
+          material=STEEL)
+    _cylinder(b, (0.5, 0.5, 1.0), (2.5, 0.5, 0.0), 0.5, (0.8, 0.8, 0.8), material=STEEL)
+    _cylinder(b, (-1.5, 0, 1.0), (-1.5, 1.5, 1.0), 0.4, (0.9, 0.3, 0.2))
+    b.light(POINT_LIGHT, center=(-2.5, 3.5, 2.5), color=(0.4, 0.4, 0.4))
+    b.light(POINT_LIGHT, center=(3.0, 3.0, 3.0), color=(0.3, 0.3, 0.3))
+    g = b.globals((0.5, 1.25, 6.5), (0.0, 0.75, 0.0), 0.0625, 6.0)
+    g.nogloss = 1
+    return _shade_globals(b, g)
+
+
+def shade_glass():
+    """A glass sphere and a glass pane (RectPrismV2) over a floor before a wall: rays enter and leave both;
+    off-centre hits on the sphere are the rays whose Fresnel weights are NaN on both sides (Q25). The sphere
+    is small: a ray that leaves it through its middle reads the reference's uninitialised `inside` (Q5), and
+    the compiled reference and the defined reading must agree on 98 % of the class."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    _rect(b, (-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), (0.58, 0.82, 1.0), flags=0)
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 4, -4), (-4, 4, -4), (0.9, 0.5, 0.2), flags=0)
+    b.shape(SPHERE, v=[(1.25, 1.0, 1.0)], radius=0.5625, color=(0.9, 0.9, 1.0), material=GLASS, center=(1.25, 1.0, 1.0))
+    pa, pb, pc, pd = (-2.5, 0.25, 1.5), (-0.5, 0.25, 1.5), (-0.5, 0.25, 1.25), (-2.5, 0.25, 1.25)
+    up = lambda p: (p[0], p[1] + 2.0, p[2])
+    b.shape(PRISM_V2, v=[pa, pb, pc, pd, up(pa), up(pb), up(pc), up(pd)], color=(0.9, 1.0, 0.9), material=GLASS,
+            length=2.0, width=0.25, center=(-1.5, 1.25, 1.375))
+    _cylinder(b, (-1.5, 0, -1.5), (-1.5, 1.5, -1.5), 0.5, (0.9, 0.3, 0.2))
+    b.light(POINT_LIGHT, center=(-2.5, 3.5, 2.5), color=(0.4, 0.4, 0.4))
+    b.light(POINT_LIGHT, center=(3.0, 3.0, 3.0), color=(0.3, 0.3, 0.3))
+    return _shade_globals(b, b.globals((0.5, 1.25, 6.5), (0.0, 0.75, 0.0), 0.0625, 6.0))
+
+
+def shade_emitters():
+    """The camera sees a "spherelight" and a "rectanglelight" shape directly (their emission formulas); the
+    floor and wall are lit by a point light, the emitters only occlude."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    _rect(b, (-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), (0.58, 0.82, 1.0), flags=0)
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 4, -4), (-4, 4, -4), (0.0, 0.81, 0.99), flags=0)
+    b.shape(SPHERE, v=[(1.5, 1.25, 0.5)], radius=0.75, color=(0.6, 0.55, 0.4), emit=1, flags=F_LIGHT, center=(1.5, 1.25, 0.5))
+    ra, rb, rc, rd = (-3.0, 0.5, -1.0), (-1.0, 0.5, 0.0), (-1.0, 2.0, 0.0), (-3.0, 2.0, -1.0)
+    b.shape(RECTANGLE, v=[ra, rb, rc, rd], color=(0.5, 0.6, 0.6), emit=2, flags=F_LIGHT, length=1.0, width=1.0,
+            center=tuple((ra[a] + rb[a] + rc[a] + rd[a]) / 4 for a in range(3)))
+    b.light(POINT_LIGHT, center=(0.0, 3.5, 3.0), color=(0.5, 0.5, 0.5))
+    return _shade_globals(b, b.globals((0.5, 1.25, 6.5), (0.0, 0.75, 0.0), 0.0625, 6.0))
+
+
+def shade_textured(pixels, width, height):
+    """A textured triangle with UV vertices and a textured CheckerboardWithHole floor with a border (getUV
+    types 1 and 2; its hole type 0) under one point light. pixels: width * height * 3 bytes, kept alive by
+    the returned keepalive."""
+    import ctypes
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    b.shape(CHECKER_HOLE, v=[(-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4),
+                             (1.5, 0, 2.5), (2.5, 0, 2.5), (2.5, 0, 1.5), (1.5, 0, 1.5)],
+            color=(0.58, 0.82, 1.0), color1=(0.58, 0.82, 1.0), color2=(1.0, 0.416, 0.835), S=2.0, length=8.0, width=8.0,
+            borderwidth=0.25, bordercolor=(0.3, 0.1, 0.4), center=(0, 0, 0), flags=F_TEXTURE, tex_frame=0)
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 4, -4), (-4, 4, -4), (0.0, 0.81, 0.99), flags=0)
+    A, B, C = (-2.5, 0.25, 0.0), (1.5, 0.25, -1.0), (-0.5, 3.0, -1.5)
+    _triangle(b, A, B, C, (0.2, 0.8, 0.3), flags=F_TEXTURE | F_UV_VERTS, tex_frame=0,
+              uv=[(0.0, 0.0), (1.0, 0.125), (0.5, 1.0)])
+    b.light(POINT_LIGHT, center=(0.5, 3.5, 3.0), color=(0.6, 0.6, 0.6))
+    desc, g, keep = _shade_globals(b, b.globals((0.5, 1.5, 6.5), (0.0, 0.5, 0.0), 0.0625, 6.0))
+    buf = (ctypes.c_uint8 * len(pixels)).from_buffer_copy(bytes(pixels))
+    tex = (_lib.TextureDesc * 1)()
+    tex[0].width, tex[0].height, tex[0].channels = width, height, 3
+    tex[0].pixels = ctypes.cast(buf, ctypes.POINTER(ctypes.c_uint8))
+    desc.n_textures, desc.textures = 1, tex
+    return desc, g, (keep, buf, tex)
+
+
+def shade_area():
+    """Area lights without extent: a rectangle light with A == B == D (and C) and a sphere light of radius 0.
+    A + x (B - A) + y (D - A) and radius * (...) + center then do not depend on the draws. Both light objects
+    are shapes of the scene too, but shapes without extent that no shadow ray can hit: this class pins the
+    area-light shadow path and the light colour, not the own-shape skip (shade_own_shape does)."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    _rect(b, (-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), (0.58, 0.82, 1.0), flags=0)
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 4, -4), (-4, 4, -4), (0.0, 0.81, 0.99), flags=0)
+    _cylinder(b, (0.25, 0, 0.5), (0.25, 2.0, 0.5), 1.0, (0.95, 0.64, 0.54))
+    p, q = (-2.5, 3.5, 1.5), (3.0, 3.0, 2.0)
+    rl = b.shape(RECTANGLE, v=[p, p, p, p], color=(0.8, 0.8, 0.8), emit=2, flags=F_LIGHT, length=1.0, width=1.0, center=p)
+    sl = b.shape(SPHERE, v=[q], radius=0.0, color=(1.0, 1.0, 0.9), emit=1, flags=F_LIGHT, center=q)
+    b.light(RECT_LIGHT, rl, center=p, color=(0.45, 0.45, 0.45), A=p, B=p, D=p)
+    b.light(SPHERE_LIGHT, sl, 0.0, center=q, color=(0.35, 0.35, 0.3))
+    return _shade_globals(b, b.globals((0.5, 1.25, 6.5), (0.0, 0.75, 0.0), 0.0625, 6.0))
+
+
+def shade_own_shape():
+    """The light-is-this-shape skip of the shadow loop: a rectangle light WITH extent, a shape of the scene,
+    over a floor and a low wall of the raw model. A raw surface's contribution is its own colour whatever the
+    light's direction, so a sample's colour depends on the draws only through the shadow verdict; nothing but
+    the light's own rectangle lies on a segment to a point of it, so every draw is unoccluded once the own
+    shape is skipped (the surface's colour) -- and occluded by it, 1e-3 before t_max, if it were not (black).
+    No sphere light: sphereLight::sampleRay returns the sampled point itself (Q11), a direction that does not
+    aim at the sphere, so its own-shape skip is out of a deterministic scene's reach."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    _rect(b, (-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), (0.58, 0.82, 1.0), flags=0, model=RAW)
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 2, -4), (-4, 2, -4), (0.0, 0.81, 0.99), flags=0, model=RAW)
+    ra, rb, rc, rd = (-3.0, 3.5, 1.0), (-2.0, 3.5, 1.0), (-2.0, 3.5, 0.0), (-3.0, 3.5, 0.0)
+    rl = b.shape(RECTANGLE, v=[ra, rb, rc, rd], color=(0.8, 0.8, 0.8), emit=2, flags=F_LIGHT, length=1.0, width=1.0,
+                 center=(-2.5, 3.5, 0.5))
+    b.light(RECT_LIGHT, rl, center=(-2.5, 3.5, 0.5), color=(0.45, 0.45, 0.45), A=ra, B=rb, D=rd)
+    return _shade_globals(b, b.globals((0.5, 1.25, 6.5), (0.0, 0.75, 0.0), 0.0625, 6.0))
+
+
+def shade_grazing():
+    """The mirror branch's `refl_ray . n > eps` cut (eps = 1e-3f). The camera looks level from y = 1 through a
+    lens of 2^-10, so the rays of pixel row 8 are level to 1e-4; a steel strip rises towards the back by
+    1.1e-3 per unit and meets them about 3.6 away. Along the row |ray| grows from 1 to 1.25, so the cosine
+    between ray and strip runs from about 1.2e-3 in the middle to 0.8e-3 at the ends: rays on both sides of
+    the cut. The reflected rays climb to the (wide) back wall. Every other row passes over or under the strip."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    _rect(b, (-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), (0.58, 0.82, 1.0), flags=0)
+    _rect(b, (-12, 0, -4), (12, 0, -4), (12, 4, -4), (-12, 4, -4), (0.9, 0.5, 0.2), flags=0)   # wide: every reflection meets it
+    y = lambda z: 1.0 + 1.1e-3 * (2.9 - z)
+    _rect(b, (-4, y(5.0), 5.0), (4, y(5.0), 5.0), (4, y(0.0), 0.0), (-4, y(0.0), 0.0), (0.8, 0.8, 0.8), flags=0,
+          material=STEEL)
+    _cylinder(b, (-1.5, 0, -1.5), (-1.5, 1.5, -1.5), 0.5, (0.9, 0.3, 0.2))
+    b.light(POINT_LIGHT, center=(-2.5, 3.5, 2.5), color=(0.4, 0.4, 0.4))
+    b.light(POINT_LIGHT, center=(3.0, 3.0, 3.0), color=(0.3, 0.3, 0.3))
+    return _shade_globals(b, b.globals((0.0, 1.0, 6.5), (0.0, 1.0, 0.0), 2.0 ** -10, 6.0))
+
+
+# class name -> scene function; the wave5 scenes are 8 x 4 pixels at 64 spp (2048 rays: the smallest image
+# that selects the 5-wave builds), "averaged" 16 x 8 at 4 spp
+SHADE_SCENES = {
+    "phong": lambda: shade_model(PHONG),
+    "oren-nayar": lambda: shade_model(OREN_NAYAR),
+    "cook-torrance": lambda: shade_model(COOK_TORRANCE),
+    "raw": lambda: shade_model(RAW),
+    "mirror": shade_mirror,
+    "glass": shade_glass,
+    "emitters": shade_emitters,
+    "area": shade_area,
+    "wave5-phong": lambda: shade_model(PHONG, triangle=False, res=(8, 4), spp=64),
+    "wave5-cook-torrance": lambda: shade_model(COOK_TORRANCE, triangle=False, res=(8, 4), spp=64),
+    "wave5-oren-nayar": lambda: shade_model(OREN_NAYAR, res=(8, 4), spp=64),
+    "averaged": lambda: shade_model(PHONG, res=(16, 8), spp=4),
+    # mesh-featured twins: the 4-wave and 5-wave mesh builds get the mirror, Phong and Cook-Torrance loops too
+    "mirror-mesh": lambda: shade_mirror(triangle=True),
+    "wave5-phong-mesh": lambda: shade_model(PHONG, res=(8, 4), spp=64),
+    "wave5-cook-torrance-mesh": lambda: shade_model(COOK_TORRANCE, res=(8, 4), spp=64),
+    "own-shape": shade_own_shape,
+    "grazing": shade_grazing,
+}
