@@ -15,7 +15,7 @@ an error (there is no CPU path in this package).
 import ctypes
 
 from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT, DT_OUT_IMAGE, DT_OUT_SLAB, AccelInfo, BVHNode, Camera, DenoiseParams, DenoiseVarParams, DTError, Globals, SceneDesc,
-                   OcclusionParams, Stats, TemporalParams, Tiles, UpsampleParams, check, lib)
+                   SHAPE_TYPES, OcclusionParams, Stats, TemporalParams, Tiles, UpsampleParams, check, lib)
 
 __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_scene", "Scene",
            "render", "render_sky", "renderImage", "renderImageCloud", "write_ppm", "DATA_DIR",
@@ -31,7 +31,7 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "render_mattes", "matte_mask", "shape_groups", "MATTE_PLANES",
            "UpsampleParams", "upsample_params_default", "upsample", "low_res_globals",
            "OcclusionParams", "occlusion_params_default", "render_occlusion", "occlusion_ao_ray", "occlusion_light_ray",
-           "occlusion_images"]
+           "occlusion_images", "points_occlusion", "shape_texels", "bake_occlusion"]
 
 
 def globals_default():
@@ -371,6 +371,98 @@ def render_occlusion(scene, g, frame, n_samples=None, ao_rays=4, ao_radius=None,
     check(lib.dt_render_occlusion(scene.handle, ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None, n,
                                   ctypes.byref(p), ctypes.byref(o), side or 0,
                                   ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)), "dt_render_occlusion")
+    return out, st
+
+
+def points_occlusion(scene, g, points, normals, frame=0, n_samples=16, ao_rays=4, ao_radius=None, lights=(),
+                     stream=None):
+    """Occlusion at surface points the caller supplies (include/dt.h dt_points_occlusion), for baking: points and
+    normals are float64, shaped (n, 3) or flat, numpy arrays or torch tensors, both on one side; a normal is
+    used as given (unit length and pointing away from the surface is the caller's business). Point i takes
+    n_samples samples of render_occlusion's probes with pixel = i: ao_rays ambient-occlusion probes (ao_radius
+    None: occlusion_params_default's constant) and one probe per light of `lights`. Returns (dict(ao=...,
+    light=...), stats) on the side of points: `ao` float32 (n,), only with ao_rays > 0; `light` float32
+    (n, len(lights)), only with lights. A point with a non-finite component gets zeros. 64 consecutive points
+    share a wave: keep neighbours in the arrays neighbours in space."""
+    from ._lib import Occlusion
+    n, pp, np_, side = _ray_arrays("points_occlusion", points, normals)
+    p = OcclusionParams()
+    p.ao_rays, p.n_lights = int(ao_rays), len(lights)
+    if len(lights) > len(p.lights):
+        raise DTError("points_occlusion: %d lights, at most %d" % (len(lights), len(p.lights)))
+    for j, l in enumerate(lights):
+        p.lights[j] = int(l)
+    if p.ao_rays > 0:
+        p.ao_radius = occlusion_params_default().ao_radius if ao_radius is None else float(ao_radius)
+    out, o = {}, Occlusion()
+    none = ctypes.cast(_NO_RAYS, ctypes.c_void_p)
+    if p.ao_rays > 0:
+        out["ao"] = _ray_new(points, (n,), "torch.float32", "float32")
+        o.ao = _ptr(out["ao"])[0].value or none.value
+    if lights:
+        out["light"] = _ray_new(points, (n, len(lights)), "torch.float32", "float32")
+        o.light = _ptr(out["light"])[0].value or none.value
+    st = Stats()
+    check(lib.dt_points_occlusion(scene.handle, ctypes.byref(g), int(frame), n, pp, np_, int(n_samples), ctypes.byref(p),
+                                  ctypes.byref(o), side, ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)),
+          "dt_points_occlusion")
+    return out, st
+
+
+def _shape_texels(desc, shape_index, width, height, side):
+    """shape_texels' arrays and the indices v*width + u of the texels kept"""
+    import numpy as np
+    d = desc.desc if isinstance(desc, BuiltScene) else desc
+    shape_index, width, height = int(shape_index), int(width), int(height)
+    if not 0 <= shape_index < int(d.n_shapes):
+        raise DTError("shape_texels: shape %d, the scene has %d shapes" % (shape_index, int(d.n_shapes)))
+    if width < 1 or height < 1:
+        raise DTError("shape_texels: width and height must be >= 1")
+    RECTANGLE, CHECKERBOARD, TRIANGLE = 4, 6, 3
+    s = d.shapes[shape_index]
+    if s.type not in (RECTANGLE, CHECKERBOARD, TRIANGLE):
+        raise DTError("shape_texels: shape %d is a %s; a rectangle, checkerboard or triangle is needed"
+                      % (shape_index, SHAPE_TYPES.get(s.type, s.type)))
+    A = np.array(s.v[0][:], np.float64)
+    e1 = np.array(s.v[1][:], np.float64) - A
+    e2 = np.array(s.v[2 if s.type == TRIANGLE else 3][:], np.float64) - A
+    a = np.tile((np.arange(width) + 0.5) / width, height)
+    b = np.repeat((np.arange(height) + 0.5) / height, width)
+    keep = np.flatnonzero(a + b <= 1.0) if s.type == TRIANGLE else np.arange(width * height)
+    a, b = a[keep], b[keep]
+    points = (A[None, :] + a[:, None] * e1[None, :]) + b[:, None] * e2[None, :]
+    # (each operation one rounded f64 one, in this order: dtrender --bake-occlusion computes the same bits)
+    nrm = np.array([e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]])
+    length = np.sqrt((nrm[0] * nrm[0] + nrm[1] * nrm[1]) + nrm[2] * nrm[2])
+    if not (np.isfinite(length) and length > 0):
+        raise DTError("shape_texels: shape %d has no area" % shape_index)
+    nrm = float(side) * (nrm / length)
+    return np.ascontiguousarray(points), np.ascontiguousarray(np.tile(nrm, (len(keep), 1))), keep
+
+
+def shape_texels(desc, shape_index, width, height, side=1):
+    """The texel centres of a width x height lightmap over a DT_SHAPE_RECTANGLE, DT_SHAPE_CHECKERBOARD or
+    DT_SHAPE_TRIANGLE shape of a scene descriptor (a BuiltScene or a SceneDesc), as points_occlusion takes them:
+    (points, normals), float64 (n, 3), texel (u, v) at row v*width + u. With e1 = B - A and e2 = D - A (a
+    triangle: C - A), the centre is A + ((u+0.5)/width)*e1 + ((v+0.5)/height)*e2 and the normal
+    side * normalized(cross(e1, e2)); of a triangle only the texels whose centre lies inside it are kept, in the
+    same order. Pure numpy, no device. Neighbouring rows are neighbouring texels, which is what the kernel's
+    waves want."""
+    return _shape_texels(desc, shape_index, width, height, side)[:2]
+
+
+def bake_occlusion(scene, desc, g, shape_index, width, height, side=1, **kw):
+    """A lightmap of one shape: points_occlusion(scene, g, *shape_texels(desc, shape_index, width, height, side),
+    **kw) as numpy images, (dict(ao=(height, width), light=(height, width, n_lights)), stats), row v, column u.
+    A triangle's texels outside it are 0."""
+    import numpy as np
+    points, normals, keep = _shape_texels(desc, shape_index, width, height, side)
+    planes, st = points_occlusion(scene, g, points, normals, **kw)
+    out = {}
+    for name, a in planes.items():
+        img = np.zeros((int(height) * int(width),) + a.shape[1:], np.float32)
+        img[keep] = a
+        out[name] = img.reshape((int(height), int(width)) + a.shape[1:])
     return out, st
 
 

@@ -124,6 +124,7 @@ class Occlusion(ctypes.Structure):
 DT_OCCL_MAX_AO_RAYS = 16
 DT_OCCL_MAX_LIGHTS = 8
 DT_OCCL_TRIES = 16
+DT_POCCL_MAX_SAMPLES = 1024
 DT_MATTE_TABLE = 64       # distinct groups a pixel's histogram holds
 DT_MATTE_MAX_LAYERS = 8
 
@@ -204,7 +205,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_trace_rays", "dt_rays_occluded", "dt_render_mattes", "dt_matte_mask",
            "dt_upsample_params_default", "dt_upsample",
            "dt_guide_bounce", "dt_render_features_path",
-           "dt_occlusion_params_default", "dt_render_occlusion", "dt_occlusion_ao_ray", "dt_occlusion_light_ray"]
+           "dt_occlusion_params_default", "dt_render_occlusion", "dt_occlusion_ao_ray", "dt_occlusion_light_ray",
+           "dt_points_occlusion"]
 
 
 class DTError(RuntimeError):
@@ -298,6 +300,8 @@ def _load():
                                           P(c_double), P(c_double), P(c_double)]),
         "dt_occlusion_light_ray": (c_int32, [ctypes.c_uint32, c_int32, ctypes.c_uint32, ctypes.c_uint32, c_int32,
                                              P(LightDesc), P(c_double), P(c_double)]),
+        "dt_points_occlusion": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                          c_int32, P(OcclusionParams), P(Occlusion), c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_trace_rays": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p, P(RayHits),
                                     c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_rays_occluded": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p,

@@ -83,6 +83,11 @@ extern "C" const void* dt_mattes_kernel_ptr(void);
 extern "C" hipError_t dt_launch_occlusion(const void* dev_launch, int n_samples, int ao_rays, float ao_radius, int n_lights,
                                           const void* lights, float* ao, float* light, int grid, hipStream_t stream);
 extern "C" const void* dt_occlusion_kernel_ptr(void);
+extern "C" hipError_t dt_launch_points_occl(const void* dev_launch, uint32_t seed, int32_t frame, int64_t n,
+                                            const double* point, const double* normal, int n_samples, int ao_rays,
+                                            float ao_radius, int n_lights, const void* lights, float* ao, float* light,
+                                            int grid, hipStream_t stream);
+extern "C" const void* dt_points_occl_kernel_ptr(void);
 
 namespace {
 
@@ -1911,17 +1916,12 @@ void dt_occlusion_params_default(dt_occlusion_params* p)
   p->ao_radius = 1.0f;   // one world unit (include/dt.h: a choice, not a measurement)
 }
 
-int dt_render_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t n_samples,
-                        const dt_occlusion_params* params, const dt_occlusion* out, int32_t out_on_device, void* stream,
-                        dt_stats* stats)
+// The rules dt_render_occlusion and dt_points_occlusion share for params and out (both non-null), under the
+// caller's prefix: the counts and the radius, planes given without their count, every plane NULL, then (the
+// scene is looked at only from there on) the light indices and the RectPrismWithCylinder rule.
+static int check_occlusion(const std::string& who, const dt_scene* sc, const dt_occlusion_params* params,
+                           const dt_occlusion* out)
 {
-  dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  const std::string who = "dt_render_occlusion: ";
-  if (!sc) return fail(DT_E_INVALID, who + "null scene");
-  if (!g) return fail(DT_E_INVALID, who + "null globals");
-  if (!params) return fail(DT_E_INVALID, who + "null params");
-  if (!out) return fail(DT_E_INVALID, who + "null out");
-  if (int rc = dt_window_check(g, 0, n_samples)) return fail(rc, who + "n_samples: " + g_err);
   if (params->ao_rays < 0 || params->ao_rays > DT_OCCL_MAX_AO_RAYS)
     return fail(DT_E_INVALID, who + "ao_rays " + std::to_string(params->ao_rays) + " outside 0.." +
                                   std::to_string(DT_OCCL_MAX_AO_RAYS));
@@ -1940,15 +1940,14 @@ int dt_render_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame
       return fail(DT_E_INVALID, who + "lights[" + std::to_string(j) + "] = " + std::to_string(params->lights[j]) +
                                     ", the scene has " + std::to_string(scene_lights) + " lights");
   if (sc->no_cull) return fail(DT_E_UNSUPPORTED, who + "scenes with a RectPrismWithCylinder");
-  // a plane that is not wanted costs no probes
-  const int ao_rays = out->ao ? params->ao_rays : 0, n_lights = out->light ? params->n_lights : 0;
-  dtd::DParams P;
-  std::vector<float> zs;
-  if (int rc = prepare_render(sc, g, frame, tiles, P, zs)) return rc;
-  AuxLaunch aux(stream);
-  if (int rc = aux.begin(sc, P, true)) return rc;
-  dtd::OcclLight recs[DT_OCCL_MAX_LIGHTS];
-  memset(recs, 0, sizeof(recs));
+  return DT_OK;
+}
+
+// the records of the chosen lights that travel with a launch (dt_occl.h OcclLight, from the scene's flattened lights)
+static void occlusion_lights(const dt_scene* sc, const dt_occlusion_params* params, int n_lights,
+                             dtd::OcclLight recs[DT_OCCL_MAX_LIGHTS])
+{
+  memset(recs, 0, sizeof(dtd::OcclLight) * DT_OCCL_MAX_LIGHTS);
   for (int j = 0; j < n_lights; ++j) {
     const dtd::DLight& L = sc->flat.lights[params->lights[j]];
     dtd::OcclLight& o = recs[j];
@@ -1957,6 +1956,29 @@ int dt_render_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame
     o.radius = L.radius;
     for (int k = 0; k < 3; ++k) { o.center[k] = L.center[k]; o.A[k] = L.A[k]; o.B[k] = L.B[k]; o.D[k] = L.D[k]; }
   }
+}
+
+int dt_render_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t n_samples,
+                        const dt_occlusion_params* params, const dt_occlusion* out, int32_t out_on_device, void* stream,
+                        dt_stats* stats)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  const std::string who = "dt_render_occlusion: ";
+  if (!sc) return fail(DT_E_INVALID, who + "null scene");
+  if (!g) return fail(DT_E_INVALID, who + "null globals");
+  if (!params) return fail(DT_E_INVALID, who + "null params");
+  if (!out) return fail(DT_E_INVALID, who + "null out");
+  if (int rc = dt_window_check(g, 0, n_samples)) return fail(rc, who + "n_samples: " + g_err);
+  if (int rc = check_occlusion(who, sc, params, out)) return rc;
+  // a plane that is not wanted costs no probes
+  const int ao_rays = out->ao ? params->ao_rays : 0, n_lights = out->light ? params->n_lights : 0;
+  dtd::DParams P;
+  std::vector<float> zs;
+  if (int rc = prepare_render(sc, g, frame, tiles, P, zs)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, true)) return rc;
+  dtd::OcclLight recs[DT_OCCL_MAX_LIGHTS];
+  occlusion_lights(sc, params, n_lights, recs);
   void* dlights = nullptr;
   if (n_lights > 0)
     if (int rc = aux.plane(recs, sizeof(recs), false, true, false, &dlights)) return rc;
@@ -1979,6 +2001,62 @@ int dt_render_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame
     stats->rays = stats->samples;
     stats->shadow_rays = aux.h[ST_SHADOW];
     stats->prism_norm_fallback = aux.h[ST_PRISM];
+    stats->kernel_ms = aux.kernel_ms;
+  }
+  return DT_OK;
+}
+
+// Occlusion queries at surface points: dt_points_occl_kernel over the caller's points, one lane per point. As a
+// ray query it takes only the traversal parameters from g (prepare_whole at frame 0, as dt_rays_occluded, so
+// that a probe is answered as that call answers it); the RNG key (g->seed, frame) travels as kernel
+// arguments. It neither reads nor rebuilds the primary-ray lists.
+int dt_points_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame, int64_t n_points, const double* point,
+                        const double* normal, int32_t n_samples, const dt_occlusion_params* params,
+                        const dt_occlusion* out, int32_t on_device, void* stream, dt_stats* stats)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  const std::string who = "dt_points_occlusion: ";
+  if (!sc) return fail(DT_E_INVALID, who + "null scene");
+  if (!g) return fail(DT_E_INVALID, who + "null globals");
+  if (!point) return fail(DT_E_INVALID, who + "null point");
+  if (!normal) return fail(DT_E_INVALID, who + "null normal");
+  if (!params) return fail(DT_E_INVALID, who + "null params");
+  if (!out) return fail(DT_E_INVALID, who + "null out");
+  if (n_points < 0) return fail(DT_E_INVALID, who + "n_points < 0");
+  if (n_points >= (int64_t)1 << 32) return fail(DT_E_INVALID, who + "n_points >= 2^32 (a point is the RNG counter's pixel)");
+  if (n_samples < 1 || n_samples > DT_POCCL_MAX_SAMPLES)
+    return fail(DT_E_INVALID, who + "n_samples " + std::to_string(n_samples) + " outside 1.." +
+                                  std::to_string(DT_POCCL_MAX_SAMPLES));
+  if (int rc = check_occlusion(who, sc, params, out)) return rc;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n_points == 0) return DT_OK;
+  // a plane that is not wanted costs no probes
+  const int ao_rays = out->ao ? params->ao_rays : 0, n_lights = out->light ? params->n_lights : 0;
+  dtd::DParams P;
+  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, false)) return rc;
+  dtd::OcclLight recs[DT_OCCL_MAX_LIGHTS];
+  occlusion_lights(sc, params, n_lights, recs);
+  void* dlights = nullptr;
+  if (n_lights > 0)
+    if (int rc = aux.plane(recs, sizeof(recs), false, true, false, &dlights)) return rc;
+  const size_t n = (size_t)n_points;
+  void *dpoint = nullptr, *dnormal = nullptr, *dao = nullptr, *dlight = nullptr;
+  if (int rc = aux.plane(point, 3 * n * sizeof(double), on_device, true, false, &dpoint)) return rc;
+  if (int rc = aux.plane(normal, 3 * n * sizeof(double), on_device, true, false, &dnormal)) return rc;
+  if (int rc = aux.plane(out->ao, n * sizeof(float), on_device, false, true, &dao)) return rc;
+  if (int rc = aux.plane(out->light, n * (size_t)params->n_lights * sizeof(float), on_device, false, true, &dlight))
+    return rc;
+  static int resident = 0;
+  const int grid = aux_grid(dt_points_occl_kernel_ptr(), resident, (n_points + 63) / 64);
+  if (int rc = aux.start()) return rc;
+  if (int rc = aux.finish(dt_launch_points_occl(aux.launch, (uint32_t)g->seed, frame, n_points, (const double*)dpoint,
+                                                (const double*)dnormal, n_samples, ao_rays, params->ao_radius, n_lights,
+                                                dlights, (float*)dao, (float*)dlight, grid, aux.st)))
+    return rc;
+  if (stats) {
+    stats->shadow_rays = aux.h[ST_SHADOW];
     stats->kernel_ms = aux.kernel_ms;
   }
   return DT_OK;

@@ -109,7 +109,12 @@ using namespace dtd;
 #ifndef DT_OCCL
 #define DT_OCCL 0
 #endif
-#if DT_OCCL
+// DT_POCCL=1 (a tenth compilation, build/dt_kernels_poccl.o): only dt_points_occl_kernel, the occlusion
+// queries of dt_points_occlusion at surface points the caller supplies, for the same reason
+#ifndef DT_POCCL
+#define DT_POCCL 0
+#endif
+#if DT_OCCL || DT_POCCL
 #include "dt_occl.h"
 #endif
 // DT_W5=1 (build/dt_kernels_w5.o): the trace kernel at 5 waves per SIMD (96 VGPRs, under 8 KiB of
@@ -3995,6 +4000,104 @@ extern "C" hipError_t dt_launch_occlusion(const void* dev_launch, int n_samples,
   return hipGetLastError();
 }
 extern "C" const void* dt_occlusion_kernel_ptr(void) { return (const void*)dt_occlusion_kernel; }
+#elif DT_POCCL
+// Occlusion queries at surface points (include/dt.h dt_points_occlusion; no reference counterpart): the probes
+// of dt_occlusion_kernel from points and normals the caller hands over, 3 doubles each, in place of the
+// camera's first hits. One point per lane, 64 consecutive points per wave, grid-stride over the waves as
+// dt_rayq_occl_kernel; the lane's point is the RNG counter's pixel, its sample loop the counter's sample.
+// Probes are generated in registers (dt_occl.h, the one definition) and answered as dt_rayq_occl_kernel
+// answers a ray: make_walk + occluded_walk<0/1>, tree walks only, one call site.
+// The loops are wave-uniform: row 0 is the AO plane (probe t = sample * ao_rays + r), row 1 + j light slot j
+// (probe t = sample), whose skip shape is the light's own, one value for the wave: one walk per probe index,
+// never one per lane. A lane counts its own unoccluded probes in a register and stores one float per row
+// (integers: no summation order). A tail lane or a void point (a non-finite component) is an inactive lane
+// of every walk: it stays in the wave, is never probed, and a void point stores 0.
+extern "C" __global__ void __launch_bounds__(64)
+dt_points_occl_kernel(const DLaunch* __restrict__ Lp, uint32_t seed, int32_t frame, int64_t n,
+                      const double* __restrict__ point, const double* __restrict__ normal, int n_samples, int ao_rays,
+                      float ao_radius, int n_lights, const dtd::OcclLight* __restrict__ lights,
+                      float* __restrict__ ao_out, float* __restrict__ light_out)
+{
+  const DScene& S = Lp->S;
+  const DParams& P = Lp->P;
+  const int lane = threadIdx.x;
+  __shared__ unsigned int wc_lds[WC_N];
+  if (lane < WC_N) wc_lds[lane] = 0;
+  __syncthreads();
+  Counters cnt;
+  cnt.wc = wc_lds;
+  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
+  unsigned long long traced = 0;   // wave-uniform
+  for (int64_t base = (int64_t)blockIdx.x * DT_WAVE; base < n; base += (int64_t)gridDim.x * DT_WAVE) {
+    const int64_t i = base + lane;
+    const bool in = i < n;
+    V3 p = v3(0, 0, 0), nrm = v3(0, 0, 0);
+    bool live = false;
+    if (in) {
+      const V3 pi = v3(point[3 * i], point[3 * i + 1], point[3 * i + 2]);
+      const V3 ni = v3(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]);
+      live = isfinite(pi.x) && isfinite(pi.y) && isfinite(pi.z) && isfinite(ni.x) && isfinite(ni.y) && isfinite(ni.z);
+      if (live) {
+        p = pi;
+        nrm = ni;
+      }
+    }
+    const uint32_t pixel = (uint32_t)i;
+    const bool any_live = __ballot(live) != 0;   // wave-uniform: a wave of void points runs no probe loop
+    for (int row = ao_rays > 0 ? 0 : 1; row <= n_lights; ++row) {
+      const int per = row == 0 ? ao_rays : 1;
+      const int n_probes = any_live ? n_samples * per : 0;
+      dtd::OcclLight L = {};
+      int skip = -1;
+      if (row > 0) {
+        L = lights[row - 1];   // wave-uniform
+        skip = uni(L.shape_index);
+      }
+      unsigned int V = 0;
+      for (int t = 0; t < n_probes; ++t) {
+        const int sample = t / per, r = t - sample * per;
+        V3 sray = v3(0, 0, 0);
+        if (live) {
+          if (row == 0) sray = dtd::occl_ao_dir(seed, frame, pixel, (uint32_t)sample, r, ao_radius, nrm);
+          else sray = dtd::occl_light_dir(seed, frame, pixel, (uint32_t)sample, row - 1, L, p);
+        }
+        // a void probe (dt_rays_occluded's rule) is an inactive lane, as in dt_rayq_occl_kernel
+        const bool act = live && isfinite(sray.x) && isfinite(sray.y) && isfinite(sray.z) &&
+                         (sray.x != 0 || sray.y != 0 || sray.z != 0);
+        if (!act) sray = v3(0, 0, 0);
+        const V3 org = act ? p : v3(0, 0, 0);
+        const float t_max = (float)norm(sray);
+        const V3 sn = act ? normalized(sray) : v3(1, 0, 0);
+        const V3 bstart = add(org, mul(1e-3, sray)), sstart = add(org, mul(1e-3, sn));
+        const unsigned long long am = __ballot(act);
+        traced += (unsigned long long)__popcll(am);
+        bool occl = false;
+        if (am) {
+          const Walk w = make_walk(P, act, sray, bstart, 0.0f);
+          const bool o = w.inf_wave ? occluded_walk<1>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt)
+                                    : occluded_walk<0>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt);
+          occl = act && o;
+        }
+        if (live && !occl) ++V;
+      }
+      if (in) {
+        if (row == 0) ao_out[i] = live ? (float)((double)V / ((double)n_samples * (double)ao_rays)) : 0.0f;
+        else light_out[(int64_t)n_lights * i + (row - 1)] = live ? (float)((double)V / (double)n_samples) : 0.0f;
+      }
+    }
+  }
+  if (lane == 0 && traced) atomicAdd(S.stats + ST_SHADOW, traced);
+}
+extern "C" hipError_t dt_launch_points_occl(const void* dev_launch, uint32_t seed, int32_t frame, int64_t n,
+                                            const double* point, const double* normal, int n_samples, int ao_rays,
+                                            float ao_radius, int n_lights, const void* lights, float* ao, float* light,
+                                            int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(dt_points_occl_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, seed, frame, n,
+                     point, normal, n_samples, ao_rays, ao_radius, n_lights, (const dtd::OcclLight*)lights, ao, light);
+  return hipGetLastError();
+}
+extern "C" const void* dt_points_occl_kernel_ptr(void) { return (const void*)dt_points_occl_kernel; }
 #elif DT_MATTE
 // Object mattes (include/dt.h dt_render_mattes; no reference counterpart): for the samples 0 .. n_samples-1 of
 // every owned pixel the render's own primary ray to its closest hit, as dt_features_kernel takes it (items
@@ -5008,7 +5111,7 @@ extern "C" hipError_t dt_launch_unpack(const void* dev_launch, int world, int64_
 }
 #endif
 
-#if !DT_ISECT && !DT_FEAT && !DT_RAYQ && !DT_MATTE && !DT_FEATP && !DT_OCCL
+#if !DT_ISECT && !DT_FEAT && !DT_RAYQ && !DT_MATTE && !DT_FEATP && !DT_OCCL && !DT_POCCL
 // every trace-kernel build: <kernel>_launch and <kernel>_ptr (dt_api.cpp's kernel table)
 #if DT_W5
 static_assert(DT_TRACE_MIN_WAVES == 5 && DT_PSUM_LDS == 2, "5-wave build: Makefile W5FLAGS");

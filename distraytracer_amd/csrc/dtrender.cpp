@@ -48,6 +48,13 @@
 //                     0..16, default 4; --ao-radius R world units, default 1.0) and PREFIX.light<j>.png for
 //                     the j-th light of --occlusion-lights 0,1,... (indices into the scene's lights, at most 8;
 //                     default none). The frame file is the same bytes as without the flag.
+//   --bake-occlusion SHAPE  after the frame, a lightmap of shape SHAPE of the scene (a rectangle, checkerboard or
+//                     triangle; dt_points_occlusion): --bake-size WxH texels, texel (u, v) centred at
+//                     A + ((u+0.5)/W)*(B-A) + ((v+0.5)/H)*(D-A) (a triangle: C-A, texels outside it stay 0), the
+//                     normal normalized(cross(B-A, D-A)), as distraytracer_amd.shape_texels; --bake-samples N
+//                     samples per texel (default 16) of --ao-rays / --ao-radius / --occlusion-lights probes,
+//                     written as --bake-out P: P.ao.png and P.light<j>.png, W x H, row v, grey value*255 as
+//                     --occlusion. Without the flag every byte written is the same as before.
 //   --guide-bounces K the feature buffers of --features, --denoise, --denoise-variance and --upsample are the
 //                     specular-path ones (dt_render_features_path, K = 1..8 perfect specular bounces): the
 //                     guides describe what mirrors and glass show, not the reflector. Without it (or with 0)
@@ -195,6 +202,42 @@ static int write_upsampled(const dt_scene_desc* desc, const dt_scene* s, const d
   return 0;
 }
 
+// --ao-rays, --ao-radius and --occlusion-lights as dt_occlusion_params (--occlusion, --bake-occlusion)
+static bool occlusion_params(int ao_rays, double ao_radius, const std::string& lights, dt_occlusion_params& op)
+{
+  dt_occlusion_params_default(&op);
+  op.ao_rays = ao_rays;
+  for (const char* c = lights.c_str(); *c;) {
+    char* end = nullptr;
+    const long l = strtol(c, &end, 10);
+    if (end == c || op.n_lights >= DT_OCCL_MAX_LIGHTS) {
+      fprintf(stderr, "usage: --occlusion-lights takes at most %d comma-separated light indices\n", DT_OCCL_MAX_LIGHTS);
+      return false;
+    }
+    op.lights[op.n_lights++] = (int32_t)l;
+    c = *end == ',' ? end + 1 : end;
+  }
+  if (ao_radius >= 0.0) op.ao_radius = (float)ao_radius;
+  return true;
+}
+
+// the grey PNGs of occlusion planes of w x h entries: prefix.ao.png (when ao) and prefix.light<j>.png, value*255
+static int write_occlusion_pngs(const std::string& prefix, int w, int h, const float* ao, const float* light, int n_lights)
+{
+  const size_t n_px = (size_t)w * h;
+  std::vector<float> pix(3 * n_px);
+  for (int plane = ao ? -1 : 0; plane < n_lights; ++plane) {
+    for (size_t q = 0; q < n_px; ++q) {
+      const float v = (plane < 0 ? ao[q] : light[(size_t)n_lights * q + plane]) * 255.0f;
+      pix[3 * q] = pix[3 * q + 1] = pix[3 * q + 2] = v;
+    }
+    const std::string pf = prefix + (plane < 0 ? std::string(".ao") : ".light" + std::to_string(plane)) + ".png";
+    const int rc = dt_write_png(pf.c_str(), w, h, pix.data());
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 int main(int argc, char** argv)
 {
   dt_globals g;
@@ -211,6 +254,9 @@ int main(int argc, char** argv)
   std::string occl_prefix, occl_lights;
   int ao_rays = 4;
   double ao_radius = -1.0;   // < 0: dt_occlusion_params_default's
+  int bake_shape = -1, bake_w = 0, bake_h = 0, bake_samples = 16;
+  std::string bake_prefix;
+  bool bake_asked = false;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     if (a == "--out" && i + 1 < argc) out = argv[++i];
@@ -236,9 +282,17 @@ int main(int argc, char** argv)
     else if (a == "--ao-rays" && i + 1 < argc) ao_rays = atoi(argv[++i]);
     else if (a == "--ao-radius" && i + 1 < argc) ao_radius = atof(argv[++i]);
     else if (a == "--occlusion-lights" && i + 1 < argc) occl_lights = argv[++i];
+    else if (a == "--bake-occlusion" && i + 1 < argc) { bake_shape = atoi(argv[++i]); bake_asked = true; }
+    else if (a == "--bake-size" && i + 1 < argc) sscanf(argv[++i], "%dx%d", &bake_w, &bake_h);
+    else if (a == "--bake-out" && i + 1 < argc) bake_prefix = argv[++i];
+    else if (a == "--bake-samples" && i + 1 < argc) bake_samples = atoi(argv[++i]);
   }
   if (guide_bounces < 0 || guide_bounces > DT_GUIDE_MAX_BOUNCES) {
     fprintf(stderr, "usage: --guide-bounces K needs K in 0..%d\n", DT_GUIDE_MAX_BOUNCES);
+    return 2;
+  }
+  if (bake_asked && (bake_shape < 0 || bake_w < 1 || bake_h < 1 || bake_prefix.empty())) {
+    fprintf(stderr, "usage: --bake-occlusion SHAPE (>= 0) needs --bake-size WxH and --bake-out PREFIX\n");
     return 2;
   }
   if (denoise_variance && adaptive < 0.0) {
@@ -301,6 +355,14 @@ int main(int argc, char** argv)
   if (upsample && (upsample < 2 || upsample > 4 || g.xRes % upsample || g.yRes % upsample)) {
     fprintf(stderr, "usage: --upsample S needs S = 2, 3 or 4 and a resolution that S divides (%dx%d)\n", g.xRes, g.yRes);
     return 2;
+  }
+  if (bake_asked) {
+    const int t = bake_shape < desc->n_shapes ? desc->shapes[bake_shape].type : 0;
+    if (t != DT_SHAPE_RECTANGLE && t != DT_SHAPE_CHECKERBOARD && t != DT_SHAPE_TRIANGLE) {
+      fprintf(stderr, "usage: --bake-occlusion %d: a rectangle, checkerboard or triangle of the scene's %d shapes is needed\n",
+              bake_shape, desc->n_shapes);
+      return 2;
+    }
   }
   dt_scene* s = nullptr;
   rc = dt_scene_create(desc, &g, &s);
@@ -497,22 +559,10 @@ int main(int argc, char** argv)
   }
   if (!occl_prefix.empty()) {
     dt_occlusion_params op;
-    dt_occlusion_params_default(&op);
-    op.ao_rays = ao_rays;
-    for (const char* c = occl_lights.c_str(); *c;) {
-      char* end = nullptr;
-      const long l = strtol(c, &end, 10);
-      if (end == c || op.n_lights >= DT_OCCL_MAX_LIGHTS) {
-        fprintf(stderr, "usage: --occlusion-lights takes at most %d comma-separated light indices\n", DT_OCCL_MAX_LIGHTS);
-        return 2;
-      }
-      op.lights[op.n_lights++] = (int32_t)l;
-      c = *end == ',' ? end + 1 : end;
-    }
-    if (ao_radius >= 0.0) op.ao_radius = (float)ao_radius;
+    if (!occlusion_params(ao_rays, ao_radius, occl_lights, op)) return 2;
     const int n = (int)sqrt((double)g.antialias_samples);
     const size_t n_px = (size_t)g.xRes * g.yRes;
-    std::vector<float> ao(n_px, 0.0f), lv(n_px * (size_t)(op.n_lights > 0 ? op.n_lights : 1), 0.0f), pix(3 * n_px);
+    std::vector<float> ao(n_px, 0.0f), lv(n_px * (size_t)(op.n_lights > 0 ? op.n_lights : 1), 0.0f);
     dt_occlusion o;
     memset(&o, 0, sizeof o);
     if (op.ao_rays != 0) o.ao = ao.data();
@@ -520,18 +570,62 @@ int main(int argc, char** argv)
     dt_stats ost;
     rc = dt_render_occlusion(s, &g, frame, nullptr, n * n, &op, &o, 0, nullptr, &ost);
     if (rc) return die("dt_render_occlusion", rc);
-    for (int plane = o.ao ? -1 : 0; plane < op.n_lights; ++plane) {
-      for (size_t q = 0; q < n_px; ++q) {
-        const float v = (plane < 0 ? ao[q] : lv[(size_t)op.n_lights * q + plane]) * 255.0f;
-        pix[3 * q] = pix[3 * q + 1] = pix[3 * q + 2] = v;
-      }
-      const std::string pf = occl_prefix + (plane < 0 ? std::string(".ao") : ".light" + std::to_string(plane)) + ".png";
-      rc = dt_write_png(pf.c_str(), g.xRes, g.yRes, pix.data());
-      if (rc) return die("dt_write_png (occlusion)", rc);
-    }
+    rc = write_occlusion_pngs(occl_prefix, g.xRes, g.yRes, o.ao, lv.data(), op.n_lights);
+    if (rc) return die("dt_write_png (occlusion)", rc);
     printf("occlusion: %llu pixels, %llu probes (%d ao rays of radius %g, %d lights) in %.3f ms (kernel) -> %s.*.png\n",
            (unsigned long long)ost.pixels, (unsigned long long)ost.shadow_rays, op.ao_rays, (double)op.ao_radius,
            op.n_lights, ost.kernel_ms, occl_prefix.c_str());
+  }
+  if (bake_shape >= 0) {
+    dt_occlusion_params op;
+    if (!occlusion_params(ao_rays, ao_radius, occl_lights, op)) return 2;
+    const dt_shape_desc& sh = desc->shapes[bake_shape];
+    const bool tri = sh.type == DT_SHAPE_TRIANGLE;
+    // the texel centres and the normal, each operation one rounded f64 one (shape_texels computes the same bits)
+    double e1[3], e2[3], nrm[3];
+    for (int k = 0; k < 3; ++k) { e1[k] = sh.v[1][k] - sh.v[0][k]; e2[k] = sh.v[tri ? 2 : 3][k] - sh.v[0][k]; }
+    nrm[0] = e1[1] * e2[2] - e1[2] * e2[1];
+    nrm[1] = e1[2] * e2[0] - e1[0] * e2[2];
+    nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
+    const double len = sqrt((nrm[0] * nrm[0] + nrm[1] * nrm[1]) + nrm[2] * nrm[2]);
+    if (!(std::isfinite(len) && len > 0)) {
+      fprintf(stderr, "usage: --bake-occlusion: shape %d has no area\n", bake_shape);
+      return 2;
+    }
+    const size_t n_tex = (size_t)bake_w * bake_h;
+    std::vector<double> pts, nrms;
+    std::vector<size_t> keep;   // texel v*W + u of every point
+    for (int v = 0; v < bake_h; ++v)
+      for (int u = 0; u < bake_w; ++u) {
+        const double a = ((double)u + 0.5) / (double)bake_w, b = ((double)v + 0.5) / (double)bake_h;
+        if (tri && !(a + b <= 1.0)) continue;
+        keep.push_back((size_t)v * bake_w + u);
+        for (int k = 0; k < 3; ++k) {
+          pts.push_back((sh.v[0][k] + a * e1[k]) + b * e2[k]);
+          nrms.push_back(1.0 * (nrm[k] / len));
+        }
+      }
+    const int nl = op.n_lights;
+    std::vector<float> pao(keep.size() + 1, 0.0f), plv(keep.size() * (size_t)(nl > 0 ? nl : 1) + 1, 0.0f);
+    dt_occlusion o;
+    memset(&o, 0, sizeof o);
+    if (op.ao_rays != 0) o.ao = pao.data();
+    if (nl > 0) o.light = plv.data();
+    dt_stats bst;
+    rc = dt_points_occlusion(s, &g, frame, (int64_t)keep.size(), pts.data(), nrms.data(), bake_samples, &op, &o, 0, nullptr,
+                             &bst);
+    if (rc) return die("dt_points_occlusion", rc);
+    std::vector<float> ao(n_tex, 0.0f), lv(n_tex * (size_t)(nl > 0 ? nl : 1), 0.0f);
+    for (size_t i = 0; i < keep.size(); ++i) {
+      ao[keep[i]] = pao[i];
+      for (int j = 0; j < nl; ++j) lv[(size_t)nl * keep[i] + j] = plv[(size_t)nl * i + j];
+    }
+    rc = write_occlusion_pngs(bake_prefix, bake_w, bake_h, o.ao ? ao.data() : nullptr, lv.data(), nl);
+    if (rc) return die("dt_write_png (bake)", rc);
+    printf("bake: shape %d, %dx%d texels, %llu points, %llu probes (%d samples, %d ao rays of radius %g, %d lights) in "
+           "%.3f ms (kernel) -> %s.*.png\n",
+           bake_shape, bake_w, bake_h, (unsigned long long)keep.size(), (unsigned long long)bst.shadow_rays, bake_samples,
+           op.ao_rays, (double)op.ao_radius, nl, bst.kernel_ms, bake_prefix.c_str());
   }
   double msps = st.samples / (st.kernel_ms * 1e-3) / 1e6;
   printf("Rendered %s frame %d: %dx%d, %d spp, depth %d in %.2f ms (kernel, %.1f Mpixel-samples/s) -> %s\n",

@@ -70,6 +70,8 @@ extern "C" {
 /* (still 8, new exports and two new structs, no struct changed: dt_occlusion_params_default,
  *    dt_render_occlusion and its dt_occlusion_params and dt_occlusion, dt_occlusion_ao_ray,
  *    dt_occlusion_light_ray -- occlusion feature buffers: ambient occlusion and per-light visibility) */
+/* (still 8, new exports only, no struct changed: dt_points_occlusion -- occlusion queries at surface points
+ *    the caller supplies, for baking) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -786,6 +788,59 @@ int dt_occlusion_ao_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint32_t s
                         const double p[3], const double n[3], double dir[3]);
 int dt_occlusion_light_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint32_t sample, int32_t j,
                            const dt_light_desc* light, const double p[3], double dir[3]);
+
+/* ---- occlusion queries at surface points: ambient occlusion and light visibility for baking ----
+ * No reference counterpart. dt_render_occlusion asks "how exposed is this surface?" at the camera's own first
+ * hits, dt_rays_occluded for rays the caller builds one by one; this call asks it at surface points the
+ * caller supplies (the texels of a lightmap, probes), with the probes generated on the device: per point 24
+ * bytes of position and 24 of normal go in, one float per plane entry comes out.
+ *
+ * Samples and RNG counter: point i (0 <= i < n_points, n_points < 2^32) takes the samples s = 0 ..
+ * n_samples-1. The RNG counter is dt_render_occlusion's with pixel = (uint32_t)i and sample = s, the key
+ * (g->seed, (uint32_t)frame), the purposes P_AO = 6 and P_OLIGHT = 7; DT_OCCL_TRIES is unchanged.
+ *
+ * Probes: with p = point[3i..3i+2] and n = normal[3i..3i+2], sample s of point i has the ao_rays probes
+ * dt_occlusion_ao_ray(seed, frame, i, s, r, ao_radius, p, n), r = 0 .. ao_rays-1, and per light slot j the probe
+ * dt_occlusion_light_ray(seed, frame, i, s, j, light, p): the rules of dt_render_occlusion, unchanged (one
+ * definition, csrc/dt_occl.h). n is the caller's normal as given: it is not normalised and fixNorm is not
+ * applied (the AO ball rests on the surface only for a unit n that points away from it). Each probe is answered exactly as dt_rays_occluded(start = p, dir, skip_shape)
+ * answers it, with skip_shape = -1 for an AO probe and L.shape_index for a probe towards light L; its
+ * void-ray rule applies: a probe with a zero (or non-finite) dir is not traced and counts as not occluded.
+ *
+ * Sums and outputs: with V the unoccluded AO probes of point i and V_j the unoccluded probes towards slot j,
+ *   ao[i] = (float)((double)V / ((double)n_samples * (double)ao_rays)),
+ *   light[n_lights*i + j] = (float)((double)V_j / (double)n_samples).
+ * The sums are integers, so the outputs do not depend on the order of the work.
+ *
+ * A point is VOID if point or normal has a non-finite component. A void point is never probed, writes 0 to
+ * each of its outputs and counts no probes; its neighbours are unaffected.
+ *
+ * point, normal and the planes of out are all host (on_device=0: staged through temporaries, as
+ * dt_rays_occluded stages its arrays) or all device (1). The call is synchronous, with a launch record,
+ * counters and events of its own; it neither reads nor rebuilds the scene's primary-ray lists, and a render
+ * of the scene afterwards is unaffected. g: as for the ray queries, only what traversal reads and the seed
+ * matter; the camera is not read.
+ * stats (optional): shadow_rays = the probes tested (the non-void ones), kernel_ms; everything else 0. A
+ * plane that is not wanted (NULL while ao_rays > 0 or n_lights > 0) costs no probes.
+ *
+ * Errors, with a dt_last_error starting "dt_points_occlusion: " and naming the argument, all before any
+ * device work: DT_E_INVALID for a null scene, globals, point, normal, params or out, n_points < 0 or
+ * n_points >= 2^32, n_samples outside 1..DT_POCCL_MAX_SAMPLES, and dt_render_occlusion's rules: ao_rays outside
+ * 0..DT_OCCL_MAX_AO_RAYS, n_lights outside 0..DT_OCCL_MAX_LIGHTS, a non-finite or non-positive ao_radius
+ * while ao_rays > 0, a light index outside the scene, out->ao given with ao_rays == 0, out->light given with
+ * n_lights == 0, every plane NULL; DT_E_UNSUPPORTED for a scene with a RectPrismWithCylinder.
+ * n_points == 0: DT_OK, nothing is launched.
+ *
+ * The walk is the renders' wave-uniform one, as for dt_rays_occluded: 64 consecutive points share a wave,
+ * which visits the union of its probes' nodes, one walk per probe index (a light slot skips one shape for the
+ * whole wave, so no grouping by skip_shape is needed). Points that are neighbours in the arrays should be
+ * neighbours in space (README.md). */
+#define DT_POCCL_MAX_SAMPLES 1024
+int dt_points_occlusion(const dt_scene* s, const dt_globals* g, int32_t frame, int64_t n_points,
+                        const double* point, const double* normal,   /* 3 doubles per point each */
+                        int32_t n_samples,                           /* 1..DT_POCCL_MAX_SAMPLES */
+                        const dt_occlusion_params* params, const dt_occlusion* out,
+                        int32_t on_device, void* stream, dt_stats* stats);
 
 /* ---- feature-guided denoising of previews: an edge-avoiding a-trous filter ----
  * No reference counterpart. The consumer of the feature buffers: (preview, albedo, normal, depth) ->
