@@ -57,6 +57,10 @@ def oracle():
         o.or_sample_color.restype = ctypes.c_int
         o.or_sample_color.argtypes = [P(SceneDesc), P(Globals), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, P(ctypes.c_double), P(ctypes.c_int)]
+        o.or_sample_color_log.restype = ctypes.c_int
+        o.or_sample_color_log.argtypes = [P(SceneDesc), P(Globals), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, P(ctypes.c_double), P(ctypes.c_int), P(ctypes.c_int),
+                                          P(ctypes.c_double), ctypes.c_int, P(ctypes.c_int)]
         _o = o
     return _o
 

@@ -322,7 +322,22 @@ typedef struct {
   float shift;     /* motion-blur y shift of "rectangle" shapes + leaf bump (cpp:1106-1160) */
   dt_stats* st;
   uint64_t* wk;    /* include/dt_work.h event counts of the reference's loop (or_render_work), or NULL */
+  struct DrawLog* log;   /* the uniform values ray_color consumes, in order (or_sample_color_log), or NULL */
 } Ctx;
+
+/* Every uniform value handed to rayColor's arithmetic, as the double the reference's uniform(generator)
+   stands for: rect_sample's two, the sphere light's two per attempt, the glossy sample's two per attempt.
+   n counts every draw, v holds the first cap of them. */
+typedef struct DrawLog { double* v; int cap, n; } DrawLog;
+
+static inline void log_draws(const Ctx* c, double u0, double u1)
+{
+  DrawLog* l = c->log;
+  if (!l) return;
+  if (l->n < l->cap) l->v[l->n] = u0;
+  if (l->n + 1 < l->cap) l->v[l->n + 1] = u1;
+  l->n += 2;
+}
 
 #define WK(c, k) do { if ((c)->wk) (c)->wk[(k)]++; } while (0)
 
@@ -1372,6 +1387,7 @@ static V3 light_sample(const Ctx* c, int li, V3 point, uint32_t node)
     uint32_t o[4];
     or_philox4x32(ctr, c->rng.key, o);
     const int k = (li & 1) * 2;
+    log_draws(c, or_u32_01(o[k]), or_u32_01(o[k + 1]));
     return sub(rect_sample(v3a(L->A), v3a(L->B), v3a(L->D), or_u32_01(o[k]), or_u32_01(o[k + 1])), point);
   }
   /* sphereLight::sampleRay returns the sampled point itself (Q11) */
@@ -1380,6 +1396,7 @@ static V3 light_sample(const Ctx* c, int li, V3 point, uint32_t node)
   int attempt = 0;
   double u0, u1;
   rng2(&c->rng, node, P_SPHL, ((uint32_t)li << 8) | (uint32_t)attempt, &u0, &u1);
+  log_draws(c, u0, u1);
   double theta = 2 * M_PI * u0;
   double phi = acos(1 - 2 * u1);
   V3 dir = v3(sin(phi) * cos(theta), sin(phi) * sin(theta), cos(phi));
@@ -1399,6 +1416,7 @@ static V3 light_sample(const Ctx* c, int li, V3 point, uint32_t node)
     }
     attempt++;
     rng2(&c->rng, node, P_SPHL, ((uint32_t)li << 8) | (uint32_t)attempt, &u0, &u1);
+    log_draws(c, u0, u1);
     theta = 2 * M_PI * u0;
     phi = acos(1 - 2 * u1);
     dir = v3(sin(phi) * cos(theta), sin(phi) * sin(theta), cos(phi));
@@ -1559,6 +1577,7 @@ static void ray_color(const Ctx* c, V3 ray, V3 eye, int depth, V3* color, int* h
           double u0, u1;
           WK(c, DT_WK_GLOSSY);
           glossy_xy(&c->rng, node, i, attempt, &u0, &u1);
+          log_draws(c, u0, u1);
           V3 sample_refl = sub(rect_sample(A, B, D, u0, u1), isectP);
           int sample_limit = 10;
           int exhausted = 0;
@@ -1570,6 +1589,7 @@ static void ray_color(const Ctx* c, V3 ray, V3 eye, int depth, V3* color, int* h
             glossy_rect(refl_ray, isectP, multiplier, &A, &B, &C, &D, &wv, &lv);
             attempt++;
             glossy_xy(&c->rng, node, i, attempt, &u0, &u1);
+            log_draws(c, u0, u1);
             sample_refl = sub(rect_sample(A, B, D, u0, u1), isectP);
             sample_limit--;
           }
@@ -1866,13 +1886,14 @@ static int render_setup(RenderCtx* R, const dt_scene_desc* d, const dt_globals* 
 
 /* one sample of renderImage's inner loop (cpp:1062-1211) */
 static void render_sample(const RenderCtx* R, const dt_globals* g, int x, int y, int i, V3* out,
-                          int* out_hit, dt_stats* st, uint64_t* wk)
+                          int* out_hit, dt_stats* st, uint64_t* wk, DrawLog* log, int* out_motion)
 {
   const Cam* cam = &R->cam;
   Ctx c;
   c.s = &R->scene;
   c.st = st;
   c.wk = wk;
+  c.log = log;
   WK(&c, DT_WK_CAMERA);
   c.shift = 0.0f;
   c.rng.key[0] = g->seed;
@@ -1894,6 +1915,7 @@ static void render_sample(const RenderCtx* R, const dt_globals* g, int x, int y,
   int hit = 0, motion = 0;
   ray_color(&c, sub(focalPoint, eye_sample), eye_sample, g->max_depth, &tmp_color, &hit, &motion, 1.0f,
             root_key(0));
+  if (out_motion) *out_motion = motion;   /* of the primary call: the blur passes below overwrite it */
   if (!hit) {
     if (g->perlin_cloud) {
       V3 point = mat4_point(R->frame >= g->frame_cloud ? R->new_mcam : cam->mcam, focalPoint);
@@ -1921,6 +1943,7 @@ static void render_sample(const RenderCtx* R, const dt_globals* g, int x, int y,
       }
       Ctx cm = c;
       cm.shift = val;
+      cm.log = NULL;   /* the log is the primary call tree's */
       WK(&c, DT_WK_CAMERA);
       V3 motion_color = v3(0, 0, 0);
       ray_color(&cm, sub(focalPoint, eye_sample), eye_sample, g->max_depth, &motion_color, &hit, &motion,
@@ -1951,8 +1974,25 @@ int or_sample_color(const dt_scene_desc* d, const dt_globals* g, int frame, int 
   int rc = render_setup(&R, d, g, frame);
   if (rc == DT_OK) {
     V3 col;
-    render_sample(&R, g, x, y, sample, &col, out_hit, NULL, NULL);
+    render_sample(&R, g, x, y, sample, &col, out_hit, NULL, NULL, NULL, NULL);
     out_color[0] = col.x; out_color[1] = col.y; out_color[2] = col.z;
+  }
+  scene_free(&R.scene);
+  return rc;
+}
+
+int or_sample_color_log(const dt_scene_desc* d, const dt_globals* g, int frame, int x, int y, int sample,
+                        double out_color[3], int* out_hit, int* out_in_motion, double* draws, int cap,
+                        int* n_draws)
+{
+  RenderCtx R;
+  int rc = render_setup(&R, d, g, frame);
+  if (rc == DT_OK) {
+    V3 col;
+    DrawLog log = {draws, draws ? cap : 0, 0};
+    render_sample(&R, g, x, y, sample, &col, out_hit, NULL, NULL, &log, out_in_motion);
+    out_color[0] = col.x; out_color[1] = col.y; out_color[2] = col.z;
+    *n_draws = log.n;
   }
   scene_free(&R.scene);
   return rc;
@@ -1971,6 +2011,7 @@ static void primary_ray(const RenderCtx* R, const dt_globals* g, int frame, long
   c->s = &R->scene;
   c->st = NULL;
   c->wk = NULL;
+  c->log = NULL;
   c->shift = 0.0f;
   c->rng.key[0] = g->seed;
   c->rng.key[1] = (uint32_t)frame;
@@ -2221,7 +2262,7 @@ int or_render_work(const dt_scene_desc* d, const dt_globals* g, int frame, const
       V3 color = v3(0, 0, 0);
       for (int i = 0; i < R.sampled_n; i++) {
         V3 tc;
-        render_sample(&R, g, x, y, i, &tc, NULL, &local, work ? wk : NULL);
+        render_sample(&R, g, x, y, i, &tc, NULL, &local, work ? wk : NULL, NULL, NULL);
         color = add(color, tc);
       }
       color = divs(color, R.sampled_n);

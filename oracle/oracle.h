@@ -23,8 +23,10 @@
  *     RectPrismWithCylinder::getNorm where the reference throws or answers from a stale lastHit.
  *   - render_final_project.cpp and helpers.h: rayColor and generateBVH are pinned ray by ray against the
  *     reference's own, included unmodified by oracle/ref/shade_harness.cpp (-> oracle/_ref/libref_shade_cr.so
- *     -> tests/golden/shade_ref.npz, tests/test_oracle_shade.py). Not pinned: glossy and area-light
- *     sampling, the motion-blur re-trace, DoF and jitter generation (the reference's RNG, renderImage).
+ *     -> tests/golden/shade_ref.npz, tests/test_oracle_shade.py); its glossy, rectangle-light and sphere-light
+ *     sampling and in_motion against a draw-tape build fed or_sample_color_log's draws
+ *     (-> tests/golden/shade_sampling_ref.npz, tests/test_oracle_shade_sampling.py). Not pinned: the
+ *     motion-blur re-trace, DoF and jitter generation (renderImage).
  *
  * RNG: the reference draws from random_device-seeded mt19937 (F7) and cannot be
  * reproduced; oracle and device share the counter-based stream documented in
@@ -104,6 +106,16 @@ int  or_segment_intersect(const double A[3], const double B[3], const double ray
 /* one rayColor call tree for a single pixel-sample (debug / unit tests) */
 int or_sample_color(const dt_scene_desc* d, const dt_globals* g, int frame, int x, int y,
                     int sample, double out_color[3], int* out_hit);
+
+/* or_sample_color, also returning what the reference's rayColor would have to be told to answer the same ray
+ * (tests/test_oracle_shade_sampling.py): the uniform values the primary ray_color call tree consumed, in
+ * consumption order, each as the double handed to the arithmetic (or_u32_01 for rect_sample's and the glossy
+ * sample's two, or_u01 for the sphere light's two per attempt), and in_motion as that call left it. The DoF
+ * and blur-time draws happen outside rayColor and are not logged, nor are the blur passes' own draws.
+ * *n_draws counts every draw; draws[0 .. cap-1] receives the first cap of them (draws may be NULL). */
+int or_sample_color_log(const dt_scene_desc* d, const dt_globals* g, int frame, int x, int y, int sample,
+                        double out_color[3], int* out_hit, int* out_in_motion, double* draws, int cap,
+                        int* n_draws);
 
 #ifdef __cplusplus
 }

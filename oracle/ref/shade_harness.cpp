@@ -7,6 +7,8 @@
 // generateBVH; ref_load_texture is its loadTexture; ref_ray_color is one rayColor call tree.
 // tools/gen_golden_shade.py turns the answers into tests/golden/shade_ref.npz. Nothing of the reference
 // is copied here.
+// With -DREF_TAPE (and ref/tape_random.h force-included, here and into a second compile of geometry.cpp)
+// every uniform draw of rayColor's call tree comes from the tape set by ref_tape_set.
 #include "render_final_project.cpp"
 
 #include "../../include/dt.h"
@@ -185,5 +187,26 @@ int ref_bvh(dt_bvh_node* nodes, int cap, int* indices, int index_cap, int* n_nod
   *n_indices = ni;
   return 0;
 }
+
+#ifdef REF_TAPE
+// the one definition of the draw tape (ref/tape_random.h)
+const double* ref_tape_values = nullptr;
+int ref_tape_len = 0, ref_tape_pos = 0, ref_tape_over = 0;
+
+// the next draws are values[0 .. n-1] (the caller keeps them alive); rewinds and clears the over-ask flag
+void ref_tape_set(const double* values, int n)
+{
+  ref_tape_values = values;
+  ref_tape_len = n;
+  ref_tape_pos = 0;
+  ref_tape_over = 0;
+}
+
+// draws asked for since ref_tape_set, the ones past the end included
+int ref_tape_consumed(void) { return ref_tape_pos; }
+
+// 1 when the reference asked for more than it was given (each such draw got 0.5)
+int ref_tape_overasked(void) { return ref_tape_over; }
+#endif
 
 }  // extern "C"

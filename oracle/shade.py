@@ -4,7 +4,12 @@ reference is) on the project's primary rays, and the project's side of the compa
 
 tools/gen_golden_shade.py builds the scenes of tests/scene_gen.py SHADE_SCENES, lets RefShade answer their
 rays and writes tests/golden/shade_ref.npz; tests/test_oracle_shade.py and tests/test_gpu_shade.py read the
-fixture only. The fixture holds data: shape, light and globals records, rays, colours, flags, BVH lists."""
+fixture only. The fixture holds data: shape, light and globals records, rays, colours, flags, BVH lists.
+
+The stochastic paths have a second fixture, tests/golden/shade_sampling_ref.npz (tools/gen_golden_shade_sampling.py,
+SAMPLING_SCENES): the draw-tape builds of the reference (libref_shade_tape_cr.so and its plain twin, whose
+uniform_real_distribution hands out a tape, oracle/ref/tape_random.h) answer each ray with the draws
+or_sample_color_log logged for it as the tape; the draws the reference consumed are stored per vector, the tape is not."""
 import ctypes
 import os
 import tempfile
@@ -18,9 +23,13 @@ from . import geom as G
 
 REF_SHADE_SO = os.path.join(HERE, "_ref", "libref_shade.so")
 REF_SHADE_CR_SO = os.path.join(HERE, "_ref", "libref_shade_cr.so")
+REF_SHADE_TAPE_SO = os.path.join(HERE, "_ref", "libref_shade_tape.so")
+REF_SHADE_TAPE_CR_SO = os.path.join(HERE, "_ref", "libref_shade_tape_cr.so")
 LIGHT_DT = np.dtype(LightDesc)
 BVH_DT = np.dtype(BVHNode)
 GOLD = os.path.join(os.path.dirname(HERE), "tests", "golden", "shade_ref.npz")
+GOLD_SAMPLING = os.path.join(os.path.dirname(HERE), "tests", "golden", "shade_sampling_ref.npz")
+LOG_CAP = 4096   # doubles per vector: far above what a depth-4 tree with 3 glossy samples can draw
 
 P = ctypes.POINTER
 _D = P(ctypes.c_double)
@@ -38,8 +47,11 @@ def read_rgb(rel):
 
 
 def build(name, sg):
-    """(desc, g, keepalive, texture or None) of a SHADE_SCENES class or "textured"; sg: tests/scene_gen.py,
-    imported by the caller"""
+    """(desc, g, keepalive, texture or None) of a SHADE_SCENES or SAMPLING_SCENES class or "textured"; sg:
+    tests/scene_gen.py, imported by the caller"""
+    if name in sg.SAMPLING_SCENES:
+        desc, g, keep = sg.SAMPLING_SCENES[name]()
+        return desc, g, keep, None
     if name == "textured":
         px, w, h = read_rgb(sg.SHADE_TEXTURE)
         desc, g, keep = sg.shade_textured(px, w, h)
@@ -114,6 +126,34 @@ def oracle_colors(desc, g):
     return col, hit
 
 
+def oracle_logs(desc, g):
+    """or_sample_color_log over every sample: (colour [pixel, sample, 3] f64, hit, in_motion [pixel, sample]
+    int32, draws: a list per pixel of a list per sample of the f64 values ray_color consumed, in order)"""
+    o = oracle()
+    n, W = spp(g), g.xRes
+    npx = g.xRes * g.yRes
+    col = np.zeros((npx, n, 3))
+    hit, mot = np.zeros((npx, n), dtype=np.int32), np.zeros((npx, n), dtype=np.int32)
+    draws = [[None] * n for _ in range(npx)]
+    c, h, m, nd = (ctypes.c_double * 3)(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    buf = (ctypes.c_double * LOG_CAP)()
+    dp = ctypes.pointer(desc)
+    for p in range(npx):
+        for i in range(n):
+            rc = o.or_sample_color_log(dp, ctypes.byref(g), 0, p % W, p // W, i, c, ctypes.byref(h), ctypes.byref(m),
+                                       buf, LOG_CAP, ctypes.byref(nd))
+            if rc or nd.value > LOG_CAP:
+                raise RuntimeError("or_sample_color_log failed %d (%d draws)" % (rc, nd.value))
+            col[p, i] = c[0], c[1], c[2]
+            hit[p, i], mot[p, i] = h.value, m.value
+            draws[p][i] = np.array(buf[:nd.value], dtype=np.float64)
+    return col, hit, mot, draws
+
+
+def draw_counts(draws):
+    return np.array([[len(t) for t in row] for row in draws], dtype=np.int32)
+
+
 def image_from_colors(g, col):
     """renderImage's epilogue on per-sample colours [pixel, sample, 3]: color += tmp in sample order,
     color /= n in double, clamp((float)c) * 255.0f into the ppmOut layout (cpp:1212-1217)"""
@@ -164,14 +204,23 @@ def bvh_differs(a, b):
 
 
 class RefShade:
-    """One of the two reference builds with a scene set"""
+    """One of the reference builds with a scene set: cr or plain libm, each as it is or as a draw-tape build"""
 
     @staticmethod
-    def available(cr=True):
-        return os.path.exists(REF_SHADE_CR_SO if cr else REF_SHADE_SO)
+    def path(cr=True, tape=False):
+        return ((REF_SHADE_TAPE_CR_SO if cr else REF_SHADE_TAPE_SO) if tape else
+                (REF_SHADE_CR_SO if cr else REF_SHADE_SO))
 
-    def __init__(self, cr=True):
-        self.r = r = ctypes.CDLL(REF_SHADE_CR_SO if cr else REF_SHADE_SO)
+    @staticmethod
+    def available(cr=True, tape=False):
+        return os.path.exists(RefShade.path(cr, tape))
+
+    def __init__(self, cr=True, tape=False):
+        self.r = r = ctypes.CDLL(RefShade.path(cr, tape))
+        self.tape = tape
+        if tape:
+            r.ref_tape_set.restype = None
+            r.ref_tape_set.argtypes = [_D, ctypes.c_int]
         S, L = P(ShapeDesc), P(LightDesc)
         r.ref_reset.restype = None
         r.ref_load_texture.argtypes = [ctypes.c_char_p]
@@ -209,6 +258,27 @@ class RefShade:
             hit[k], mot[k] = h.value, m.value
         return col.reshape(shp + (3,)), hit.reshape(shp), mot.reshape(shp), threw.reshape(shp)
 
+    def colors_taped(self, start, d, draws):
+        """colors() with draws[pixel][sample] as the tape of that ray's rayColor call: also the number of draws
+        the reference asked for and whether it asked past the tape's end, int32 [pixel, sample]"""
+        assert self.tape
+        shp = start.shape[:-1]
+        col = np.zeros(shp + (3,))
+        hit, mot, threw, used, over = (np.zeros(shp, dtype=np.int32) for _ in range(5))
+        h, m = ctypes.c_int(), ctypes.c_int()
+        for p in range(shp[0]):
+            for i in range(shp[1]):
+                t = np.ascontiguousarray(draws[p][i], dtype=np.float64)
+                self.r.ref_tape_set(t.ctypes.data_as(_D), len(t))
+                s1, d1 = np.ascontiguousarray(start[p, i]), np.ascontiguousarray(d[p, i])
+                c1 = np.zeros(3)
+                threw[p, i] = self.r.ref_ray_color(d1.ctypes.data_as(_D), s1.ctypes.data_as(_D), self.depth, 1.0,
+                                                   c1.ctypes.data_as(_D), ctypes.byref(h), ctypes.byref(m))
+                col[p, i], hit[p, i], mot[p, i] = c1, h.value, m.value
+                used[p, i], over[p, i] = self.r.ref_tape_consumed(), self.r.ref_tape_overasked()
+        self.r.ref_tape_set(None, 0)
+        return col, hit, mot, threw, used, over
+
     def bvh(self):
         nn, ni = ctypes.c_int(), ctypes.c_int()
         self.r.ref_bvh(None, 0, None, 0, ctypes.byref(nn), ctypes.byref(ni))
@@ -237,6 +307,25 @@ def answer(name, sg):
            "hit": hit, "in_motion": mot, "threw": threw, "bvh_nodes": nodes, "bvh_idx": idx}
     out.update(plain_pack(col, pcol))
     return out, (desc, g, keep), (ocol, ohit)
+
+
+def answer_sampling(name, sg):
+    """answer() for a SAMPLING_SCENES class: the tape builds, fed the oracle's logs ray by ray. Adds `draws`, the
+    number of uniform values the cr build consumed per vector; returns the over-ask flags and the oracle's
+    colour, hit, in_motion and log lengths beside it"""
+    desc, g, keep, _ = build(name, sg)
+    start, d = primary_rays(g)
+    ocol, ohit, omot, logs = oracle_logs(desc, g)
+    cr, plain = RefShade(True, tape=True), RefShade(False, tape=True)
+    cr.set(desc, g)
+    col, hit, mot, threw, used, over = cr.colors_taped(start, d, logs)
+    plain.set(desc, g)
+    pcol = plain.colors_taped(start, d, logs)[0]
+    shape_rec, _ = G.records_from_desc(desc)
+    out = {"shapes": shape_rec, "lights": light_records(desc), "globals": G.record_from_globals(g), "start": start,
+           "dir": d, "color": col, "hit": hit, "in_motion": mot, "threw": threw, "draws": used}
+    out.update(plain_pack(col, pcol))
+    return out, (desc, g, keep), (ocol, ohit, omot, draw_counts(logs), over)
 
 
 def plain_pack(col, pcol):

@@ -427,3 +427,137 @@ SHADE_SCENES = {
     "own-shape": shade_own_shape,
     "grazing": shade_grazing,
 }
+
+
+# ---------------------------------------------------------------------------------------------------
+# The stochastic scenes of tests/golden/shade_sampling_ref.npz (tools/gen_golden_shade_sampling.py): area
+# lights WITH extent, sphere lights with a radius, glossy reflectors with nogloss = 0, shapes in motion.
+# The draw-tape build of the reference answers their rays with the draws the oracle logged
+# (or_sample_color_log) as the tape. No glass; blur_samples = 0 in the stored globals (the blur passes are
+# renderImage's, not rayColor's). Lights are dim and mostly of one channel each: a channel then says which
+# light lit a sample.
+# ---------------------------------------------------------------------------------------------------
+_GLOSSY_KW = dict(material=LINOLEUM, roughness=0.6, refr=(1.543, 0.0))
+_CAMERA = ((0.5, 1.25, 6.5), (0.0, 0.75, 0.0), 0.0625, 6.0)
+
+
+def _sampling_globals(b, g, res, spp, depth, brdf):
+    g.xRes, g.yRes, g.antialias_samples, g.max_depth, g.brdf_samples = res[0], res[1], spp, depth, brdf
+    g.nogloss, g.blur_samples = 0, 0
+    desc, keep = b.desc()
+    return desc, g, keep
+
+
+def _rect_light(b, A, B, D, color, shape=False):
+    """a rectangle light over A, B, D (C = B + D - A); shape=True: also the "rectanglelight" shape it is"""
+    C = tuple(B[a] + D[a] - A[a] for a in range(3))
+    cen = tuple((A[a] + B[a] + C[a] + D[a]) / 4 for a in range(3))
+    si = -1
+    if shape:
+        si = b.shape(RECTANGLE, v=[A, B, C, D], color=(0.8, 0.8, 0.8), emit=2, flags=F_LIGHT, length=1.0, width=1.0,
+                     center=cen)
+    return b.light(RECT_LIGHT, si, center=cen, color=color, A=A, B=B, D=D)
+
+
+def sampling_rect_light():
+    """Rectangle lights with extent over a Phong floor. Light 0 (red, the only red one) hangs over a plate:
+    floor pixels fully lit by it, in its penumbra (the red channel present in some samples of a pixel and not
+    in others) and in its umbra. Lights 0 and 1 share one Philox draw (words 0-1 and 2-3); light 1 is a shape of
+    the scene too (the own-shape skip with real sampling); lights 2 and 3 are point lights; light 4 is a
+    rectangle light at an even index, with a draw of its own. 16 x 8 at 4 spp."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    _rect(b, (-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), (0.9, 0.9, 0.9), flags=0)
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 4, -4), (-4, 4, -4), (0.6, 0.9, 0.9), flags=0)
+    _cylinder(b, (1.5, 0, 0.5), (1.5, 1.5, 0.5), 0.5, (0.95, 0.64, 0.54))
+    _rect(b, (-2.5, 2.0, 2.0), (-0.5, 2.0, 2.0), (-0.5, 2.0, 0.0), (-2.5, 2.0, 0.0), (0.7, 0.7, 0.75), flags=0)
+    _rect_light(b, (-2.0, 3.5, 1.5), (-1.0, 3.5, 1.5), (-2.0, 3.5, 0.5), (0.5, 0.0, 0.0))
+    _rect_light(b, (1.0, 3.5, 0.5), (2.5, 3.5, 0.5), (1.0, 3.5, -1.0), (0.0, 0.4, 0.0), shape=True)
+    b.light(POINT_LIGHT, center=(3.0, 3.0, 3.0), color=(0.0, 0.0, 0.3))
+    b.light(POINT_LIGHT, center=(-3.5, 1.0, 3.0), color=(0.0, 0.0, 0.2))
+    _rect_light(b, (3.9, 1.0, -1.0), (3.9, 1.0, -2.5), (3.9, 2.5, -1.0), (0.0, 0.25, 0.25))
+    return _sampling_globals(b, b.globals(*_CAMERA), (16, 8), 4, 3, 2)
+
+
+def sampling_sphere_light():
+    """Sphere lights with a radius over a Phong floor and wall. sampleRay returns the sampled POINT (Q11): the
+    shadow ray leaves the surface in the direction of that position vector. Light 0 (red) has no baxis: half of
+    its first draws face away and the mirror image is taken. Light 1 (blue) has baxis = -y and hangs to the side,
+    so that for floor points away from it neither the draw nor its mirror image passes both tests and it draws
+    again. Light 2 (green) is the sphere shape at (0, 3, 0): from a floor point near the origin the segment
+    along the sampled position vector ends inside or behind that very sphere, so those points are green only
+    because the light's own sphere is skipped."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    _rect(b, (-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), (0.9, 0.9, 0.9), flags=0)
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 4, -4), (-4, 4, -4), (0.6, 0.9, 0.9), flags=0)
+    _cylinder(b, (-1.5, 0, -1.0), (-1.5, 1.5, -1.0), 0.5, (0.95, 0.64, 0.54))
+    sl = b.shape(SPHERE, v=[(0.0, 3.0, 0.0)], radius=1.0, color=(0.6, 0.6, 0.5), emit=1, flags=F_LIGHT,
+                 center=(0.0, 3.0, 0.0))
+    b.light(SPHERE_LIGHT, -1, 0.75, center=(-2.0, 2.0, 1.0), color=(0.5, 0.0, 0.0))
+    b.light(SPHERE_LIGHT, -1, 0.5, center=(3.0, 2.5, 1.0), color=(0.0, 0.0, 0.5), baxis=(0.0, -1.0, 0.0))
+    b.light(SPHERE_LIGHT, sl, 1.0, center=(0.0, 3.0, 0.0), color=(0.0, 0.5, 0.0))
+    return _sampling_globals(b, b.globals(*_CAMERA), (32, 16), 1, 3, 2)
+
+
+def sampling_glossy():
+    """Glossy reflectors with nogloss = 0 under point lights: every draw is a glossy sample's. The camera looks
+    level along -x from (6, 0.375, 0) with depth of field off: the floor is seen from steep (near) to grazing (far,
+    where the squeeze loops move the vertices of the sample rectangle and samples below the surface force the
+    resample loop); the wall at x = -4 has an x-normal, and the ray of pixel (W/2, H/2) is exactly (-c, 0, 0),
+    so that gloss_ray x (1, 0, 0) vanishes and the isApprox fallback runs. 8 x 16 at 4 spp (rows 0.05 apart in slope): without a lens the
+    four samples of a pixel are one ray with four draw sequences."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    _rect(b, (-4, 0, 4), (8, 0, 4), (8, 0, -4), (-4, 0, -4), (0.58, 0.82, 1.0), flags=F_GLOSSY, **_GLOSSY_KW)
+    _rect(b, (-4, 0, 4), (-4, 0, -4), (-4, 4, -4), (-4, 4, 4), (0.9, 0.8, 0.3), flags=F_GLOSSY, **_GLOSSY_KW)
+    _rect(b, (-4, 0, -4), (8, 0, -4), (8, 4, -4), (-4, 4, -4), (0.0, 0.81, 0.99), flags=0)
+    _cylinder(b, (0.0, 0, 2.0), (0.0, 1.5, 2.0), 0.5, (0.9, 0.3, 0.2))
+    _cylinder(b, (2.0, 0, -2.0), (2.0, 2.0, -2.0), 0.5, (0.3, 0.9, 0.4))
+    b.light(POINT_LIGHT, center=(2.0, 3.5, 2.0), color=(0.4, 0.4, 0.4))
+    b.light(POINT_LIGHT, center=(0.0, 3.0, -3.0), color=(0.3, 0.3, 0.3))
+    return _sampling_globals(b, b.globals((6.0, 0.375, 0.0), (0.0, 0.375, 0.0), 0.0, 6.0), (8, 16), 4, 3, 3)
+
+
+def sampling_glossy_area(triangle=False, res=(32, 16), spp=1):
+    """Glossy children landing on surfaces lit by rectangle lights: a glossy floor and a glossy side wall (two
+    levels of k / brdf_samples at depth 4), a plain back wall and a Cook-Torrance cylinder (the one user of
+    the float libm in these classes), a rectangle light with extent
+    that is a shape and one that is not. The draws happen at child node keys. triangle=True: the mesh twin."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    _rect(b, (-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), (0.58, 0.82, 1.0), flags=F_GLOSSY, **_GLOSSY_KW)
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 4, -4), (-4, 4, -4), (0.0, 0.81, 0.99), flags=0)
+    _rect(b, (4, 0, -4), (4, 0, 4), (4, 4, 4), (4, 4, -4), (0.9, 0.8, 0.3), flags=F_GLOSSY, **_GLOSSY_KW)
+    _cylinder(b, (-1.5, 0, 0.5), (-1.5, 1.5, 0.5), 0.5, (0.95, 0.64, 0.54), model=COOK_TORRANCE,
+              **_MODEL_KW[COOK_TORRANCE])
+    if triangle:
+        _triangle(b, (0.5, 0.25, 1.0), (2.0, 0.25, 1.5), (1.25, 2.0, 0.5), (0.2, 0.8, 0.3))
+    _rect_light(b, (-1.0, 3.75, 1.0), (1.0, 3.75, 1.0), (-1.0, 3.75, -1.0), (0.45, 0.45, 0.4), shape=True)
+    _rect_light(b, (-3.9, 1.0, 2.0), (-3.9, 1.0, 0.5), (-3.9, 2.5, 2.0), (0.3, 0.25, 0.3))
+    return _sampling_globals(b, b.globals(*_CAMERA), res, spp, 4, 2)
+
+
+def sampling_in_motion():
+    """in_motion, which every deeper rayColor call overwrites: a moving cylinder seen directly; a static steel
+    panel showing it; a MOVING steel cylinder showing static walls; a glossy floor whose last sample decides.
+    Point lights: every draw is a glossy sample's."""
+    b = _Builder(1.0, (0.0, 0.0, 0.0))
+    _rect(b, (-4, 0, 4), (4, 0, 4), (4, 0, -4), (-4, 0, -4), (0.58, 0.82, 1.0), flags=F_GLOSSY, **_GLOSSY_KW)
+    _rect(b, (-4, 0, -4), (4, 0, -4), (4, 4, -4), (-4, 4, -4), (0.0, 0.81, 0.99), flags=0)
+    _rect(b, (-3.0, 0.5, -3.5), (-0.5, 0.5, -3.0), (-0.5, 3.0, -3.0), (-3.0, 3.0, -3.5), (0.8, 0.8, 0.8), flags=0,
+          material=STEEL)
+    _cylinder(b, (-2.0, 0, -0.5), (-2.0, 1.75, -0.5), 0.5, (0.9, 0.3, 0.2), flags=F_MOTION)
+    _cylinder(b, (0.5, 0.5, 1.0), (2.5, 0.5, 0.0), 0.5, (0.8, 0.8, 0.8), material=STEEL, flags=F_MOTION)
+    _cylinder(b, (2.5, 0, -2.0), (2.5, 1.5, -2.0), 0.5, (0.3, 0.9, 0.4))
+    b.light(POINT_LIGHT, center=(-2.5, 3.5, 2.5), color=(0.4, 0.4, 0.4))
+    b.light(POINT_LIGHT, center=(3.0, 3.0, 3.0), color=(0.3, 0.3, 0.3))
+    return _sampling_globals(b, b.globals(*_CAMERA), (32, 16), 1, 4, 2)
+
+
+# class name -> scene function (the wave5 twins: 8 x 4 at 64 spp, the smallest image of the 5-wave builds)
+SAMPLING_SCENES = {
+    "rect-light": sampling_rect_light,
+    "sphere-light": sampling_sphere_light,
+    "glossy": sampling_glossy,
+    "glossy-area": sampling_glossy_area,
+    "in-motion": sampling_in_motion,
+    "wave5-glossy-area": lambda: sampling_glossy_area(res=(8, 4), spp=64),
+    "wave5-glossy-area-mesh": lambda: sampling_glossy_area(triangle=True, res=(8, 4), spp=64),
+}

@@ -40,6 +40,20 @@ def compare(G, out, ocol, ohit):
     return np.where(bad, 2, np.where(bits, 1, 0)).astype(np.int32)
 
 
+def write_npz(path, store):
+    """a fixed member order and no timestamps: the same answers give the same bytes"""
+    import zipfile
+    import io
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k in sorted(store):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(store[k]), allow_pickle=False)
+            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            z.writestr(zi, buf.getvalue())
+    print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))
+
+
 def main():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import scene_gen as sg
@@ -102,18 +116,7 @@ def main():
         return
     if refuse:
         sys.exit("not written")
-    path = os.path.join(ROOT, "tests", "golden", "shade_ref.npz")
-    # (a fixed member order and no timestamps: the same answers give the same bytes)
-    import zipfile
-    import io
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
-        for k in sorted(store):
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.asanyarray(store[k]), allow_pickle=False)
-            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            zi.compress_type = zipfile.ZIP_DEFLATED
-            z.writestr(zi, buf.getvalue())
-    print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))
+    write_npz(os.path.join(ROOT, "tests", "golden", "shade_ref.npz"), store)
 
 
 if __name__ == "__main__":
