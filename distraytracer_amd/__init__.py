@@ -15,7 +15,7 @@ an error (there is no CPU path in this package).
 import ctypes
 
 from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT, DT_OUT_IMAGE, DT_OUT_SLAB, AccelInfo, BVHNode, Camera, DenoiseParams, DenoiseVarParams, DTError, Globals, SceneDesc,
-                   SHAPE_TYPES, OcclusionParams, Stats, TemporalParams, Tiles, UpsampleParams, check, lib)
+                   SHAPE_TYPES, OcclusionParams, RayOrderParams, DT_RAY_ORDER_TILE, Stats, TemporalParams, Tiles, UpsampleParams, check, lib)
 
 __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_scene", "Scene",
            "render", "render_sky", "renderImage", "renderImageCloud", "write_ppm", "DATA_DIR",
@@ -28,6 +28,7 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "DenoiseVarParams", "denoise_var_params_default", "variance",
            "Camera", "camera", "TemporalParams", "temporal_params_default", "reproject", "TemporalAccumulator",
            "trace_rays", "rays_occluded", "RAY_PLANES",
+           "RayOrderParams", "RayOrder", "ray_order_params_default", "ray_order_key", "ray_order", "DT_RAY_ORDER_TILE",
            "render_mattes", "matte_mask", "shape_groups", "MATTE_PLANES",
            "UpsampleParams", "upsample_params_default", "upsample", "low_res_globals",
            "OcclusionParams", "occlusion_params_default", "render_occlusion", "occlusion_ao_ray", "occlusion_light_ray",
@@ -640,13 +641,118 @@ def _ray_out(what, name, a, n, per, torch_dtype, np_dtype, side):
     return p if p.value else ctypes.cast(_NO_RAYS, ctypes.c_void_p)
 
 
-def trace_rays(scene, g, start, dir, planes=RAY_PLANES, out=None, stream=None):
+def ray_order_params_default():
+    """dt_ray_order_params_default: origin_bits 5, dir_bits 6, origin-major, the box from the rays (a choice, not a
+    measurement; for rays that all start on one lens use origin_bits=0, dir_bits=8)"""
+    p = RayOrderParams()
+    lib.dt_ray_order_params_default(ctypes.byref(p))
+    return p
+
+
+def ray_order_key(params, lo, hi, start, dir):
+    """The sort key of one ray inside the box (lo, hi) (include/dt.h dt_ray_order_key), on the host."""
+    from ._lib import D3
+    key = ctypes.c_uint32()
+    check(lib.dt_ray_order_key(ctypes.byref(params), D3(*[float(x) for x in lo]), D3(*[float(x) for x in hi]),
+                               D3(*[float(x) for x in start]), D3(*[float(x) for x in dir]), ctypes.byref(key)),
+          "dt_ray_order_key")
+    return key.value
+
+
+def _side(a):
+    return 1 if hasattr(a, "data_ptr") and a.is_cuda else 0
+
+
+def _data_ptr(a):
+    p = a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+    return ctypes.c_void_p(p) if p else ctypes.cast(_NO_RAYS, ctypes.c_void_p)
+
+
+def _is_contiguous(a):
+    return a.is_contiguous() if hasattr(a, "data_ptr") else a.flags["C_CONTIGUOUS"]
+
+
+class RayOrder:
+    """What ray_order returns: `perm` (perm[i] is the caller's index of the ray that goes to place i; uint32 in
+    numpy, the same bits as int32 in torch: entries are below 2^30), `keys` (in the caller's order, or None),
+    `box` (lo and hi as used, six floats), `kernel_ms` (the device chain's HIP-event time, 0.0 on the host),
+    and the two row permutations of dt_permute_rows on the side of perm."""
+
+    def __init__(self, n, perm, keys, box, kernel_ms, stream):
+        self.n, self.perm, self.keys, self.box, self.kernel_ms, self.stream = n, perm, keys, box, kernel_ms, stream
+
+    def _permute(self, what, a, out, inverse):
+        if _side(a) != _side(self.perm) or not _is_contiguous(a):
+            raise DTError("RayOrder.%s: a contiguous array on the side of the order is needed" % what)
+        nbytes = _numel_any(a) * (a.element_size() if hasattr(a, "data_ptr") else a.itemsize)
+        if self.n == 0 and nbytes == 0:
+            row = 1
+        elif self.n == 0 or nbytes % self.n or not 1 <= nbytes // self.n <= 64:
+            raise DTError("RayOrder.%s: %d bytes are not %d rows of 1..64 bytes" % (what, nbytes, self.n))
+        else:
+            row = nbytes // self.n
+        if out is None:
+            if hasattr(a, "data_ptr"):
+                import torch
+                out = torch.empty_like(a)
+            else:
+                import numpy as np
+                out = np.empty_like(a)
+        elif (_side(out) != _side(a) or not _is_contiguous(out) or out.dtype != a.dtype or
+              _numel_any(out) != _numel_any(a)):
+            raise DTError("RayOrder.%s: out must be a contiguous array like the input, on its side" % what)
+        check(lib.dt_permute_rows(self.n, row, _data_ptr(self.perm), _data_ptr(a), _data_ptr(out), inverse,
+                                  _side(a), ctypes.c_void_p(self.stream) if self.stream else None), "dt_permute_rows")
+        return out
+
+    def apply(self, a, out=None):
+        """rows in sorted order: out[i] = a[perm[i]] (a: n rows of 1..64 bytes, such as start, dir, skip_shape)"""
+        return self._permute("apply", a, out, 0)
+
+    def restore(self, a, out=None):
+        """answers back in the caller's order: out[perm[i]] = a[i]"""
+        return self._permute("restore", a, out, 1)
+
+
+def ray_order(start, dir, params=None, keys=False, stream=None):
+    """The order that sorts rays into coherent waves (include/dt.h dt_ray_order): start and dir as for trace_rays.
+    Returns a RayOrder whose perm is the stable ascending order of the rays' keys, numpy's argsort(keys,
+    kind="stable"); on the device a radix sort enqueued on `stream` (the call waits for it: box and kernel_ms
+    come back). One order serves every query on the same rays: order.apply(start), order.apply(dir), the
+    query, order.restore(answer) -- or trace_rays(..., order=order)."""
+    n, sp, dp, side = _ray_arrays("ray_order", start, dir)
+    p = params if params is not None else ray_order_params_default()
+    perm = _ray_new(start, (n,), "torch.int32", "uint32")
+    k = _ray_new(start, (n,), "torch.int32", "uint32") if keys else None
+    work = None
+    if side and n:
+        import torch
+        work = torch.empty(int(lib.dt_ray_order_workspace_bytes(n)), dtype=torch.uint8, device=start.device)
+    box = (ctypes.c_double * 6)()
+    ms = ctypes.c_float(0.0)
+    check(lib.dt_ray_order(n, sp, dp, ctypes.byref(p), _data_ptr(perm), _data_ptr(k) if keys else None, box,
+                           _data_ptr(work) if work is not None else (ctypes.cast(_NO_RAYS, ctypes.c_void_p) if side else None),
+                           side, ctypes.c_void_p(stream) if stream else None, ctypes.byref(ms)), "dt_ray_order")
+    return RayOrder(n, perm, k, tuple(box), float(ms.value), stream)
+
+
+def _order_for(what, order, start, dir, n, side, stream):
+    if order is True:
+        order = ray_order(start, dir, stream=stream)
+    if not isinstance(order, RayOrder) or order.n != n or _side(order.perm) != side:
+        raise DTError("%s: order must be True or a RayOrder of these %d rays, on their side" % (what, n))
+    return order
+
+
+def trace_rays(scene, g, start, dir, planes=RAY_PLANES, out=None, stream=None, order=None):
     """Closest hits of caller-supplied rays (include/dt.h dt_trace_rays): start and dir are float64, shaped
     (n, 3) or flat, numpy arrays or torch tensors, both on one side. Returns (hits, stats): hits is a dict
     plane name -> array on the side of start for the planes asked for: shape (int32, -1: none), t (float32
     along the unnormalised dir, FLT_MAX: none), point, normal and albedo (float64, (n, 3); zeros on a miss).
     `out`: a dict of planes to write into instead (it decides the planes). 64 consecutive rays share a
-    wave: keep neighbours in the arrays neighbours in space. g: the globals of the scene's renders."""
+    wave: keep neighbours in the arrays neighbours in space, or pass `order` (True, or a RayOrder of these
+    rays from ray_order): the rays are gathered into sorted order, traced, and every answer is put back in
+    the caller's order -- the same bits. g: the globals of the scene's renders."""
     n, sp, dp, side = _ray_arrays("trace_rays", start, dir)
     if out is None:
         for name in planes:
@@ -661,17 +767,25 @@ def trace_rays(scene, g, start, dir, planes=RAY_PLANES, out=None, stream=None):
             raise DTError("trace_rays: unknown plane %r" % (name,))
         tt, nt, per = _RAY_PLANE_TYPES[name]
         setattr(h, name, _ray_out("trace_rays", name, a, n, per, tt, nt, side))
+    if order is not None:
+        order = _order_for("trace_rays", order, start, dir, n, side, stream)
+        tmp = {name: _ray_new(start, tuple(a.shape), *_RAY_PLANE_TYPES[name][:2]) for name, a in out.items()}
+        _, st = trace_rays(scene, g, order.apply(start), order.apply(dir), out=tmp, stream=stream)
+        for name, a in out.items():
+            order.restore(tmp[name], out=a)
+        return out, st
     st = Stats()
     check(lib.dt_trace_rays(scene.handle, ctypes.byref(g), n, sp, dp, ctypes.byref(h), side,
                             ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)), "dt_trace_rays")
     return out, st
 
 
-def rays_occluded(scene, g, start, dir, skip_shape=None, out=None, stream=None):
+def rays_occluded(scene, g, start, dir, skip_shape=None, out=None, stream=None, order=None):
     """Is start + dir hidden from start (include/dt.h dt_rays_occluded)? start and dir as for trace_rays;
     skip_shape: optional int32 per ray on the same side, the shape the test leaves out (-1: none), such as
     the shape a light is. Returns (occluded, stats): uint8 per ray (1 or 0) on the side of start, or `out`.
-    A wave is served in groups of equal skip_shape: group the rays by it where it varies."""
+    A wave is served in groups of equal skip_shape: group the rays by it where it varies. `order` as for
+    trace_rays: the rays and skip_shape are gathered into sorted order and the answer is put back."""
     n, sp, dp, side = _ray_arrays("rays_occluded", start, dir)
     kp = None
     if skip_shape is not None:
@@ -679,6 +793,12 @@ def rays_occluded(scene, g, start, dir, skip_shape=None, out=None, stream=None):
     if out is None:
         out = _ray_new(start, (n,), "torch.uint8", "uint8")
     op = _ray_out("rays_occluded", "out", out, n, 1, "torch.uint8", "uint8", side)
+    if order is not None:
+        order = _order_for("rays_occluded", order, start, dir, n, side, stream)
+        tmp, st = rays_occluded(scene, g, order.apply(start), order.apply(dir),
+                                skip_shape=order.apply(skip_shape) if skip_shape is not None else None, stream=stream)
+        order.restore(tmp, out=out)
+        return out, st
     st = Stats()
     check(lib.dt_rays_occluded(scene.handle, ctypes.byref(g), n, sp, dp, kp, op, side,
                                ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)), "dt_rays_occluded")

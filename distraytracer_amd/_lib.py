@@ -105,6 +105,16 @@ class RayHits(ctypes.Structure):
                 ("normal", ctypes.c_void_p), ("albedo", ctypes.c_void_p)]
 
 
+class RayOrderParams(ctypes.Structure):
+    """dt_ray_order_params: origin_bits 0..10 and dir_bits 0..8 per axis (3*origin_bits + 2*dir_bits in 1..30),
+    dir_major 0/1, box_given 0/1 and the box (finite, lo <= hi; read iff box_given)"""
+    _fields_ = [("origin_bits", c_int32), ("dir_bits", c_int32), ("dir_major", c_int32), ("box_given", c_int32),
+                ("box_lo", D3), ("box_hi", D3)]
+
+
+DT_RAY_ORDER_TILE = 4096   # keys per workgroup of the radix sort (include/dt.h)
+
+
 class Mattes(ctypes.Structure):
     """dt_mattes: the planes of dt_render_mattes (a null pointer: not wanted)"""
     _fields_ = [("id", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("distinct", ctypes.c_void_p)]
@@ -206,7 +216,9 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_upsample_params_default", "dt_upsample",
            "dt_guide_bounce", "dt_render_features_path",
            "dt_occlusion_params_default", "dt_render_occlusion", "dt_occlusion_ao_ray", "dt_occlusion_light_ray",
-           "dt_points_occlusion"]
+           "dt_points_occlusion",
+           "dt_ray_order_params_default", "dt_ray_order_key", "dt_ray_order_workspace_bytes", "dt_ray_order",
+           "dt_permute_rows"]
 
 
 class DTError(RuntimeError):
@@ -306,6 +318,14 @@ def _load():
                                     c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_rays_occluded": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, c_int32, ctypes.c_void_p, P(Stats)]),
+        "dt_ray_order_params_default": (None, [P(RayOrderParams)]),
+        "dt_ray_order_key": (c_int32, [P(RayOrderParams), P(c_double), P(c_double), P(c_double), P(c_double),
+                                       P(c_uint32)]),
+        "dt_ray_order_workspace_bytes": (c_int64, [c_int64]),
+        "dt_ray_order": (c_int32, [c_int64, ctypes.c_void_p, ctypes.c_void_p, P(RayOrderParams), ctypes.c_void_p,
+                                   ctypes.c_void_p, P(c_double), ctypes.c_void_p, c_int32, ctypes.c_void_p, P(c_float)]),
+        "dt_permute_rows": (c_int32, [c_int64, c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_int32,
+                                      c_int32, ctypes.c_void_p]),
         "dt_render_mattes": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, P(Tiles), c_int32, ctypes.c_void_p, c_int32,
                                        c_int32, P(Mattes), c_int32, ctypes.c_void_p, P(Stats), P(c_uint64)]),
         "dt_matte_mask": (c_int32, [c_int64, c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_int32,

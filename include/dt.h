@@ -72,6 +72,9 @@ extern "C" {
  *    dt_occlusion_light_ray -- occlusion feature buffers: ambient occlusion and per-light visibility) */
 /* (still 8, new exports only, no struct changed: dt_points_occlusion -- occlusion queries at surface points
  *    the caller supplies, for baking) */
+/* (still 8, new exports and one new struct, no struct changed: dt_ray_order_params_default, dt_ray_order_key,
+ *    dt_ray_order_workspace_bytes, dt_ray_order and its dt_ray_order_params, dt_permute_rows -- ray ordering:
+ *    sort caller-supplied rays into coherent waves) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -672,7 +675,8 @@ int dt_matte_mask(int64_t n_pixels, int32_t layers, const int32_t* id, const flo
  * is wanted), tex_fetches and uv_out_of_range (iff albedo is), kernel_ms; everything else 0.
  *
  * The walk is the renders' wave-uniform one: 64 consecutive rays share a wave, which visits the union of
- * its rays' nodes. Rays that are neighbours in the arrays should be neighbours in space (README.md). */
+ * its rays' nodes. Rays that are neighbours in the arrays should be neighbours in space (README.md);
+ * dt_ray_order (below) sorts rays that are not. */
 typedef struct dt_ray_hits {   /* each plane optional (NULL: not wanted); n_rays entries; all on one side */
   int32_t* shape;    /* closest shape, -1: none */
   float*   t;        /* its t along the unnormalised dir, FLT_MAX: none */
@@ -700,6 +704,83 @@ int dt_trace_rays(const dt_scene* s, const dt_globals* g, int64_t n_rays, const 
 int dt_rays_occluded(const dt_scene* s, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
                      const int32_t* skip_shape /* optional, n_rays; -1: none */, uint8_t* occluded,
                      int32_t on_device, void* stream, dt_stats* stats);
+
+/* ---- ray ordering: sort caller-supplied rays into coherent waves ----
+ * No reference counterpart. The ray queries serve 64 consecutive array entries with one wave, and a wave walks
+ * the union of its lanes' nodes: rays with no natural order cost up to 4x. dt_ray_order gives
+ * every ray a key (the cell of its start in a box and the cell of its direction on the octahedral map, both
+ * Morton-interleaved) and returns the stable ascending order of the keys as a permutation; dt_permute_rows
+ * gathers rows by it (the rays, skip_shape) and puts the answers back in the caller's order.
+ *
+ * The key. B = 3*origin_bits + 2*dir_bits, 1 <= B <= 30. Every operation below is one rounded IEEE f64
+ * operation in the parenthesisation written (no contraction, no libm; csrc/dt_order.h is the one definition
+ * for the host loop, the kernel and dt_ray_order_key; tests/rayorder_ref.py restates it in numpy).
+ *   A VOID ray (dt_trace_rays's rule: a non-finite component of start or dir, or an all-zero dir) has the key
+ *   1u << B: void rays sort last, and they contribute nothing to the box.
+ *   The box (lo, hi): box_lo, box_hi if box_given; else per axis the minimum and the maximum of the non-void
+ *   rays' starts, each reported as x + 0.0 (a -0 becomes +0, whichever zero a reduction met first); with no
+ *   non-void ray, all zeros.
+ *   cell(f, bits): !(f > 0) (a NaN included) -> 0; f >= 1 -> 2^bits - 1; otherwise (uint32_t)(f * 2^bits).
+ *   Origin cell, per axis k: e = hi_k - lo_k; f = e > 0 ? (o_k - lo_k) / e : 0; c_k = cell(f, origin_bits).
+ *   Direction cell: s = (|dx| + |dy|) + |dz|; u = dx / s; v = dy / s; if dz < 0:
+ *     (u, v) = ((1 - |v|) * (u >= 0 ? 1 : -1), (1 - |u|) * (v >= 0 ? 1 : -1)), both from the old u and v;
+ *   g_u = u * 0.5 + 0.5, g_v = v * 0.5 + 0.5; d_0 = cell(g_u, dir_bits), d_1 = cell(g_v, dir_bits).
+ *   (Huge finite components may overflow s or o_k - lo_k to inf: the rules above still give one key.)
+ *   Packing: bit 3i + k of M3 is bit i of c_k; bit 2i + k of M2 is bit i of d_k;
+ *     dir_major == 0: key = (M3 << 2*dir_bits) | M2     (rays of one place together, then by direction)
+ *     dir_major == 1: key = (M2 << 3*origin_bits) | M3  (rays of one direction together, then by place).
+ * dt_ray_order_params_default: origin_bits 5, dir_bits 6, dir_major 0, box_given 0. The defaults are a choice,
+ * not a measurement: 32 cells per axis and 64 x 64 directions for rays scattered through a scene. Rays that
+ * all start on one lens (a camera's) cannot be told apart by an origin cell: use origin_bits 0, dir_bits 8.
+ * Fewer key bits mean fewer sort passes (below).
+ * dt_ray_order_key: the key of one ray inside the box (lo, hi), on the host, for tests and callers. DT_OK; a
+ * null argument or a bad bit count: DT_E_INVALID ("dt_ray_order_key: ").
+ *
+ * dt_ray_order: perm[i] is the caller's index of the ray that goes to place i, in the stable ascending order
+ * of the keys: exactly numpy's argsort(keys, kind="stable"). keys (optional): the n_rays keys in the caller's
+ * order. box (optional, always a host pointer): lo[3], hi[3] as used. start, dir, perm and keys are all host
+ * (on_device = 0: a host loop with std::stable_sort that touches no device; workspace is not read and may be
+ * NULL) or all device (1; workspace: dt_ray_order_workspace_bytes(n_rays) bytes of device memory, any
+ * alignment). The device path enqueues on `stream`: a min / max reduction for the box (unless it is given;
+ * exact and order-free), a key kernel, and an LSD radix sort of (key, index) pairs with 8-bit digits in
+ * ceil((B + 1) / 8) passes, each pass a histogram of DT_RAY_ORDER_TILE keys per workgroup, a scan of the
+ * histograms and a scatter, every step a kernel of its own: no workgroup ever waits on another. The call
+ * returns without waiting unless kernel_ms (optional: the HIP-event time of the whole chain) or a box that
+ * the device computed (box given as a pointer while box_given == 0) is asked for; then it is synchronous.
+ * Errors, all before any device work: DT_E_INVALID, with a dt_last_error starting "dt_ray_order: " and naming
+ * the argument, for a null start, dir, params or perm, a null workspace with on_device, n_rays < 0,
+ * origin_bits outside 0..10, dir_bits outside 0..8, B outside 1..30, dir_major or box_given other than 0 or
+ * 1, a given box that is not finite or has lo > hi; DT_E_LIMIT for n_rays > 2^30. n_rays == 0: DT_OK, nothing
+ * is launched (box: the given one, or zeros).
+ *
+ * dt_permute_rows: rows of row_bytes (1..64) bytes. inverse == 0: dst[i] = src[perm[i]], a gather that puts
+ * rays in order; inverse == 1: dst[perm[i]] = src[i], which puts answers back in the caller's order. perm, src
+ * and dst all host or all device (1: one kernel on stream, enqueue only); src and dst must not overlap. The
+ * rows move as 8-byte words where row_bytes and both addresses are multiples of 8 (the 24-byte rays, points
+ * and normals), as dwords for multiples of 4 (shape, t, skip_shape), as bytes otherwise (occluded). The host
+ * path checks perm[i] < n (DT_E_INVALID naming the entry); the device path trusts the caller: an entry >= n
+ * reads or writes outside the arrays. DT_E_INVALID ("dt_permute_rows: ") for a null perm, src or dst, n < 0,
+ * row_bytes outside 1..64, inverse other than 0 or 1, overlapping src and dst; DT_E_LIMIT for n > 2^32.
+ *
+ * What ordering costs and when it pays: BASELINE.md "Ray ordering". dt_points_occlusion takes no order: its
+ * RNG counter is the point's index. */
+#define DT_RAY_ORDER_TILE 4096   /* keys per workgroup of the radix sort's histogram and scatter kernels */
+typedef struct dt_ray_order_params {
+  int32_t origin_bits;   /* 0..10 per axis */
+  int32_t dir_bits;      /* 0..8 per axis of the octahedral map */
+  int32_t dir_major;     /* 0: origin cell in the high bits; 1: direction cell in the high bits */
+  int32_t box_given;     /* 0: the box is the min/max of the non-void rays' starts */
+  double  box_lo[3], box_hi[3];   /* read iff box_given: finite, lo <= hi */
+} dt_ray_order_params;
+void    dt_ray_order_params_default(dt_ray_order_params* p);
+int     dt_ray_order_key(const dt_ray_order_params* p, const double lo[3], const double hi[3], const double start[3],
+                         const double dir[3], uint32_t* key);
+int64_t dt_ray_order_workspace_bytes(int64_t n_rays);
+int     dt_ray_order(int64_t n_rays, const double* start, const double* dir, const dt_ray_order_params* p,
+                     uint32_t* perm, uint32_t* keys /* optional, caller order */, double box[6] /* optional, host */,
+                     void* workspace, int32_t on_device, void* stream, float* kernel_ms /* optional */);
+int     dt_permute_rows(int64_t n, int32_t row_bytes /* 1..64 */, const uint32_t* perm, const void* src, void* dst,
+                        int32_t inverse, int32_t on_device, void* stream);
 
 /* ---- occlusion feature buffers: ambient occlusion and per-light visibility ----
  * No reference counterpart. The guides of dt_render_features say what a surface is; these say how exposed it
