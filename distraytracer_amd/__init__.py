@@ -28,6 +28,7 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "DenoiseVarParams", "denoise_var_params_default", "variance",
            "Camera", "camera", "TemporalParams", "temporal_params_default", "reproject", "TemporalAccumulator",
            "trace_rays", "rays_occluded", "RAY_PLANES",
+           "trace_rays_multi", "segment_through_glass", "RAY_MULTI_PLANES",
            "RayOrderParams", "RayOrder", "ray_order_params_default", "ray_order_key", "ray_order", "DT_RAY_ORDER_TILE",
            "render_mattes", "matte_mask", "shape_groups", "MATTE_PLANES",
            "UpsampleParams", "upsample_params_default", "upsample", "low_res_globals",
@@ -803,6 +804,88 @@ def rays_occluded(scene, g, start, dir, skip_shape=None, out=None, stream=None, 
     check(lib.dt_rays_occluded(scene.handle, ctypes.byref(g), n, sp, dp, kp, op, side,
                                ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)), "dt_rays_occluded")
     return out, st
+
+
+RAY_MULTI_PLANES = ("count", "shape", "t", "point", "normal", "albedo")
+DT_MAT_GLASS = 1   # include/dt.h
+
+
+def _restore_wide(order, tmp, out):
+    """out[perm[i]] = tmp[i] for rows wider than dt_permute_rows takes (64 bytes), by the arrays' own indexing"""
+    if hasattr(tmp, "data_ptr"):
+        out.index_copy_(0, order.perm.long(), tmp)
+    else:
+        import numpy as np
+        out[order.perm.astype(np.int64)] = tmp
+    return out
+
+
+def trace_rays_multi(scene, g, start, dir, k=4, planes=("count", "shape", "t"), order=None, stream=None):
+    """The k nearest surfaces along caller-supplied rays (include/dt.h dt_trace_rays_multi): start and dir as for
+    trace_rays, k in 1..8. Returns (hits, stats): hits is a dict plane name -> array on the side of start for
+    the planes asked for: count (int32, (n,): hits recorded, 0..k), shape (int32, (n, k): the shape ranked j,
+    -1 beyond count), t (float32, (n, k), FLT_MAX beyond count), point, normal and albedo (float64, (n, k, 3),
+    zeros beyond count). Every gathered shape is tested on its own and gives at most one hit, its first
+    intersection; hits are ranked by t, equal t by shape index. `order` as for trace_rays (True, or a RayOrder of
+    these rays): the rays are gathered into sorted order, traced, and every answer is put back in the caller's
+    order, the same bits -- by dt_permute_rows where a ray's row has at most 64 bytes, by the arrays' own
+    indexing where it is wider (point, normal and albedo for k >= 3)."""
+    what = "trace_rays_multi"
+    n, sp, dp, side = _ray_arrays(what, start, dir)
+    from ._lib import DT_MULTIHIT_MAX, RayMultiHits
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= DT_MULTIHIT_MAX:
+        raise DTError("%s: k must be an integer in 1..%d, not %r" % (what, DT_MULTIHIT_MAX, k))
+    for name in planes:
+        if name not in RAY_MULTI_PLANES:
+            raise DTError("%s: unknown plane %r" % (what, name))
+
+    def new(name):
+        if name == "count":
+            return _ray_new(start, (n,), "torch.int32", "int32")
+        tt, nt, per = _RAY_PLANE_TYPES[name]
+        return _ray_new(start, (n, k) if per == 1 else (n, k, 3), tt, nt)
+
+    out = {name: new(name) for name in planes}
+    if order is not None:
+        order = _order_for(what, order, start, dir, n, side, stream)
+        tmp, st = trace_rays_multi(scene, g, order.apply(start), order.apply(dir), k=k, planes=planes, stream=stream)
+        for name, a in out.items():
+            row = _numel_any(a) * (a.element_size() if hasattr(a, "data_ptr") else a.itemsize) // n if n else 1
+            if row <= 64:
+                order.restore(tmp[name], out=a)
+            else:
+                _restore_wide(order, tmp[name], a)
+        return out, st
+    h = RayMultiHits()
+    for name, a in out.items():
+        setattr(h, name, _data_ptr(a))
+    st = Stats()
+    check(lib.dt_trace_rays_multi(scene.handle, ctypes.byref(g), n, sp, dp, k, ctypes.byref(h), side,
+                                  ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)), "dt_trace_rays_multi")
+    return out, st
+
+
+def segment_through_glass(scene, desc, g, start, dir, k=8):
+    """Is the segment start .. start + dir clear but for glass? Over trace_rays_multi(k): per ray `clear` (every
+    recorded hit with t < 1 is on a DT_MAT_GLASS shape of desc), `panes` (how many such hits on glass) and
+    `truncated` (count == k and all k hits are glass with t < 1: more surfaces may follow on the segment, so
+    clear and panes are a lower bound only; ask again with a larger k, up to 8). Returns ({clear, panes,
+    truncated}, stats) as numpy arrays (bool, int32, bool).
+    For callers that want light or line of sight through the panes of a scene, which rays_occluded cannot give
+    (a pane shadows like a wall there). It is not the light loop's test, and differs from rays_occluded: no
+    1e-3 offset of the start, the shapes' intersect and not intersectShadow, no skip_shape, and every shape
+    counts once (its first intersection; the far side of a glass sphere is not a second pane)."""
+    import numpy as np
+    hits, st = trace_rays_multi(scene, g, start, dir, k=k, planes=("count", "shape", "t"))
+    shape, t, count = hits["shape"], hits["t"], hits["count"]
+    if hasattr(shape, "data_ptr"):
+        shape, t, count = shape.cpu().numpy(), t.cpu().numpy(), count.cpu().numpy()
+    glass = np.array([desc.shapes[i].material == DT_MAT_GLASS for i in range(desc.n_shapes)] + [False], bool)
+    on_seg = (np.arange(k)[None, :] < count[:, None]) & (t < np.float32(1))
+    is_glass = glass[shape]   # -1 (no hit) reads the appended False
+    return {"clear": ~(on_seg & ~is_glass).any(axis=1),
+            "panes": (on_seg & is_glass).sum(axis=1).astype(np.int32),
+            "truncated": (count == k) & (on_seg & is_glass).all(axis=1)}, st
 
 
 def feature_images(g, feats):

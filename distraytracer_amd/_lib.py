@@ -105,6 +105,15 @@ class RayHits(ctypes.Structure):
                 ("normal", ctypes.c_void_p), ("albedo", ctypes.c_void_p)]
 
 
+DT_MULTIHIT_MAX = 8   # the largest k of dt_trace_rays_multi (include/dt.h)
+
+
+class RayMultiHits(ctypes.Structure):
+    """dt_ray_multihits: the planes of dt_trace_rays_multi (a null pointer: not wanted)"""
+    _fields_ = [("count", ctypes.c_void_p), ("shape", ctypes.c_void_p), ("t", ctypes.c_void_p),
+                ("point", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("albedo", ctypes.c_void_p)]
+
+
 class RayOrderParams(ctypes.Structure):
     """dt_ray_order_params: origin_bits 0..10 and dir_bits 0..8 per axis (3*origin_bits + 2*dir_bits in 1..30),
     dir_major 0/1, box_given 0/1 and the box (finite, lo <= hi; read iff box_given)"""
@@ -218,7 +227,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_occlusion_params_default", "dt_render_occlusion", "dt_occlusion_ao_ray", "dt_occlusion_light_ray",
            "dt_points_occlusion",
            "dt_ray_order_params_default", "dt_ray_order_key", "dt_ray_order_workspace_bytes", "dt_ray_order",
-           "dt_permute_rows"]
+           "dt_permute_rows",
+           "dt_trace_rays_multi"]
 
 
 class DTError(RuntimeError):
@@ -318,6 +328,8 @@ def _load():
                                     c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_rays_occluded": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, c_int32, ctypes.c_void_p, P(Stats)]),
+        "dt_trace_rays_multi": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p, c_int32,
+                                          P(RayMultiHits), c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_ray_order_params_default": (None, [P(RayOrderParams)]),
         "dt_ray_order_key": (c_int32, [P(RayOrderParams), P(c_double), P(c_double), P(c_double), P(c_double),
                                        P(c_uint32)]),

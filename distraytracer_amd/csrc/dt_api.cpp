@@ -76,6 +76,10 @@ extern "C" hipError_t dt_launch_rayq_occl(const void* dev_launch, int64_t n, con
                                           const int32_t* skip_shape, uint8_t* occluded, int grid, hipStream_t stream);
 extern "C" const void* dt_rayq_kernel_ptr(void);
 extern "C" const void* dt_rayq_occl_kernel_ptr(void);
+extern "C" hipError_t dt_launch_rayq_multi(const void* dev_launch, int64_t n, const double* start, const double* dir,
+                                           int k, int32_t* count, int32_t* shape, float* t, double* point,
+                                           double* normal, double* albedo, int grid, hipStream_t stream);
+extern "C" const void* dt_rayq_multi_kernel_ptr(int k);
 extern "C" hipError_t dt_launch_mattes(const void* dev_launch, int n_samples, const int32_t* gmap, int layers, int32_t* id,
                                        float* weight, int32_t* distinct, unsigned long long* overflow, int grid,
                                        hipStream_t stream);
@@ -1857,6 +1861,59 @@ int dt_trace_rays(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, con
   if (int rc = aux.start()) return rc;
   if (int rc = aux.finish(dt_launch_rayq(aux.launch, n_rays, (const double*)dstart, (const double*)ddir, (int32_t*)dev[0],
                                          (float*)dev[1], (double*)dev[2], (double*)dev[3], (double*)dev[4], grid, aux.st)))
+    return rc;
+  if (stats) {
+    stats->rays = aux.h[ST_RAYS];
+    stats->tex_fetches = aux.h[ST_TEX];
+    stats->uv_out_of_range = aux.h[ST_UV];
+    stats->prism_norm_fallback = aux.h[ST_PRISM];
+    stats->kernel_ms = aux.kernel_ms;
+  }
+  return DT_OK;
+}
+
+// dt_trace_rays_multi: dt_rayq_multi_kernel in the smallest list capacity (1, 2, 4, 8) that holds k; the
+// resident waves are cached per capacity, as each is a kernel of its own
+int dt_trace_rays_multi(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, const double* start,
+                        const double* dir, int32_t k, const dt_ray_multihits* out, int32_t on_device, void* stream,
+                        dt_stats* stats)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  if (!sc) return fail(DT_E_INVALID, "dt_trace_rays_multi: null scene");
+  if (!g) return fail(DT_E_INVALID, "dt_trace_rays_multi: null globals");
+  if (!start) return fail(DT_E_INVALID, "dt_trace_rays_multi: null start");
+  if (!dir) return fail(DT_E_INVALID, "dt_trace_rays_multi: null dir");
+  if (!out) return fail(DT_E_INVALID, "dt_trace_rays_multi: null out");
+  if (!out->count && !out->shape && !out->t && !out->point && !out->normal && !out->albedo)
+    return fail(DT_E_INVALID, "dt_trace_rays_multi: out wants no plane (every pointer is null)");
+  if (n_rays < 0) return fail(DT_E_INVALID, "dt_trace_rays_multi: n_rays < 0");
+  if (k < 1 || k > DT_MULTIHIT_MAX)
+    return fail(DT_E_INVALID, "dt_trace_rays_multi: k = " + std::to_string(k) + " outside 1.." +
+                                  std::to_string(DT_MULTIHIT_MAX));
+  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_trace_rays_multi: scenes with a RectPrismWithCylinder");
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n_rays == 0) return DT_OK;
+  dtd::DParams P;
+  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, false)) return rc;
+  const size_t n = (size_t)n_rays, nk = n * (size_t)k;
+  void *dstart = nullptr, *ddir = nullptr;
+  if (int rc = aux.plane(start, 3 * n * sizeof(double), on_device, true, false, &dstart)) return rc;
+  if (int rc = aux.plane(dir, 3 * n * sizeof(double), on_device, true, false, &ddir)) return rc;
+  void* host[6] = {out->count, out->shape, out->t, out->point, out->normal, out->albedo};
+  void* dev[6];
+  const size_t bytes[6] = {n * sizeof(int32_t),      nk * sizeof(int32_t),     nk * sizeof(float),
+                           3 * nk * sizeof(double),  3 * nk * sizeof(double),  3 * nk * sizeof(double)};
+  for (int p = 0; p < 6; ++p)
+    if (int rc = aux.plane(host[p], bytes[p], on_device, false, true, &dev[p])) return rc;
+  static int resident[4] = {0, 0, 0, 0};   // per capacity 1, 2, 4, 8
+  const int slot = k <= 1 ? 0 : k <= 2 ? 1 : k <= 4 ? 2 : 3;
+  const int grid = aux_grid(dt_rayq_multi_kernel_ptr(k), resident[slot], (n_rays + 63) / 64);
+  if (int rc = aux.start()) return rc;
+  if (int rc = aux.finish(dt_launch_rayq_multi(aux.launch, n_rays, (const double*)dstart, (const double*)ddir, k,
+                                               (int32_t*)dev[0], (int32_t*)dev[1], (float*)dev[2], (double*)dev[3],
+                                               (double*)dev[4], (double*)dev[5], grid, aux.st)))
     return rc;
   if (stats) {
     stats->rays = aux.h[ST_RAYS];

@@ -117,6 +117,11 @@ using namespace dtd;
 #if DT_OCCL || DT_POCCL
 #include "dt_occl.h"
 #endif
+// DT_MHIT=1 (an eleventh compilation, build/dt_kernels_mhit.o): only dt_rayq_multi_kernel, the multi-hit ray
+// query of dt_trace_rays_multi in its four list capacities, for the same reason
+#ifndef DT_MHIT
+#define DT_MHIT 0
+#endif
 // DT_W5=1 (build/dt_kernels_w5.o): the trace kernel at 5 waves per SIMD (96 VGPRs, under 8 KiB of
 // LDS per wave: DT_PSUM_LDS=2), launched for one-pixel-per-wave work (spp >= 64; never
 // with more than 8 pixels per wave, the slots DT_PSUM_LDS=2 keeps)
@@ -1674,6 +1679,127 @@ __device__ __forceinline__ bool closest_hit_walk(const DScene& S, const DParams&
   return any;
 }
 
+// Multi-hit walks (dt_rayq_multi_kernel, include/dt.h dt_trace_rays_multi): a lane's K nearest hits, sorted by
+// the key (t, shape) ascending; an empty slot holds (FLT_MAX, INT_MAX), which every hit's key (t < FLT_MAX)
+// precedes, so the number of hits is the number of slots with t < FLT_MAX and no count is carried. The
+// list must stay in registers: every slot is named by a constant (the recursion over J below, no loop to
+// unroll, no dynamic index that would send the array to scratch).
+template <int K>
+struct HitList {
+  float t[K];
+  int s[K];
+};
+
+template <int K>
+__device__ __forceinline__ void hitlist_clear(HitList<K>& L)
+{
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    L.t[j] = FLT_MAX;
+    L.s[j] = 0x7fffffff;
+  }
+}
+
+__device__ __forceinline__ bool hitkey_less(float t, int s, float t1, int s1)
+{
+  return t < t1 || (t == t1 && s < s1);
+}
+
+// Slots J .. 0 of a compare-and-shift insertion, from the back: slot J takes slot J-1 where the key precedes
+// that one too (read before the step below overwrites it), the key where it precedes slot J only. `here`: on,
+// and the key precedes slot J. One key compare per slot.
+template <int K, int J>
+__device__ __forceinline__ void hitlist_step(HitList<K>& L, bool on, float t, int s, bool here)
+{
+  if constexpr (J > 0) {
+    const bool prev = on && hitkey_less(t, s, L.t[J - 1], L.s[J - 1]);
+    L.t[J] = prev ? L.t[J - 1] : here ? t : L.t[J];
+    L.s[J] = prev ? L.s[J - 1] : here ? s : L.s[J];
+    hitlist_step<K, J - 1>(L, on, t, s, prev);
+  } else {
+    L.t[0] = here ? t : L.t[0];
+    L.s[0] = here ? s : L.s[0];
+  }
+}
+
+template <int K>
+__device__ __forceinline__ void hitlist_insert(HitList<K>& L, bool on, float t, int s)
+{
+  hitlist_step<K, K - 1>(L, on, t, s, on && hitkey_less(t, s, L.t[K - 1], L.s[K - 1]));
+}
+
+// The first entry, and the rest moved up by one (the attribute loop of dt_rayq_multi_kernel takes the hits
+// one by one through slot 0, so its runtime trip count indexes nothing)
+template <int K>
+__device__ __forceinline__ void hitlist_pop(HitList<K>& L, float& t, int& s)
+{
+  t = L.t[0];
+  s = L.s[0];
+#pragma unroll
+  for (int j = 0; j + 1 < K; ++j) {
+    L.t[j] = L.t[j + 1];
+    L.s[j] = L.s[j + 1];
+  }
+  L.t[K - 1] = FLT_MAX;
+  L.s[K - 1] = 0x7fffffff;
+}
+
+// closest_hit_walk's structure at shift 0 (MODE 0: finite rays on the fast tree; 1: the reference tree, exact
+// for any wave), with every gathered shape tested on its own (t enters as FLT_MAX, nothing carried) and kept
+// in the lane's list; a hit is a true return with t < FLT_MAX (false for NaN and for the edge-on
+// checkerboard return, which leaves t alone). The list is a function of the set of gathered shapes only (a
+// total order on (t, shape), every shape in one leaf), so neither tree nor visiting order shows in it, and
+// the edge-on re-walk of closest_hit has no counterpart here.
+// Culling: closest_hit_walk's bound, from the K-th distance once the list is full (tcull = FLT_MAX before).
+// A hit that could still enter the list has t <= t_K, at a point of its shape, hence inside the leaf's box:
+// the box's entry parameter is <= t up to the rounding of the two float computations, which the bound's
+// relative 1e-4 and absolute 1e-4 cover as they do for closest_hit_walk's t_min, so the leaf passes
+// tmin <= tcull, equal t included. t_K only shrinks, so with the monotone finite-ray slab test a lane that
+// failed an ancestor fails below it too (no resume point, as in closest_hit_walk). MODE 1 does not cull
+// (node_hit<true> reads no tcull).
+template <int MODE, int K>
+__device__ __forceinline__ void multi_hit_walk(const DScene& S, const DParams& P, const Walk& w, bool active, V3 ray,
+                                               V3 org, HitList<K>& L)
+{
+  static_assert(MODE == 0 || MODE == 1, "the shift is 0: never the bump tree");
+  constexpr bool GENERAL = MODE == 1;
+  const bool ftree = !GENERAL && P.n_fnodes > 0 && (P.ftree_mode & 1);
+  const DNodeDev* const NODES = ftree ? S.fnodes : S.nodes;
+  const int n_nodes = ftree ? P.n_fnodes : P.n_nodes;
+  int resume = active ? 0 : 0x7fffffff;
+  const unsigned long long am = __ballot(active);
+  int i = 0;
+  while (i < n_nodes) {
+    const DNodeDev nd = cas(NODES)[i];
+    const bool act = GENERAL ? resume <= i : inv(am);
+    const float tk = L.t[K - 1];
+    const float tcull = tk == FLT_MAX ? FLT_MAX : tk * 1.0001f + 1e-4f;
+    const unsigned long long hbm = node_mask<GENERAL>(w, nd, 0.0f, org, tcull, am, act);
+    const bool hb = inv(hbm);
+    if (nd.meta & DN_LEAF) {
+      if (hbm) {
+        const int nq = (nd.meta & DN_SINGLE) ? 1 : nd.aux;
+        for (int q = 0; q < nq; ++q) {
+          int sid, type, off;
+          uint32_t flags;
+          leaf_shape(S, nd, q, sid, type, flags, off);
+          if (inv(hbm)) {
+            float t = FLT_MAX;
+            int ins = 0, cc = -1, edge = 0;
+            const bool ret = shape_hit(S, sid, type, flags, cas(S.geom) + off, ray, org, 0.0f, t, ins, cc, edge);
+            hitlist_insert(L, ret && t < FLT_MAX, t, sid);
+          }
+        }
+      }
+      if (GENERAL && act) resume = nd.skip;
+      i = i + 1;
+    } else {
+      if (GENERAL && act && !hb) resume = nd.skip;
+      i = hbm ? i + 1 : nd.skip;
+    }
+  }
+}
+
 // Closest hit of primary rays over their pixel block's candidate leaves (host_primlists.cpp), in
 // order of the smallest ray parameter each leaf's box can be reached at: once every lane's best hit
 // lies before the next entry, no later leaf can change a result. Same box filter, shape tests and
@@ -2341,8 +2467,8 @@ struct Ctx {
   Rng rng;
 };
 
-#if DT_FEAT || DT_RAYQ || DT_FEATP || DT_OCCL
-// What dt_features_kernel takes from run_pass (dt_rayq_kernel and dt_features_path_kernel too), as copies for its build only: with run_pass calling
+#if DT_FEAT || DT_RAYQ || DT_FEATP || DT_OCCL || DT_MHIT
+// What dt_features_kernel takes from run_pass (dt_rayq_kernel, dt_rayq_multi_kernel and dt_features_path_kernel too), as copies for its build only: with run_pass calling
 // these helpers, some trace builds' objects came out as other bytes (the room builds with hit_color,
 // every build with texel_color), and the product kernels' objects are to stay byte-identical.
 // hit_color: the colour the reference's intersect() leaves in the hit shape (a Checkerboard's square,
@@ -3686,8 +3812,8 @@ extern "C" hipError_t dt_launch_features_path(const void* dev_launch, int n_samp
   return hipGetLastError();
 }
 extern "C" const void* dt_features_path_kernel_ptr(void) { return (const void*)dt_features_path_kernel; }
-#elif DT_RAYQ
-// Ray queries (include/dt.h dt_trace_rays, dt_rays_occluded; no reference counterpart): rays the caller
+#elif DT_RAYQ || DT_MHIT
+// Ray queries (include/dt.h dt_trace_rays, dt_rays_occluded, dt_trace_rays_multi; no reference counterpart): rays the caller
 // hands over in memory, 3 doubles of start and of direction each, one ray per lane, 64 consecutive rays
 // per wave, grid-stride over the waves as dt_isect_kernel. The walks are the wave-uniform ones of the
 // trace kernel (node and shape data through scalar loads, the lanes' decisions as masks), so a wave
@@ -3713,6 +3839,7 @@ __device__ __forceinline__ bool rayq_load(const double* __restrict__ start, cons
   return live;
 }
 
+#if DT_RAYQ
 // dt_trace_rays: rayColor's gather and closest hit (cpp:491-538) at shift 0, as dt_isect_kernel takes it
 // without a primary list (pblock -1: the fast tree; the exact walk for a wave with an axis-parallel ray
 // and after an edge-on checkerboard hit), and per hit what dt_features_kernel computes for one sample.
@@ -3856,6 +3983,134 @@ extern "C" hipError_t dt_launch_rayq_occl(const void* dev_launch, int64_t n, con
 }
 extern "C" const void* dt_rayq_kernel_ptr(void) { return (const void*)dt_rayq_kernel; }
 extern "C" const void* dt_rayq_occl_kernel_ptr(void) { return (const void*)dt_rayq_occl_kernel; }
+#else   // DT_MHIT
+// dt_trace_rays_multi: per ray the k nearest of the shapes dt_trace_rays gathers, each tested on its own
+// (multi_hit_walk: the fast tree for finite waves, the reference tree for a wave with an axis-parallel ray),
+// in a list of K >= k register slots per lane (K: 1, 2, 4 or 8; the host launches the smallest that holds k),
+// of which the first k are written. Then per rank j < k, at wave-uniform control flow, what dt_rayq_kernel
+// computes for its one hit, for the lanes with j < count; the other lanes write -1, FLT_MAX and zeros, so
+// every element of every wanted plane is written. The walk carries no checker colour per slot (8 more live
+// registers at K = 8): where albedo is wanted, a recorded checkerboard is tested once more (t reset) for
+// its square.
+template <int K>
+__global__ void __launch_bounds__(64)
+dt_rayq_multi_kernel(const DLaunch* __restrict__ Lp, int64_t n, const double* __restrict__ start,
+                     const double* __restrict__ dir, int k, int32_t* __restrict__ count_out,
+                     int32_t* __restrict__ shape_out, float* __restrict__ t_out, double* __restrict__ point,
+                     double* __restrict__ normal, double* __restrict__ albedo)
+{
+  const DScene& S = Lp->S;
+  const DParams& P = Lp->P;
+  const int lane = threadIdx.x;
+  __shared__ unsigned int wc_lds[WC_N];
+  if (lane < WC_N) wc_lds[lane] = 0;
+  __syncthreads();
+  unsigned int* const wc = wc_lds;
+  unsigned long long traced = 0;   // wave-uniform
+  for (int64_t base = (int64_t)blockIdx.x * DT_WAVE; base < n; base += (int64_t)gridDim.x * DT_WAVE) {
+    const int64_t i = base + lane;
+    const bool in = i < n;
+    V3 org, ray;
+    const bool act = rayq_load(start, dir, i, in, org, ray);
+    const unsigned long long am = __ballot(act);
+    traced += (unsigned long long)__popcll(am);
+    HitList<K> L;
+    hitlist_clear(L);
+    if (am) {
+      const Walk w = make_walk(P, act, ray, org, 0.0f);
+      if (w.inf_wave) multi_hit_walk<1>(S, P, w, act, ray, org, L);
+      else multi_hit_walk<0>(S, P, w, act, ray, org, L);
+    }
+    if (in && count_out) {
+      int c = 0;
+#pragma unroll
+      for (int j = 0; j < K; ++j) c += L.t[j] < FLT_MAX ? 1 : 0;
+      count_out[i] = c < k ? c : k;
+    }
+    for (int j = 0; j < k; ++j) {
+      float tj;
+      int sj;
+      hitlist_pop(L, tj, sj);
+      const bool hit = act && tj < FLT_MAX;   // j < count
+      V3 p = v3(0, 0, 0), nrm = v3(0, 0, 0), col = v3(0, 0, 0);
+      if (hit && (point || normal || albedo)) {
+        const DShapeHdr hd = S.hdr[sj];
+        GP g = cas(S.geom) + hd.off;
+        const DMat& M = S.mat[sj];
+        p = add(org, mul(tj, ray));
+        int ccol = -1;
+        if (albedo && (hd.type == DT_SHAPE_CHECKERBOARD || hd.type == DT_SHAPE_CHECKERBOARD_HOLE)) {
+          float t2 = FLT_MAX;
+          int ins = 0, edge = 0;
+          shape_hit(S, sj, hd.type, hd.flags, g, ray, org, 0.0f, t2, ins, ccol, edge);
+        }
+        if (normal) {
+          nrm = shape_norm(hd.type, hd.flags, g, p, 0.0f, wc + WC_PRISM, ccol);
+          const V3 in_dir = normalized(ray);
+          if (dot(mul(1e4, in_dir), nrm) >= 0) nrm = mul(-1, nrm);   // fixNorm
+        }
+        if (albedo) {
+          col = hit_color(g, M, ccol);
+          if (M.flags & DT_F_TEXTURE) {
+            double tu = 0, tv = 0;
+            const int uvt = shape_uv(hd.type, hd.flags, g, p, 0.0f, tu, tv);
+            if (uvt == 2) {
+              col = v3a(M.bordercolor);
+            } else if (uvt == 1 && M.tex >= 0) {
+              col = texel_color(S, M, tu, tv);
+              atomicAdd(wc + WC_TEX, 1u);
+            }
+            if (uvt != 0 && (tu < 0 || tv < 0 || tu > 1 || tv > 1)) atomicAdd(wc + WC_UV, 1u);
+          }
+        }
+      }
+      if (in) {
+        const int64_t e = (int64_t)k * i + j;
+        if (shape_out) shape_out[e] = hit ? sj : -1;
+        if (t_out) t_out[e] = hit ? tj : FLT_MAX;
+        if (point) { point[3 * e] = p.x; point[3 * e + 1] = p.y; point[3 * e + 2] = p.z; }
+        if (normal) { normal[3 * e] = nrm.x; normal[3 * e + 1] = nrm.y; normal[3 * e + 2] = nrm.z; }
+        if (albedo) { albedo[3 * e] = col.x; albedo[3 * e + 1] = col.y; albedo[3 * e + 2] = col.z; }
+      }
+    }
+  }
+  __syncthreads();
+  const int st_of[WC_N] = {ST_RAYS, ST_SHADOW, ST_TEX, ST_STACK, ST_REFL, ST_GLOSSY, ST_UV, ST_PRISM, ST_SPHL};
+  if (lane < WC_N) {
+    const unsigned long long v = lane == WC_RAYS ? traced : wc_lds[lane];
+    if (v) atomicAdd(S.stats + st_of[lane], v);
+  }
+}
+
+// the list capacity a launch with k takes: the smallest of 1, 2, 4, 8 that holds it
+static int rayq_multi_capacity(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
+
+extern "C" hipError_t dt_launch_rayq_multi(const void* dev_launch, int64_t n, const double* start, const double* dir,
+                                           int k, int32_t* count, int32_t* shape, float* t, double* point,
+                                           double* normal, double* albedo, int grid, hipStream_t stream)
+{
+#define DT_MHIT_LAUNCH(K)                                                                                            \
+  hipLaunchKernelGGL(dt_rayq_multi_kernel<K>, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n, start, \
+                     dir, k, count, shape, t, point, normal, albedo)
+  switch (rayq_multi_capacity(k)) {
+    case 1: DT_MHIT_LAUNCH(1); break;
+    case 2: DT_MHIT_LAUNCH(2); break;
+    case 4: DT_MHIT_LAUNCH(4); break;
+    default: DT_MHIT_LAUNCH(8); break;
+  }
+#undef DT_MHIT_LAUNCH
+  return hipGetLastError();
+}
+extern "C" const void* dt_rayq_multi_kernel_ptr(int k)
+{
+  switch (rayq_multi_capacity(k)) {
+    case 1: return (const void*)dt_rayq_multi_kernel<1>;
+    case 2: return (const void*)dt_rayq_multi_kernel<2>;
+    case 4: return (const void*)dt_rayq_multi_kernel<4>;
+    default: return (const void*)dt_rayq_multi_kernel<8>;
+  }
+}
+#endif
 #elif DT_OCCL
 // Occlusion feature buffers (include/dt.h dt_render_occlusion; no reference counterpart): for the samples
 // 0 .. n_samples-1 of every owned pixel the render's own primary ray to its closest hit, as
@@ -5111,7 +5366,7 @@ extern "C" hipError_t dt_launch_unpack(const void* dev_launch, int world, int64_
 }
 #endif
 
-#if !DT_ISECT && !DT_FEAT && !DT_RAYQ && !DT_MATTE && !DT_FEATP && !DT_OCCL && !DT_POCCL
+#if !DT_ISECT && !DT_FEAT && !DT_RAYQ && !DT_MATTE && !DT_FEATP && !DT_OCCL && !DT_POCCL && !DT_MHIT
 // every trace-kernel build: <kernel>_launch and <kernel>_ptr (dt_api.cpp's kernel table)
 #if DT_W5
 static_assert(DT_TRACE_MIN_WAVES == 5 && DT_PSUM_LDS == 2, "5-wave build: Makefile W5FLAGS");

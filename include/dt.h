@@ -75,6 +75,8 @@ extern "C" {
 /* (still 8, new exports and one new struct, no struct changed: dt_ray_order_params_default, dt_ray_order_key,
  *    dt_ray_order_workspace_bytes, dt_ray_order and its dt_ray_order_params, dt_permute_rows -- ray ordering:
  *    sort caller-supplied rays into coherent waves) */
+/* (still 8, one new export and one new struct, no struct changed: dt_trace_rays_multi and its
+ *    dt_ray_multihits -- multi-hit ray queries: the k nearest surfaces along caller-supplied rays) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -704,6 +706,54 @@ int dt_trace_rays(const dt_scene* s, const dt_globals* g, int64_t n_rays, const 
 int dt_rays_occluded(const dt_scene* s, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
                      const int32_t* skip_shape /* optional, n_rays; -1: none */, uint8_t* occluded,
                      int32_t on_device, void* stream, dt_stats* stats);
+
+/* ---- multi-hit ray queries: the k nearest surfaces along caller-supplied rays ----
+ * No reference counterpart. dt_trace_rays says what a ray hits first; this call says what lies behind it: per
+ * ray the k nearest shapes along it, ordered. Seeing through the panes of a scene, picking the object behind
+ * the front one, thickness, X-ray views, depth peeling and a caller's own transparent-shadow rule start here.
+ * Rays, the void-ray rule, sides and staging, g, synchrony, "a render afterwards is unaffected" and the thread
+ * rule are dt_trace_rays's. A void ray has count 0.
+ *
+ * Every answer is defined bit for bit and independent of the order of the work:
+ *   CANDIDATES  the shapes dt_trace_rays gathers for the ray (dir, start) at shift 0: every leaf whose box the
+ *     ray passes.
+ *   PER-SHAPE TEST  each gathered shape h is tested on its own: intersect(dir, start) with t entering as
+ *     FLT_MAX. Nothing is carried from shape to shape (dt_trace_rays carries t).
+ *   HIT  h is a hit iff intersect returns true and t_h < FLT_MAX (false for a NaN). An edge-on checkerboard
+ *     hit, which returns true without writing t (Q16, oracle.c shape_intersect), is therefore not a hit here.
+ *   ONE HIT PER SHAPE  a shape contributes at most one hit, its own first intersection: the far side of a
+ *     sphere, a cylinder or a prism is not a second hit.
+ *   RANKING  hits are ordered by t ascending (float compare), ties by shape index ascending. The first
+ *     min(k, hits) are recorded; count is that number. Tree and visiting order cannot matter.
+ *   ATTRIBUTES  each recorded hit gets what dt_trace_rays computes for its one hit: point, getNorm + fixNorm,
+ *     the colour rule with the checker square, texel and border colour; computed only for the planes that
+ *     take them.
+ * Relation to dt_trace_rays: with k = 1, shape[i] and t[i] equal dt_trace_rays's wherever the smallest t is
+ * attained by one gathered shape only and no gathered shape takes the edge-on path. Nothing more is promised
+ * (dt_trace_rays breaks ties by gather order and lets an edge-on hit keep the previous shape's t).
+ * stats (optional): rays = the non-void rays; prism_norm_fallback per recorded hit, iff normal is wanted;
+ * tex_fetches and uv_out_of_range per recorded hit, iff albedo is; kernel_ms; everything else 0.
+ *
+ * The walk is dt_trace_rays's wave-uniform one, with a per-ray sorted list of k hits in registers; a ray's
+ * list culls the tree by its k-th distance once it is full, so a larger k walks further. The ordering advice
+ * of dt_trace_rays holds (dt_ray_order). Cost: BASELINE.md "Multi-hit ray queries". */
+#define DT_MULTIHIT_MAX 8
+typedef struct dt_ray_multihits {   /* each plane optional (NULL: not wanted), not all NULL; all on one side */
+  int32_t* count;   /* 1 per ray: hits recorded, 0..k */
+  int32_t* shape;   /* k per ray, entry k*i + j: the shape ranked j; -1 for j >= count[i] */
+  float*   t;       /* k per ray, same indexing: its t along the unnormalised dir; FLT_MAX for j >= count */
+  double*  point;   /* 3k per ray, entry 3*(k*i + j) + c: start + (double)t * dir; zeros beyond count */
+  double*  normal;  /* same indexing: fixNorm(normalized(dir), getNorm(point)); zeros beyond count */
+  double*  albedo;  /* same indexing: dt_trace_rays's colour rule at that hit; zeros beyond count */
+} dt_ray_multihits;
+
+/* DT_E_INVALID, with a dt_last_error starting "dt_trace_rays_multi: " and naming the argument: a null scene,
+ * globals, start, dir or out, an out with every plane NULL, n_rays < 0, k outside 1..DT_MULTIHIT_MAX;
+ * DT_E_UNSUPPORTED: a scene with a RectPrismWithCylinder; all before any device work. n_rays == 0: DT_OK,
+ * nothing is launched. */
+int dt_trace_rays_multi(const dt_scene* s, const dt_globals* g, int64_t n_rays, const double* start,
+                        const double* dir, int32_t k /* 1..DT_MULTIHIT_MAX */, const dt_ray_multihits* out,
+                        int32_t on_device, void* stream, dt_stats* stats);
 
 /* ---- ray ordering: sort caller-supplied rays into coherent waves ----
  * No reference counterpart. The ray queries serve 64 consecutive array entries with one wave, and a wave walks
