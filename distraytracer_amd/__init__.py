@@ -29,6 +29,7 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "Camera", "camera", "TemporalParams", "temporal_params_default", "reproject", "TemporalAccumulator",
            "trace_rays", "rays_occluded", "RAY_PLANES",
            "trace_rays_multi", "segment_through_glass", "RAY_MULTI_PLANES",
+           "camera_rays", "camera_rays_rows", "rays_resolve", "peel_layers", "RESOLVE_MODES",
            "RayOrderParams", "RayOrder", "ray_order_params_default", "ray_order_key", "ray_order", "DT_RAY_ORDER_TILE",
            "render_mattes", "matte_mask", "shape_groups", "MATTE_PLANES",
            "UpsampleParams", "upsample_params_default", "upsample", "low_res_globals",
@@ -886,6 +887,118 @@ def segment_through_glass(scene, desc, g, start, dir, k=8):
     return {"clear": ~(on_seg & ~is_glass).any(axis=1),
             "panes": (on_seg & is_glass).sum(axis=1).astype(np.int32),
             "truncated": (count == k) & (on_seg & is_glass).all(axis=1)}, st
+
+
+RESOLVE_MODES = {"mean": 0, "hit_mean": 1}   # DT_RESOLVE_MEAN, DT_RESOLVE_HIT_MEAN
+
+
+def _sample_range(what, samples):
+    try:
+        b, e = (int(v) for v in samples)
+    except (TypeError, ValueError):
+        raise DTError("%s: samples must be a pair (begin, end), not %r" % (what, samples))
+    return b, e
+
+
+def camera_rays_rows(g, samples=(0, 1), tile=None):
+    """Rows of camera_rays' arrays for (g, tile, samples): accum_doubles(g, tile) // 3 * (end - begin)."""
+    b, e = _sample_range("camera_rays_rows", samples)
+    n = int(lib.dt_camera_rays_rows(ctypes.byref(g), ctypes.byref(tile) if tile else None, b, e))
+    if n < 0:
+        raise DTError("camera_rays_rows: %s" % lib.dt_last_error().decode(errors="replace"))
+    return n
+
+
+def camera_rays(g, frame=0, samples=(0, 1), tile=None, out=None, stream=None, host=False):
+    """The render's own camera rays as arrays (include/dt.h dt_camera_rays): for the samples begin .. end-1 of
+    every owned pixel the ray render() starts that sample from, bit for bit. Returns (start, dir), float64,
+    shaped (slots, ns, 3): slot q is the pixel whose colour sits at floats 3q..3q+2 of render's output (image
+    or slab layout per `tile`), ns = end - begin. CUDA tensors by default, numpy arrays with host=True, zero-filled
+    so that the rows of pixels the tile share does not own are void rays for the ray queries. `out`: a pair
+    (start, dir) to write into instead, where only owned rows are written. No scene is needed. Only the
+    thin-lens perspective camera of the renders; the motion-blur re-trace of frames >= frame_prism is not
+    reproduced. Pass the arrays (reshaped to (-1, 3) or as they are) to trace_rays, rays_occluded,
+    trace_rays_multi, and the answers to rays_resolve."""
+    b, e = _sample_range("camera_rays", samples)
+    ns = e - b
+    rows = camera_rays_rows(g, (b, e), tile)
+    if out is None:
+        if host:
+            import numpy as np
+            out = (np.zeros((rows // ns, ns, 3), np.float64), np.zeros((rows // ns, ns, 3), np.float64))
+        else:
+            import torch
+            out = (torch.zeros((rows // ns, ns, 3), dtype=torch.float64, device="cuda"),
+                   torch.zeros((rows // ns, ns, 3), dtype=torch.float64, device="cuda"))
+    start, dir = out
+    sp, sdev = _ptr_typed(start, "torch.float64", "float64")
+    dp, ddev = _ptr_typed(dir, "torch.float64", "float64")
+    if sdev != ddev or _numel_any(start) != 3 * rows or _numel_any(dir) != 3 * rows:
+        raise DTError("camera_rays: start and dir hold 3 doubles for each of the %d rows, on the same side" % rows)
+    check(lib.dt_camera_rays(ctypes.byref(g), int(frame), ctypes.byref(tile) if tile else None, b, e, sp, dp, sdev,
+                             ctypes.c_void_p(stream) if stream else None, None), "dt_camera_rays")
+    return start, dir
+
+
+def rays_resolve(g, values, n_samples, shape=None, mode="mean", tile=None, coverage=False, out=None, stream=None):
+    """Per-ray answers back to per-pixel planes (include/dt.h dt_rays_resolve): values holds `width` (1..3)
+    float64 per row in camera_rays' row order with n_samples rows per slot -- shaped (slots, n_samples, width),
+    (rows, width) or, for width 1, (rows,). Per owned pixel and component the f64 sum of its rows, left to right,
+    divided by n_samples (mode "mean") or by the number of rows that count ("hit_mean", 0 where none does);
+    `shape` (int32 per row, such as trace_rays' shape plane): rows with shape < 0 add nothing and do not count.
+    Returns the float32 plane shaped (slots, width), or (plane, coverage) with coverage=True (the rows that
+    count / n_samples, float32 per slot), on the side of values (numpy, or the tensor's device); unowned pixels
+    stay 0, or as they came in `out` (a plane, or a pair with coverage=True). f64 rows only."""
+    what = "rays_resolve"
+    n = int(n_samples)
+    slots = accum_doubles(g, tile) // 3
+    vp, side = _ptr_typed(values, "torch.float64", "float64")
+    total = _numel_any(values)
+    if n < 1 or slots * n == 0 or total % (slots * n) or not 1 <= total // (slots * n) <= 3:
+        raise DTError("%s: values holds %d doubles, not 1..3 for each of %d slots x %d samples" % (what, total, slots, n))
+    width = total // (slots * n)
+    if mode not in RESOLVE_MODES:
+        raise DTError("%s: mode must be one of %s, not %r" % (what, sorted(RESOLVE_MODES), mode))
+    hp = _ray_out(what, "shape", shape, slots * n, 1, "torch.int32", "int32", side) if shape is not None else None
+    plane, cov = (out if coverage else (out, None)) if out is not None else (None, None)
+    if plane is None:
+        plane = _ray_new(values, (slots, width), "torch.float32", "float32")
+    if coverage and cov is None:
+        cov = _ray_new(values, (slots,), "torch.float32", "float32")
+    pp = _ray_out(what, "out", plane, slots, width, "torch.float32", "float32", side)
+    cp = _ray_out(what, "coverage", cov, slots, 1, "torch.float32", "float32", side) if coverage else None
+    check(lib.dt_rays_resolve(ctypes.byref(g), ctypes.byref(tile) if tile else None, n, width, vp, hp,
+                              RESOLVE_MODES[mode], pp, cp, side, ctypes.c_void_p(stream) if stream else None), "dt_rays_resolve")
+    return (plane, cov) if coverage else plane
+
+
+def peel_layers(scene, g, frame, k=4, n_samples=1, planes=("albedo",)):
+    """Depth peeling of the render's own view, a worked consumer of camera_rays -> trace_rays_multi ->
+    rays_resolve: layer j is what the camera's rays meet as their (j+1)-th surface. Returns a dict of numpy
+    arrays in image row order (row 0 is the top row, as in the written images): for each plane asked for
+    ("albedo", "normal") an array (k, yRes, xRes, 3), the mean over the pixel's n_samples rays of the rank-j
+    hit's value, a ray with fewer than j+1 hits adding nothing (coverage-premultiplied); and "coverage"
+    (k, yRes, xRes), the fraction of the pixel's rays with a rank-j hit. Whole frames."""
+    import torch
+    for name in planes:
+        if name not in ("albedo", "normal"):
+            raise DTError("peel_layers: unknown plane %r" % (name,))
+    n = int(n_samples)
+    start, dir = camera_rays(g, frame, samples=(0, n))
+    hits, _ = trace_rays_multi(scene, g, start.view(-1, 3), dir.view(-1, 3), k=k, planes=("shape",) + tuple(planes))
+    W, H = g.xRes, g.yRes
+    out = {name: torch.zeros((k, H * W, 3), dtype=torch.float32, device="cuda") for name in planes}
+    cov = torch.zeros((k, H * W), dtype=torch.float32, device="cuda")
+    for j in range(k):
+        shape_j = hits["shape"][:, j].contiguous()
+        for name in planes:
+            rays_resolve(g, hits[name][:, j, :].contiguous(), n, shape=shape_j, out=(out[name][j], cov[j]), coverage=True)
+        if not planes:
+            rays_resolve(g, torch.zeros(H * W * n, dtype=torch.float64, device="cuda"), n, shape=shape_j,
+                         out=(torch.zeros((H * W, 1), dtype=torch.float32, device="cuda"), cov[j]), coverage=True)
+    res = {name: a.cpu().numpy().reshape(k, H, W, 3) for name, a in out.items()}
+    res["coverage"] = cov.cpu().numpy().reshape(k, H, W)
+    return res
 
 
 def feature_images(g, feats):

@@ -106,6 +106,8 @@ class RayHits(ctypes.Structure):
 
 
 DT_MULTIHIT_MAX = 8   # the largest k of dt_trace_rays_multi (include/dt.h)
+DT_CAMERA_RAYS_MAX_SAMPLES = 1024   # the longest sample range of dt_camera_rays, the largest n_samples of dt_rays_resolve
+DT_RESOLVE_MEAN, DT_RESOLVE_HIT_MEAN = 0, 1   # dt_rays_resolve's modes (include/dt.h)
 
 
 class RayMultiHits(ctypes.Structure):
@@ -228,7 +230,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_points_occlusion",
            "dt_ray_order_params_default", "dt_ray_order_key", "dt_ray_order_workspace_bytes", "dt_ray_order",
            "dt_permute_rows",
-           "dt_trace_rays_multi"]
+           "dt_trace_rays_multi",
+           "dt_camera_rays_rows", "dt_camera_rays", "dt_rays_resolve"]
 
 
 class DTError(RuntimeError):
@@ -330,6 +333,11 @@ def _load():
                                        ctypes.c_void_p, ctypes.c_void_p, c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_trace_rays_multi": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p, c_int32,
                                           P(RayMultiHits), c_int32, ctypes.c_void_p, P(Stats)]),
+        "dt_camera_rays_rows": (c_int64, [P(Globals), P(Tiles), c_int32, c_int32]),
+        "dt_camera_rays": (c_int32, [P(Globals), c_int32, P(Tiles), c_int32, c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                     c_int32, ctypes.c_void_p, P(c_float)]),
+        "dt_rays_resolve": (c_int32, [P(Globals), P(Tiles), c_int32, c_int32, ctypes.c_void_p, ctypes.c_void_p, c_int32,
+                                      ctypes.c_void_p, ctypes.c_void_p, c_int32, ctypes.c_void_p]),
         "dt_ray_order_params_default": (None, [P(RayOrderParams)]),
         "dt_ray_order_key": (c_int32, [P(RayOrderParams), P(c_double), P(c_double), P(c_double), P(c_double),
                                        P(c_uint32)]),

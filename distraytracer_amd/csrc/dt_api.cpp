@@ -92,6 +92,8 @@ extern "C" hipError_t dt_launch_points_occl(const void* dev_launch, uint32_t see
                                             float ao_radius, int n_lights, const void* lights, float* ao, float* light,
                                             int grid, hipStream_t stream);
 extern "C" const void* dt_points_occl_kernel_ptr(void);
+extern "C" hipError_t dt_launch_camera_rays(const void* dev_launch, int sample_begin, int ns, int64_t n_rows,
+                                            double* start, double* dir, hipStream_t stream);
 
 namespace {
 
@@ -1563,6 +1565,24 @@ struct AuxLaunch {
     return DT_OK;
   }
 
+  // The same without a scene (dt_camera_rays: a kernel that reads the record's parameters only): the record
+  // of P with a zeroed scene, and counters nobody adds to, so that finish() stays as it is.
+  int begin_sceneless(const dtd::DParams& P)
+  {
+    h.assign(ST_N + 1, 0);
+    void* d = nullptr;
+    if (int rc = alloc(dt_launch_size(), &launch)) return rc;
+    if (int rc = alloc(h.size() * sizeof(h[0]), &d)) return rc;
+    counters = (unsigned long long*)d;
+    HIPCHK(hipMemsetAsync(counters, 0, h.size() * sizeof(h[0]), st));
+    record.assign(dt_launch_size(), 0);
+    memcpy(record.data() + dt_params_struct_offset(), &P, sizeof(P));
+    HIPCHK(hipMemcpyAsync(launch, record.data(), record.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    return DT_OK;
+  }
+
   // The device side of one of the caller's arrays: p itself when it is null or on the device, else a
   // temporary of `bytes`, holding p's bytes first (copy_in) and copied back to p by finish() (copy_out).
   int plane(const void* p, size_t bytes, bool on_device, bool copy_in, bool copy_out, void** dev)
@@ -1670,6 +1690,55 @@ int dt_intersect_primary(const dt_scene* sc_c, const dt_globals* g, int32_t fram
   const int grid = aux_grid(dt_isect_kernel_ptr(), resident, (n_rays + 63) / 64);
   if (int rc = aux.start()) return rc;
   if (int rc = aux.finish(dt_launch_isect(aux.launch, first_ray, n_rays, (int32_t*)dshape, (float*)dt_, grid, aux.st)))
+    return rc;
+  if (kernel_ms) *kernel_ms = aux.kernel_ms;
+  return DT_OK;
+}
+
+// Camera rays as arrays: dt_camera_rays_kernel over the rows of (g, tiles, the sample range). The camera is
+// fill_params' (the renders'), no scene is involved: the launch record holds the parameters alone.
+static int camera_rays_check(const char* who, const dt_globals* g, const dt_tiles* tiles, int32_t sample_begin,
+                             int32_t sample_end, int32_t frame, dtd::DParams& P, int64_t& n_rows)
+{
+  const std::string w = std::string(who) + ": ";
+  if (!g) return fail(DT_E_INVALID, w + "null globals");
+  if (!(0 <= sample_begin && sample_begin < sample_end && sample_end - sample_begin <= DT_CAMERA_RAYS_MAX_SAMPLES))
+    return fail(DT_E_INVALID, w + "samples [" + std::to_string(sample_begin) + "," + std::to_string(sample_end) +
+                                  "): need 0 <= sample_begin < sample_end, at most " +
+                                  std::to_string(DT_CAMERA_RAYS_MAX_SAMPLES) + " samples");
+  std::string err;
+  if (int rc = fill_params(*g, frame, tiles, P, err)) return fail(rc, w + "globals or tiles: " + err);
+  const int64_t slots = P.layout == DT_OUT_SLAB ? P.n_owned_tiles * P.tw * P.th : (int64_t)P.xRes * P.yRes;
+  n_rows = slots * (sample_end - sample_begin);
+  return DT_OK;
+}
+
+int64_t dt_camera_rays_rows(const dt_globals* g, const dt_tiles* tiles, int32_t sample_begin, int32_t sample_end)
+{
+  dtd::DParams P;
+  int64_t n_rows = 0;
+  if (camera_rays_check("dt_camera_rays_rows", g, tiles, sample_begin, sample_end, 0, P, n_rows)) return -1;
+  return n_rows;
+}
+
+int dt_camera_rays(const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t sample_begin, int32_t sample_end,
+                   double* start, double* dir, int32_t on_device, void* stream, float* kernel_ms)
+{
+  if (g && !start) return fail(DT_E_INVALID, "dt_camera_rays: null start");
+  if (g && !dir) return fail(DT_E_INVALID, "dt_camera_rays: null dir");
+  dtd::DParams P;
+  int64_t n_rows = 0;
+  if (int rc = camera_rays_check("dt_camera_rays", g, tiles, sample_begin, sample_end, frame, P, n_rows)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin_sceneless(P)) return rc;
+  // host arrays are staged through device copies of the caller's arrays: unowned rows go back as they came
+  void *dstart = nullptr, *ddir = nullptr;
+  const size_t bytes = (size_t)n_rows * 3 * sizeof(double);
+  if (int rc = aux.plane(start, bytes, on_device, true, true, &dstart)) return rc;
+  if (int rc = aux.plane(dir, bytes, on_device, true, true, &ddir)) return rc;
+  if (int rc = aux.start()) return rc;
+  if (int rc = aux.finish(dt_launch_camera_rays(aux.launch, sample_begin, sample_end - sample_begin, n_rows,
+                                                (double*)dstart, (double*)ddir, aux.st)))
     return rc;
   if (kernel_ms) *kernel_ms = aux.kernel_ms;
   return DT_OK;

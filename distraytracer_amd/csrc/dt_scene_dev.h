@@ -264,4 +264,32 @@ DT_HD int64_t tile_of(int64_t slot, int rank, int world)
   return slot * world + (int64_t)(((uint32_t)rank + tile_rot(slot, world)) % (uint32_t)world);
 }
 
+// The pixel of output slot q (the slot whose colour dt_render stores at floats 3q .. 3q+2) and whether the
+// tile share owns it, for both layouts: a slab slot is pixel_of's (dt_kernels.hip: tile slot, then row-major
+// inside the tile), an image slot is ppmOut's (yRes-1-y)*xRes + x, owned iff its tile is one of the rank's.
+// For the per-row arrays of dt_camera_rays and dt_rays_resolve, which run over slots in ascending order so
+// that a wave's rows are contiguous. T: DParams, or any record with its tile fields.
+template <class T> DT_HD bool slot_pixel(const T& P, int64_t q, int& x, int& y)
+{
+  int64_t t, slot;
+  if (P.layout != 0) {   // DT_OUT_SLAB
+    const int64_t tile_px = (int64_t)P.tw * P.th;
+    slot = q / tile_px;
+    const int local = (int)(q - slot * tile_px);
+    const int py = local / P.tw, px = local - py * P.tw;
+    t = tile_of(slot, P.rank, P.world);
+    const int ty = (int)(t / P.tiles_x), tx = (int)(t - (int64_t)ty * P.tiles_x);
+    x = P.x0 + tx * P.tw + px;
+    y = P.y0 + ty * P.th + py;
+    return slot < P.n_owned_tiles && t < P.n_tiles && x < P.x1 && y < P.y1;
+  }
+  const int row = (int)(q / P.xRes);
+  x = (int)(q - (int64_t)row * P.xRes);
+  y = P.yRes - 1 - row;
+  if (x < P.x0 || x >= P.x1 || y < P.y0 || y >= P.y1) return false;
+  t = (int64_t)((y - P.y0) / P.th) * P.tiles_x + (x - P.x0) / P.tw;
+  slot = t / P.world;
+  return tile_of(slot, P.rank, P.world) == t;
+}
+
 }  // namespace dtd

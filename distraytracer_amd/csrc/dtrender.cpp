@@ -55,6 +55,12 @@
 //                     samples per texel (default 16) of --ao-rays / --ao-radius / --occlusion-lights probes,
 //                     written as --bake-out P: P.ao.png and P.light<j>.png, W x H, row v, grey value*255 as
 //                     --occlusion. Without the flag every byte written is the same as before.
+//   --peel K          after the frame, depth peeling of the frame's own view (K = 1..8 layers; --peel-out P is
+//                     needed; --peel-samples N rays per pixel, 1..1024, default 1): dt_camera_rays, then
+//                     dt_trace_rays_multi(K), then one dt_rays_resolve per rank, written as P.layer<j>.png: layer
+//                     j's coverage-premultiplied albedo times 255 (the mean over the pixel's rays of the
+//                     (j+1)-th surface's albedo, a ray with fewer surfaces adding nothing), as
+//                     distraytracer_amd.peel_layers. Without the flag every byte written is the same as before.
 //   --guide-bounces K the feature buffers of --features, --denoise, --denoise-variance and --upsample are the
 //                     specular-path ones (dt_render_features_path, K = 1..8 perfect specular bounces): the
 //                     guides describe what mirrors and glass show, not the reflector. Without it (or with 0)
@@ -257,6 +263,9 @@ int main(int argc, char** argv)
   int bake_shape = -1, bake_w = 0, bake_h = 0, bake_samples = 16;
   std::string bake_prefix;
   bool bake_asked = false;
+  int peel = 0, peel_samples = 1;
+  bool peel_asked = false;
+  std::string peel_prefix;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     if (a == "--out" && i + 1 < argc) out = argv[++i];
@@ -286,6 +295,9 @@ int main(int argc, char** argv)
     else if (a == "--bake-size" && i + 1 < argc) sscanf(argv[++i], "%dx%d", &bake_w, &bake_h);
     else if (a == "--bake-out" && i + 1 < argc) bake_prefix = argv[++i];
     else if (a == "--bake-samples" && i + 1 < argc) bake_samples = atoi(argv[++i]);
+    else if (a == "--peel" && i + 1 < argc) { peel = atoi(argv[++i]); peel_asked = true; }
+    else if (a == "--peel-out" && i + 1 < argc) peel_prefix = argv[++i];
+    else if (a == "--peel-samples" && i + 1 < argc) peel_samples = atoi(argv[++i]);
   }
   if (guide_bounces < 0 || guide_bounces > DT_GUIDE_MAX_BOUNCES) {
     fprintf(stderr, "usage: --guide-bounces K needs K in 0..%d\n", DT_GUIDE_MAX_BOUNCES);
@@ -293,6 +305,12 @@ int main(int argc, char** argv)
   }
   if (bake_asked && (bake_shape < 0 || bake_w < 1 || bake_h < 1 || bake_prefix.empty())) {
     fprintf(stderr, "usage: --bake-occlusion SHAPE (>= 0) needs --bake-size WxH and --bake-out PREFIX\n");
+    return 2;
+  }
+  if (peel_asked && (peel < 1 || peel > DT_MULTIHIT_MAX || peel_prefix.empty() || peel_samples < 1 ||
+                     peel_samples > DT_CAMERA_RAYS_MAX_SAMPLES)) {
+    fprintf(stderr, "usage: --peel K needs K in 1..%d, --peel-out PREFIX and --peel-samples in 1..%d\n", DT_MULTIHIT_MAX,
+            DT_CAMERA_RAYS_MAX_SAMPLES);
     return 2;
   }
   if (denoise_variance && adaptive < 0.0) {
@@ -626,6 +644,43 @@ int main(int argc, char** argv)
            "%.3f ms (kernel) -> %s.*.png\n",
            bake_shape, bake_w, bake_h, (unsigned long long)keep.size(), (unsigned long long)bst.shadow_rays, bake_samples,
            op.ao_rays, (double)op.ao_radius, nl, bst.kernel_ms, bake_prefix.c_str());
+  }
+  if (peel_asked) {
+    const int K = peel, n = peel_samples;
+    const int64_t rows = dt_camera_rays_rows(&g, nullptr, 0, n);
+    if (rows < 0) return die("dt_camera_rays_rows", (int)rows);
+    const size_t n_px = (size_t)g.xRes * g.yRes;
+    std::vector<double> start((size_t)rows * 3, 0.0), dir((size_t)rows * 3, 0.0), alb((size_t)rows * K * 3, 0.0);
+    std::vector<int32_t> shp((size_t)rows * K, -1);
+    float cam_ms = 0;
+    rc = dt_camera_rays(&g, frame, nullptr, 0, n, start.data(), dir.data(), 0, nullptr, &cam_ms);
+    if (rc) return die("dt_camera_rays", rc);
+    dt_ray_multihits mh;
+    memset(&mh, 0, sizeof mh);
+    mh.shape = shp.data(); mh.albedo = alb.data();
+    dt_stats pst;
+    rc = dt_trace_rays_multi(s, &g, rows, start.data(), dir.data(), K, &mh, 0, nullptr, &pst);
+    if (rc) return die("dt_trace_rays_multi", rc);
+    std::vector<double> aj((size_t)rows * 3);
+    std::vector<int32_t> sj((size_t)rows);
+    std::vector<float> plane(3 * n_px), pix(3 * n_px);
+    for (int j = 0; j < K; ++j) {
+      for (int64_t r = 0; r < rows; ++r) {
+        sj[(size_t)r] = shp[(size_t)(r * K + j)];
+        for (int k = 0; k < 3; ++k) aj[(size_t)(3 * r + k)] = alb[(size_t)(3 * (r * K + j) + k)];
+      }
+      rc = dt_rays_resolve(&g, nullptr, n, 3, aj.data(), sj.data(), DT_RESOLVE_MEAN, plane.data(), nullptr, 0, nullptr);
+      if (rc) return die("dt_rays_resolve", rc);
+      for (size_t e = 0; e < 3 * n_px; ++e) {
+        const float v = plane[e] * 255.0f;
+        pix[e] = v < 0.0f ? 0.0f : v > 255.0f ? 255.0f : v;   // (the PNG writer truncates to a byte)
+      }
+      const std::string pf = peel_prefix + ".layer" + std::to_string(j) + ".png";
+      rc = dt_write_png(pf.c_str(), g.xRes, g.yRes, pix.data());
+      if (rc) return die("dt_write_png (peel)", rc);
+    }
+    printf("peel: %lld rays (%d per pixel), %d layers: rays %.3f ms, hits %.3f ms (kernels) -> %s.layer<j>.png\n",
+           (long long)rows, n, K, cam_ms, pst.kernel_ms, peel_prefix.c_str());
   }
   double msps = st.samples / (st.kernel_ms * 1e-3) / 1e6;
   printf("Rendered %s frame %d: %dx%d, %d spp, depth %d in %.2f ms (kernel, %.1f Mpixel-samples/s) -> %s\n",

@@ -77,6 +77,8 @@ extern "C" {
  *    sort caller-supplied rays into coherent waves) */
 /* (still 8, one new export and one new struct, no struct changed: dt_trace_rays_multi and its
  *    dt_ray_multihits -- multi-hit ray queries: the k nearest surfaces along caller-supplied rays) */
+/* (still 8, new exports only, no struct changed: dt_camera_rays_rows, dt_camera_rays, dt_rays_resolve --
+ *    camera rays as arrays, and per-ray answers resolved back to pixels) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -754,6 +756,60 @@ typedef struct dt_ray_multihits {   /* each plane optional (NULL: not wanted), n
 int dt_trace_rays_multi(const dt_scene* s, const dt_globals* g, int64_t n_rays, const double* start,
                         const double* dir, int32_t k /* 1..DT_MULTIHIT_MAX */, const dt_ray_multihits* out,
                         int32_t on_device, void* stream, dt_stats* stats);
+
+/* ---- camera rays as arrays, and per-ray answers resolved back to pixels ----
+ * The ray queries answer rays the caller hands over; picking under a cursor, X-ray views, depth peeling and
+ * thickness start from the render's own camera rays. dt_camera_rays writes those rays out, dt_rays_resolve
+ * reduces per-ray answers of any query back to per-pixel planes with the project's fixed summation order, so
+ * a query becomes a plane that lines up with the colour image edge for edge. By the definitions here,
+ * dt_camera_rays(samples 0..n) -> dt_trace_rays(shape, albedo, normal) -> dt_rays_resolve reproduces
+ * dt_render_features' albedo, normal and coverage planes bit for bit.
+ *
+ * Slots and rows. q is a pixel's output slot: its colour sits at floats 3q .. 3q+2 of dt_render's output
+ * (DT_OUT_IMAGE and DT_OUT_SLAB alike; tiles == NULL: the whole image), so there are dt_accum_doubles / 3
+ * slots. With ns = sample_end - sample_begin samples per pixel, sample i of slot q is row
+ * q*ns + (i - sample_begin); the arrays hold dt_camera_rays_rows = (dt_accum_doubles / 3) * ns rows (-1 for
+ * globals, tiles or a sample range the calls refuse). Only the rows of pixels the tile share owns are
+ * written; the others are left as they came.
+ *
+ * dt_camera_rays: no scene is needed, the camera is the globals' alone (the CPU oracle's or_primary_ray is the
+ * counterpart). Row (q, i) is the ray dt_render starts sample i of that pixel from, bit for bit: RNG pixel
+ * y*xRes + x, sample i, key (seed, frame), one draw of the depth-of-field purpose iff aperture > 0; start is
+ * the eye sample (3 doubles), dir the unnormalised ray through the pixel's focal point (3 doubles). In
+ * dt_intersect_primary's numbering it is ray ((i/8)*W*H + y*W + x)*8 + i%8. The range is free of spp and of
+ * the 64-sample chunks: 0 <= sample_begin < sample_end, at most DT_CAMERA_RAYS_MAX_SAMPLES samples.
+ * Limits: only the render's thin-lens perspective camera (no orthographic, panoramic or fisheye model); the
+ * motion-blur re-trace of frames >= frame_prism is not reproduced (as for the feature buffers).
+ * Both arrays on one side: the device (on_device=1: one kernel on `stream`, one ray per lane, a wave's 64
+ * rows 1536 contiguous bytes per array) or the host (0: staged through device copies of the caller's arrays,
+ * so unowned rows go back as they came). The call waits for its work; kernel_ms (optional): the kernel's
+ * HIP-event time. DT_E_INVALID before any device work, with a dt_last_error starting "dt_camera_rays: " and
+ * naming the argument: null globals, start or dir, a bad sample range, globals or tiles the renders refuse. */
+#define DT_CAMERA_RAYS_MAX_SAMPLES 1024
+int64_t dt_camera_rays_rows(const dt_globals* g, const dt_tiles* tiles, int32_t sample_begin, int32_t sample_end);
+int dt_camera_rays(const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t sample_begin,
+                   int32_t sample_end, double* start, double* dir, int32_t on_device, void* stream,
+                   float* kernel_ms);
+
+/* dt_rays_resolve: values holds `width` (1..3) doubles per row, rows as above with ns = n_samples
+ * (1..DT_CAMERA_RAYS_MAX_SAMPLES); shape (optional) one int32 per row: a row with shape < 0 adds nothing
+ * (a miss of dt_trace_rays). Per owned pixel q and component k, every operation one rounded IEEE f64
+ * operation (csrc/dt_rays_resolve.h is the one definition for the host loop and the kernel;
+ * tests/camera_rays_ref.py restates it in numpy):
+ *   S = 0.0 ; H = 0 ; for i = 0 .. n_samples-1 in this order: if the row counts { S = S + values[..k] ; H += 1 }
+ *   DT_RESOLVE_MEAN:      out[width*q + k] = (float)(S / (double)n_samples)
+ *   DT_RESOLVE_HIT_MEAN:  out[width*q + k] = H > 0 ? (float)(S / (double)H) : 0.0f
+ *   coverage[q] (optional) = (float)((double)H / (double)n_samples)
+ * which is how dt_render_features forms albedo and normal (MEAN), depth (HIT_MEAN) and coverage. Without
+ * shape every row counts. Only owned pixels are written. f64 rows only.
+ * All arrays on one side: host (on_device=0: a plain loop) or device (1: one kernel on `stream`, enqueue
+ * only). DT_E_INVALID before any device work, with a dt_last_error starting "dt_rays_resolve: " and naming
+ * the argument: null globals, values or out, n_samples, width or mode out of range, bad globals or tiles. */
+#define DT_RESOLVE_MEAN     0
+#define DT_RESOLVE_HIT_MEAN 1
+int dt_rays_resolve(const dt_globals* g, const dt_tiles* tiles, int32_t n_samples, int32_t width /* 1..3 */,
+                    const double* values, const int32_t* shape /* optional */, int32_t mode, float* out,
+                    float* coverage /* optional */, int32_t on_device, void* stream);
 
 /* ---- ray ordering: sort caller-supplied rays into coherent waves ----
  * No reference counterpart. The ray queries serve 64 consecutive array entries with one wave, and a wave walks
