@@ -29,6 +29,7 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "Camera", "camera", "TemporalParams", "temporal_params_default", "reproject", "TemporalAccumulator",
            "trace_rays", "rays_occluded", "RAY_PLANES",
            "trace_rays_multi", "segment_through_glass", "RAY_MULTI_PLANES",
+           "rays_transmittance", "RAY_TRANSMIT_PLANES",
            "camera_rays", "camera_rays_rows", "rays_resolve", "peel_layers", "RESOLVE_MODES",
            "RayOrderParams", "RayOrder", "ray_order_params_default", "ray_order_key", "ray_order", "DT_RAY_ORDER_TILE",
            "render_mattes", "matte_mask", "shape_groups", "MATTE_PLANES",
@@ -378,7 +379,7 @@ def render_occlusion(scene, g, frame, n_samples=None, ao_rays=4, ao_radius=None,
 
 
 def points_occlusion(scene, g, points, normals, frame=0, n_samples=16, ao_rays=4, ao_radius=None, lights=(),
-                     stream=None):
+                     stream=None, through_glass=None):
     """Occlusion at surface points the caller supplies (include/dt.h dt_points_occlusion), for baking: points and
     normals are float64, shaped (n, 3) or flat, numpy arrays or torch tensors, both on one side; a normal is
     used as given (unit length and pointing away from the surface is the caller's business). Point i takes
@@ -386,7 +387,12 @@ def points_occlusion(scene, g, points, normals, frame=0, n_samples=16, ao_rays=4
     None: occlusion_params_default's constant) and one probe per light of `lights`. Returns (dict(ao=...,
     light=...), stats) on the side of points: `ao` float32 (n,), only with ao_rays > 0; `light` float32
     (n, len(lights)), only with lights. A point with a non-finite component gets zeros. 64 consecutive points
-    share a wave: keep neighbours in the arrays neighbours in space."""
+    share a wave: keep neighbours in the arrays neighbours in space.
+    through_glass: None, a glass shape shadows like a wall (dt_points_occlusion); an integer 0..8, the probes pass
+    through glass (dt_points_occlusion_glass): a probe is unoccluded iff no other shape stops it and it crosses at
+    most that many glass shapes, and the dict gains `ao_panes` and `light_panes`, shaped like ao and light: the
+    panes the unoccluded probes crossed, summed and divided by the denominators of ao and light. 0 gives
+    today's ao and light."""
     from ._lib import Occlusion
     n, pp, np_, side = _ray_arrays("points_occlusion", points, normals)
     p = OcclusionParams()
@@ -406,6 +412,22 @@ def points_occlusion(scene, g, points, normals, frame=0, n_samples=16, ao_rays=4
         out["light"] = _ray_new(points, (n, len(lights)), "torch.float32", "float32")
         o.light = _ptr(out["light"])[0].value or none.value
     st = Stats()
+    if through_glass is not None:
+        from ._lib import OcclusionPanes
+        if isinstance(through_glass, bool) or not isinstance(through_glass, int):
+            raise DTError("points_occlusion: through_glass must be None or an integer, not %r" % (through_glass,))
+        op = OcclusionPanes()
+        if p.ao_rays > 0:
+            out["ao_panes"] = _ray_new(points, (n,), "torch.float32", "float32")
+            op.ao_panes = _ptr(out["ao_panes"])[0].value or none.value
+        if lights:
+            out["light_panes"] = _ray_new(points, (n, len(lights)), "torch.float32", "float32")
+            op.light_panes = _ptr(out["light_panes"])[0].value or none.value
+        check(lib.dt_points_occlusion_glass(scene.handle, ctypes.byref(g), int(frame), n, pp, np_, int(n_samples),
+                                            ctypes.byref(p), through_glass, ctypes.byref(o), ctypes.byref(op), side,
+                                            ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)),
+              "dt_points_occlusion_glass")
+        return out, st
     check(lib.dt_points_occlusion(scene.handle, ctypes.byref(g), int(frame), n, pp, np_, int(n_samples), ctypes.byref(p),
                                   ctypes.byref(o), side, ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)),
           "dt_points_occlusion")
@@ -454,13 +476,14 @@ def shape_texels(desc, shape_index, width, height, side=1):
     return _shape_texels(desc, shape_index, width, height, side)[:2]
 
 
-def bake_occlusion(scene, desc, g, shape_index, width, height, side=1, **kw):
+def bake_occlusion(scene, desc, g, shape_index, width, height, side=1, through_glass=None, **kw):
     """A lightmap of one shape: points_occlusion(scene, g, *shape_texels(desc, shape_index, width, height, side),
     **kw) as numpy images, (dict(ao=(height, width), light=(height, width, n_lights)), stats), row v, column u.
-    A triangle's texels outside it are 0."""
+    A triangle's texels outside it are 0. through_glass as for points_occlusion: an integer adds the images
+    ao_panes and light_panes, shaped like ao and light."""
     import numpy as np
     points, normals, keep = _shape_texels(desc, shape_index, width, height, side)
-    planes, st = points_occlusion(scene, g, points, normals, **kw)
+    planes, st = points_occlusion(scene, g, points, normals, through_glass=through_glass, **kw)
     out = {}
     for name, a in planes.items():
         img = np.zeros((int(height) * int(width),) + a.shape[1:], np.float32)
@@ -482,6 +505,14 @@ def occlusion_images(g, planes):
         v = np.asarray(planes["light"], np.float32).reshape(n1, -1)
         for j in range(v.shape[1]):
             out["light%d" % j] = np.repeat(np.ascontiguousarray(v[:, j]) * np.float32(255), 3)
+    # the pane planes of through_glass (`dtrender --bake-through-glass`): 8 panes (DT_TRANSMIT_MAX_PANES) are white
+    if "ao_panes" in planes:
+        a = np.asarray(planes["ao_panes"], np.float32).reshape(n1)
+        out["ao_panes"] = np.repeat((a / np.float32(8)) * np.float32(255), 3)
+    if "light_panes" in planes:
+        v = np.asarray(planes["light_panes"], np.float32).reshape(n1, -1)
+        for j in range(v.shape[1]):
+            out["light_panes%d" % j] = np.repeat((np.ascontiguousarray(v[:, j]) / np.float32(8)) * np.float32(255), 3)
     return out
 
 
@@ -866,6 +897,55 @@ def trace_rays_multi(scene, g, start, dir, k=4, planes=("count", "shape", "t"), 
     return out, st
 
 
+RAY_TRANSMIT_PLANES = ("panes", "pane_shape")
+
+
+def rays_transmittance(scene, g, start, dir, skip_shape=None, k=0, order=None, planes=RAY_TRANSMIT_PLANES,
+                       stream=None):
+    """rays_occluded with probes that pass through glass (include/dt.h dt_rays_transmittance): start, dir and
+    skip_shape as for rays_occluded, k in 0..8. Returns (dict(panes=..., pane_shape=...), stats) on the side of
+    start: `panes` int32 (n,), -1 where a shape that is not glass stops the probe, else the number of glass
+    shapes it crosses (0: clear), so that (panes != 0) is rays_occluded's answer; `pane_shape` int32 (n, k), the
+    k smallest indices of those glass shapes, ascending, -1 beyond (and all -1 for a blocked ray). With k = 0
+    pane_shape is an empty (n, 0) array and no list is kept on the device. planes: which of the two to compute.
+    `order` as for rays_occluded: the same bits."""
+    what = "rays_transmittance"
+    n, sp, dp, side = _ray_arrays(what, start, dir)
+    from ._lib import DT_TRANSMIT_MAX_PANES, RayTransmittance
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= DT_TRANSMIT_MAX_PANES:
+        raise DTError("%s: k must be an integer in 0..%d, not %r" % (what, DT_TRANSMIT_MAX_PANES, k))
+    for name in planes:
+        if name not in RAY_TRANSMIT_PLANES:
+            raise DTError("%s: unknown plane %r" % (what, name))
+    kp = None
+    if skip_shape is not None:
+        kp = _ray_out(what, "skip_shape", skip_shape, n, 1, "torch.int32", "int32", side)
+    out = {}
+    if "panes" in planes:
+        out["panes"] = _ray_new(start, (n,), "torch.int32", "int32")
+    if "pane_shape" in planes:
+        out["pane_shape"] = _ray_new(start, (n, k), "torch.int32", "int32")
+    if order is not None:
+        order = _order_for(what, order, start, dir, n, side, stream)
+        tmp, st = rays_transmittance(scene, g, order.apply(start), order.apply(dir),
+                                     skip_shape=order.apply(skip_shape) if skip_shape is not None else None, k=k,
+                                     planes=planes, stream=stream)
+        for name, a in out.items():
+            if _numel_any(a):
+                order.restore(tmp[name], out=a)
+        return out, st
+    h = RayTransmittance()
+    if "panes" in out:
+        h.panes = _data_ptr(out["panes"])
+    if "pane_shape" in out and k > 0:
+        h.pane_shape = _data_ptr(out["pane_shape"])
+    st = Stats()
+    check(lib.dt_rays_transmittance(scene.handle, ctypes.byref(g), n, sp, dp, kp, k, ctypes.byref(h), side,
+                                    ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)),
+          "dt_rays_transmittance")
+    return out, st
+
+
 def segment_through_glass(scene, desc, g, start, dir, k=8):
     """Is the segment start .. start + dir clear but for glass? Over trace_rays_multi(k): per ray `clear` (every
     recorded hit with t < 1 is on a DT_MAT_GLASS shape of desc), `panes` (how many such hits on glass) and
@@ -875,7 +955,11 @@ def segment_through_glass(scene, desc, g, start, dir, k=8):
     For callers that want light or line of sight through the panes of a scene, which rays_occluded cannot give
     (a pane shadows like a wall there). It is not the light loop's test, and differs from rays_occluded: no
     1e-3 offset of the start, the shapes' intersect and not intersectShadow, no skip_shape, and every shape
-    counts once (its first intersection; the far side of a glass sphere is not a second pane)."""
+    counts once (its first intersection; the far side of a glass sphere is not a second pane).
+    rays_transmittance is the light loop's test with the glass filter, on the device: intersectShadow from the
+    1e-3 offset up to t_max, skip_shape, never truncated (panes is a full count, blocked is exact), and usable
+    inside points_occlusion(through_glass=...). This function stays for callers that want the closest-hit
+    distances' view of the segment (t < 1 along the unnormalised dir)."""
     import numpy as np
     hits, st = trace_rays_multi(scene, g, start, dir, k=k, planes=("count", "shape", "t"))
     shape, t, count = hits["shape"], hits["t"], hits["count"]

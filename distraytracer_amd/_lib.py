@@ -142,6 +142,19 @@ class Occlusion(ctypes.Structure):
     _fields_ = [("ao", ctypes.c_void_p), ("light", ctypes.c_void_p)]
 
 
+DT_TRANSMIT_MAX_PANES = 8   # the largest k of dt_rays_transmittance, the largest max_panes of dt_points_occlusion_glass
+
+
+class RayTransmittance(ctypes.Structure):
+    """dt_ray_transmittance: the planes of dt_rays_transmittance (a null pointer: not wanted)"""
+    _fields_ = [("panes", ctypes.c_void_p), ("pane_shape", ctypes.c_void_p)]
+
+
+class OcclusionPanes(ctypes.Structure):
+    """dt_occlusion_panes: the pane planes of dt_points_occlusion_glass (a null pointer: not wanted)"""
+    _fields_ = [("ao_panes", ctypes.c_void_p), ("light_panes", ctypes.c_void_p)]
+
+
 DT_OCCL_MAX_AO_RAYS = 16
 DT_OCCL_MAX_LIGHTS = 8
 DT_OCCL_TRIES = 16
@@ -231,7 +244,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_ray_order_params_default", "dt_ray_order_key", "dt_ray_order_workspace_bytes", "dt_ray_order",
            "dt_permute_rows",
            "dt_trace_rays_multi",
-           "dt_camera_rays_rows", "dt_camera_rays", "dt_rays_resolve"]
+           "dt_camera_rays_rows", "dt_camera_rays", "dt_rays_resolve",
+           "dt_rays_transmittance", "dt_points_occlusion_glass"]
 
 
 class DTError(RuntimeError):
@@ -333,6 +347,12 @@ def _load():
                                        ctypes.c_void_p, ctypes.c_void_p, c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_trace_rays_multi": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p, c_int32,
                                           P(RayMultiHits), c_int32, ctypes.c_void_p, P(Stats)]),
+        "dt_rays_transmittance": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, c_int32, P(RayTransmittance), c_int32, ctypes.c_void_p,
+                                            P(Stats)]),
+        "dt_points_occlusion_glass": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, c_int64, ctypes.c_void_p,
+                                                ctypes.c_void_p, c_int32, P(OcclusionParams), c_int32, P(Occlusion),
+                                                P(OcclusionPanes), c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_camera_rays_rows": (c_int64, [P(Globals), P(Tiles), c_int32, c_int32]),
         "dt_camera_rays": (c_int32, [P(Globals), c_int32, P(Tiles), c_int32, c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                      c_int32, ctypes.c_void_p, P(c_float)]),

@@ -92,6 +92,16 @@ extern "C" hipError_t dt_launch_points_occl(const void* dev_launch, uint32_t see
                                             float ao_radius, int n_lights, const void* lights, float* ao, float* light,
                                             int grid, hipStream_t stream);
 extern "C" const void* dt_points_occl_kernel_ptr(void);
+extern "C" hipError_t dt_launch_rayq_transmit(const void* dev_launch, int64_t n, const double* start, const double* dir,
+                                              const int32_t* skip_shape, int k, int32_t* panes, int32_t* pane_shape,
+                                              int grid, hipStream_t stream);
+extern "C" const void* dt_rayq_transmit_kernel_ptr(int k);
+extern "C" hipError_t dt_launch_points_occl_glass(const void* dev_launch, uint32_t seed, int32_t frame, int64_t n,
+                                                  const double* point, const double* normal, int n_samples,
+                                                  int ao_rays, float ao_radius, int n_lights, const void* lights,
+                                                  int max_panes, float* ao, float* light, float* ao_panes,
+                                                  float* light_panes, int grid, hipStream_t stream);
+extern "C" const void* dt_points_occl_glass_kernel_ptr(void);
 extern "C" hipError_t dt_launch_camera_rays(const void* dev_launch, int sample_begin, int ns, int64_t n_rows,
                                             double* start, double* dir, hipStream_t stream);
 
@@ -2030,6 +2040,55 @@ int dt_rays_occluded(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, 
   return DT_OK;
 }
 
+// dt_rays_transmittance: dt_rayq_transmit_kernel in the smallest list capacity (0, 1, 2, 4, 8) that holds the
+// pane ids wanted (0 without out->pane_shape); the resident waves are cached per capacity, as each is a kernel
+// of its own
+int dt_rays_transmittance(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, const double* start,
+                          const double* dir, const int32_t* skip_shape, int32_t k, const dt_ray_transmittance* out,
+                          int32_t on_device, void* stream, dt_stats* stats)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  const std::string who = "dt_rays_transmittance: ";
+  if (!sc) return fail(DT_E_INVALID, who + "null scene");
+  if (!g) return fail(DT_E_INVALID, who + "null globals");
+  if (!start) return fail(DT_E_INVALID, who + "null start");
+  if (!dir) return fail(DT_E_INVALID, who + "null dir");
+  if (!out) return fail(DT_E_INVALID, who + "null out");
+  if (!out->panes && !out->pane_shape) return fail(DT_E_INVALID, who + "out wants no plane (every pointer is null)");
+  if (n_rays < 0) return fail(DT_E_INVALID, who + "n_rays < 0");
+  if (k < 0 || k > DT_TRANSMIT_MAX_PANES)
+    return fail(DT_E_INVALID, who + "k = " + std::to_string(k) + " outside 0.." + std::to_string(DT_TRANSMIT_MAX_PANES));
+  if (out->pane_shape && k == 0) return fail(DT_E_INVALID, who + "out->pane_shape given with k == 0");
+  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, who + "scenes with a RectPrismWithCylinder");
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (n_rays == 0) return DT_OK;
+  dtd::DParams P;
+  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, false)) return rc;
+  const size_t n = (size_t)n_rays;
+  void *dstart = nullptr, *ddir = nullptr, *dskip = nullptr, *dpanes = nullptr, *dshape = nullptr;
+  if (int rc = aux.plane(start, 3 * n * sizeof(double), on_device, true, false, &dstart)) return rc;
+  if (int rc = aux.plane(dir, 3 * n * sizeof(double), on_device, true, false, &ddir)) return rc;
+  if (int rc = aux.plane(skip_shape, n * sizeof(int32_t), on_device, true, false, &dskip)) return rc;
+  if (int rc = aux.plane(out->panes, n * sizeof(int32_t), on_device, false, true, &dpanes)) return rc;
+  if (int rc = aux.plane(out->pane_shape, n * (size_t)k * sizeof(int32_t), on_device, false, true, &dshape)) return rc;
+  static int resident[5] = {0, 0, 0, 0, 0};   // per capacity 0, 1, 2, 4, 8
+  const int cap_k = out->pane_shape ? k : 0;
+  const int slot = cap_k <= 0 ? 0 : cap_k <= 1 ? 1 : cap_k <= 2 ? 2 : cap_k <= 4 ? 3 : 4;
+  const int grid = aux_grid(dt_rayq_transmit_kernel_ptr(cap_k), resident[slot], (n_rays + 63) / 64);
+  if (int rc = aux.start()) return rc;
+  if (int rc = aux.finish(dt_launch_rayq_transmit(aux.launch, n_rays, (const double*)dstart, (const double*)ddir,
+                                                  (const int32_t*)dskip, k, (int32_t*)dpanes, (int32_t*)dshape, grid,
+                                                  aux.st)))
+    return rc;
+  if (stats) {
+    stats->shadow_rays = aux.h[ST_SHADOW];
+    stats->kernel_ms = aux.kernel_ms;
+  }
+  return DT_OK;
+}
+
 // Occlusion feature buffers: dt_occlusion_kernel over the samples 0 .. n_samples-1 of every owned pixel. As
 // dt_render_features it shares only the scene's primary-ray lists. Every argument check, the light indices
 // included, comes before any device work. The lights' records (dt_occl.h OcclLight, from the scene's flattened
@@ -2136,12 +2195,16 @@ int dt_render_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame
 // ray query it takes only the traversal parameters from g (prepare_whole at frame 0, as dt_rays_occluded, so
 // that a probe is answered as that call answers it); the RNG key (g->seed, frame) travels as kernel
 // arguments. It neither reads nor rebuilds the primary-ray lists.
-int dt_points_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame, int64_t n_points, const double* point,
-                        const double* normal, int32_t n_samples, const dt_occlusion_params* params,
-                        const dt_occlusion* out, int32_t on_device, void* stream, dt_stats* stats)
+//
+// dt_points_occlusion_glass is the same call with dt_points_occl_glass_kernel (glass: max_panes and the optional
+// pane planes; a row of probes runs for either of its two planes).
+static int points_occlusion_common(bool glass, const dt_scene* sc_c, const dt_globals* g, int32_t frame, int64_t n_points,
+                                   const double* point, const double* normal, int32_t n_samples,
+                                   const dt_occlusion_params* params, int32_t max_panes, const dt_occlusion* out,
+                                   const dt_occlusion_panes* panes, int32_t on_device, void* stream, dt_stats* stats)
 {
   dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  const std::string who = "dt_points_occlusion: ";
+  const std::string who = glass ? "dt_points_occlusion_glass: " : "dt_points_occlusion: ";
   if (!sc) return fail(DT_E_INVALID, who + "null scene");
   if (!g) return fail(DT_E_INVALID, who + "null globals");
   if (!point) return fail(DT_E_INVALID, who + "null point");
@@ -2153,11 +2216,23 @@ int dt_points_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame
   if (n_samples < 1 || n_samples > DT_POCCL_MAX_SAMPLES)
     return fail(DT_E_INVALID, who + "n_samples " + std::to_string(n_samples) + " outside 1.." +
                                   std::to_string(DT_POCCL_MAX_SAMPLES));
+  if (glass) {
+    if (max_panes < 0 || max_panes > DT_TRANSMIT_MAX_PANES)
+      return fail(DT_E_INVALID, who + "max_panes " + std::to_string(max_panes) + " outside 0.." +
+                                    std::to_string(DT_TRANSMIT_MAX_PANES));
+    if (panes && panes->ao_panes && params->ao_rays == 0)
+      return fail(DT_E_INVALID, who + "panes->ao_panes given with ao_rays == 0");
+    if (panes && panes->light_panes && params->n_lights == 0)
+      return fail(DT_E_INVALID, who + "panes->light_panes given with n_lights == 0");
+  }
   if (int rc = check_occlusion(who, sc, params, out)) return rc;
   if (stats) memset(stats, 0, sizeof(*stats));
   if (n_points == 0) return DT_OK;
   // a plane that is not wanted costs no probes
-  const int ao_rays = out->ao ? params->ao_rays : 0, n_lights = out->light ? params->n_lights : 0;
+  float* const ao_panes = glass && panes ? panes->ao_panes : nullptr;
+  float* const light_panes = glass && panes ? panes->light_panes : nullptr;
+  const int ao_rays = (out->ao || ao_panes) ? params->ao_rays : 0;
+  const int n_lights = (out->light || light_panes) ? params->n_lights : 0;
   dtd::DParams P;
   if (int rc = prepare_whole(sc, g, 0, P)) return rc;
   AuxLaunch aux(stream);
@@ -2174,18 +2249,50 @@ int dt_points_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame
   if (int rc = aux.plane(out->ao, n * sizeof(float), on_device, false, true, &dao)) return rc;
   if (int rc = aux.plane(out->light, n * (size_t)params->n_lights * sizeof(float), on_device, false, true, &dlight))
     return rc;
-  static int resident = 0;
-  const int grid = aux_grid(dt_points_occl_kernel_ptr(), resident, (n_points + 63) / 64);
-  if (int rc = aux.start()) return rc;
-  if (int rc = aux.finish(dt_launch_points_occl(aux.launch, (uint32_t)g->seed, frame, n_points, (const double*)dpoint,
-                                                (const double*)dnormal, n_samples, ao_rays, params->ao_radius, n_lights,
-                                                dlights, (float*)dao, (float*)dlight, grid, aux.st)))
-    return rc;
+  if (glass) {
+    void *daop = nullptr, *dlp = nullptr;
+    if (int rc = aux.plane(ao_panes, n * sizeof(float), on_device, false, true, &daop)) return rc;
+    if (int rc = aux.plane(light_panes, n * (size_t)params->n_lights * sizeof(float), on_device, false, true, &dlp))
+      return rc;
+    static int resident_glass = 0;
+    const int grid = aux_grid(dt_points_occl_glass_kernel_ptr(), resident_glass, (n_points + 63) / 64);
+    if (int rc = aux.start()) return rc;
+    if (int rc = aux.finish(dt_launch_points_occl_glass(aux.launch, (uint32_t)g->seed, frame, n_points,
+                                                        (const double*)dpoint, (const double*)dnormal, n_samples, ao_rays,
+                                                        params->ao_radius, n_lights, dlights, max_panes, (float*)dao,
+                                                        (float*)dlight, (float*)daop, (float*)dlp, grid, aux.st)))
+      return rc;
+  } else {
+    static int resident = 0;
+    const int grid = aux_grid(dt_points_occl_kernel_ptr(), resident, (n_points + 63) / 64);
+    if (int rc = aux.start()) return rc;
+    if (int rc = aux.finish(dt_launch_points_occl(aux.launch, (uint32_t)g->seed, frame, n_points, (const double*)dpoint,
+                                                  (const double*)dnormal, n_samples, ao_rays, params->ao_radius, n_lights,
+                                                  dlights, (float*)dao, (float*)dlight, grid, aux.st)))
+      return rc;
+  }
   if (stats) {
     stats->shadow_rays = aux.h[ST_SHADOW];
     stats->kernel_ms = aux.kernel_ms;
   }
   return DT_OK;
+}
+
+int dt_points_occlusion(const dt_scene* s, const dt_globals* g, int32_t frame, int64_t n_points, const double* point,
+                        const double* normal, int32_t n_samples, const dt_occlusion_params* params,
+                        const dt_occlusion* out, int32_t on_device, void* stream, dt_stats* stats)
+{
+  return points_occlusion_common(false, s, g, frame, n_points, point, normal, n_samples, params, 0, out, nullptr,
+                                 on_device, stream, stats);
+}
+
+int dt_points_occlusion_glass(const dt_scene* s, const dt_globals* g, int32_t frame, int64_t n_points, const double* point,
+                              const double* normal, int32_t n_samples, const dt_occlusion_params* params,
+                              int32_t max_panes, const dt_occlusion* out, const dt_occlusion_panes* panes,
+                              int32_t on_device, void* stream, dt_stats* stats)
+{
+  return points_occlusion_common(true, s, g, frame, n_points, point, normal, n_samples, params, max_panes, out, panes,
+                                 on_device, stream, stats);
 }
 
 // The two probe generators of dt_render_occlusion for one hit (dt_occl.h), for tests and callers.

@@ -127,6 +127,20 @@ using namespace dtd;
 #ifndef DT_CAMRAYS
 #define DT_CAMRAYS 0
 #endif
+// DT_TRANSMIT=1 (a thirteenth compilation, build/dt_kernels_transmit.o): only dt_rayq_transmit_kernel, the
+// transmittance ray query of dt_rays_transmittance in its five list capacities, for the same reason
+#ifndef DT_TRANSMIT
+#define DT_TRANSMIT 0
+#endif
+// DT_POCCLG=1 (a fourteenth compilation, build/dt_kernels_pocclg.o): only dt_points_occl_glass_kernel, the
+// occlusion queries of dt_points_occlusion_glass, whose probes pass through glass; DT_POCCL's source with the
+// transmittance walk in the place of the any-hit walk, for the same reason
+#ifndef DT_POCCLG
+#define DT_POCCLG 0
+#endif
+#if DT_POCCLG
+#include "dt_occl.h"
+#endif
 // DT_W5=1 (build/dt_kernels_w5.o): the trace kernel at 5 waves per SIMD (96 VGPRs, under 8 KiB of
 // LDS per wave: DT_PSUM_LDS=2), launched for one-pixel-per-wave work (spp >= 64; never
 // with more than 8 pixels per wave, the slots DT_PSUM_LDS=2 keeps)
@@ -2118,6 +2132,127 @@ __device__ __forceinline__ bool occluded_walk(const DScene& S, const DParams& P,
   return inv(om);
 }
 
+#if DT_TRANSMIT || DT_POCCLG
+// Transmittance walks (dt_rayq_transmit_kernel, dt_points_occl_glass_kernel; include/dt.h
+// dt_rays_transmittance): the any-hit walk with a filter. A shape counts for a lane as it occludes it in
+// occluded_walk (not the skip shape, shape_shadow true); a counting shape that is not glass blocks the lane,
+// which retires as an occluded lane does there; a counting glass shape adds one to the lane's `panes` and, for
+// K >= 1, its index to the lane's list, and the lane walks on. The wave leaves the walk when every active lane
+// is blocked or the tree is exhausted.
+// Counting precondition: a plain count is right because every shape sits in exactly one leaf of either tree.
+// The reference tree's leaves are disjoint slices of the index list (host_bvh.cpp generate: each node hands
+// [0, slice) and [slice, n) to its two children), and the fast tree keeps each of those leaves exactly once
+// under new inner nodes (host_fasttree.cpp build_fast_tree: one LeafRef per reference leaf, none split or
+// copied). A lane reaches a leaf at most once in a walk (i only grows), so it tests a shape at most once, and
+// finite waves take the fast tree as occluded_walk<0> does; nothing here falls back to the reference tree.
+// The box cull is occluded_walk's (shadow_tcull): a culled box holds no shape that can count, glass or not.
+// The list holds the K smallest indices of the counting glass shapes, ascending; an empty slot holds INT_MAX.
+// It must stay in registers: every slot is named by a constant, as in HitList (K = 0: no list at all).
+template <int K>
+struct PaneList {
+  int s[K > 0 ? K : 1];
+};
+
+template <int K>
+__device__ __forceinline__ void panelist_clear(PaneList<K>& L)
+{
+#pragma unroll
+  for (int j = 0; j < (K > 0 ? K : 1); ++j) L.s[j] = 0x7fffffff;
+}
+
+// hitlist_step with the shape index alone as the key
+template <int K, int J>
+__device__ __forceinline__ void panelist_step(PaneList<K>& L, bool on, int s, bool here)
+{
+  if constexpr (J > 0) {
+    const bool prev = on && s < L.s[J - 1];
+    L.s[J] = prev ? L.s[J - 1] : here ? s : L.s[J];
+    panelist_step<K, J - 1>(L, on, s, prev);
+  } else {
+    L.s[0] = here ? s : L.s[0];
+  }
+}
+
+template <int K>
+__device__ __forceinline__ void panelist_insert(PaneList<K>& L, bool on, int s)
+{
+  if constexpr (K > 0) panelist_step<K, K - 1>(L, on, s, on && s < L.s[K - 1]);
+}
+
+// the first entry, and the rest moved up by one (hitlist_pop)
+template <int K>
+__device__ __forceinline__ int panelist_pop(PaneList<K>& L)
+{
+  const int s = L.s[0];
+#pragma unroll
+  for (int j = 0; j + 1 < K; ++j) L.s[j] = L.s[j + 1];
+  L.s[K > 0 ? K - 1 : 0] = 0x7fffffff;
+  return s;
+}
+
+// shadow_leaf with the filter: bm collects the blocked lanes
+template <int K>
+__device__ __forceinline__ void transmit_leaf(const DScene& S, const DNodeDev& nd, unsigned long long hbm,
+                                              unsigned long long& bm, int& panes, PaneList<K>& L, V3 sn, V3 sstart,
+                                              float t_max, int skip_shape)
+{
+  const int nq = (nd.meta & DN_SINGLE) ? 1 : nd.aux;
+  for (int q = 0; q < nq; ++q) {
+    int sid, type, off;
+    uint32_t flags;
+    leaf_shape(S, nd, q, sid, type, flags, off);
+    const unsigned long long tm = sid != skip_shape ? hbm & ~bm : 0ull;   // lanes that test this shape
+    if (!tm) continue;
+    bool o = false;
+    if (inv(tm)) o = shape_shadow(type, flags, cas(S.geom) + off, sn, sstart, t_max, 0.0f);
+    if (uni(cas(S.mat)[sid].material) == DT_MAT_GLASS) {   // wave-uniform
+      panes += o ? 1 : 0;
+      panelist_insert(L, o, sid);
+    } else {
+      bm |= __ballot(o);
+    }
+  }
+}
+
+// occluded_walk<0/1> at shift 0 with transmit_leaf: true for a blocked lane
+template <int MODE, int K>
+__device__ __forceinline__ bool transmit_walk(const DScene& S, const DParams& P, const Walk& w, bool active, V3 bstart,
+                                              V3 sn, V3 sstart, float t_max, int skip_shape, int& panes,
+                                              PaneList<K>& L)
+{
+  static_assert(MODE == 0 || MODE == 1, "the shift is 0: never the bump tree");
+  constexpr bool GENERAL = MODE == 1;
+  const bool ftree = !GENERAL && P.n_fnodes > 0 && (P.ftree_mode & 2);
+  const DNodeDev* const NODES = ftree ? S.fnodes : S.nodes;
+  const int n_nodes = ftree ? P.n_fnodes : P.n_nodes;
+  int resume = active ? 0 : 0x7fffffff;
+  const unsigned long long am = __ballot(active);
+  unsigned long long bm = 0;   // blocked lanes
+  const float tcull = shadow_tcull(t_max);
+  int i = 0;
+  while (i < n_nodes) {
+    const DNodeDev nd = cas(NODES)[i];
+    const bool act = GENERAL ? resume <= i : inv(am & ~bm);   // see closest_hit_walk
+    const unsigned long long hbm = node_mask<GENERAL>(w, nd, 0.0f, bstart, tcull, am & ~bm, act);
+    const bool hb = inv(hbm);
+    if (nd.meta & DN_LEAF) {
+      if (hbm) transmit_leaf(S, nd, hbm, bm, panes, L, sn, sstart, t_max, skip_shape);
+      if (GENERAL) {
+        if (act) resume = inv(bm) ? 0x7fffffff : nd.skip;
+        if (!__ballot(resume != 0x7fffffff)) break;
+      } else if (!(am & ~bm)) {
+        break;
+      }
+      i = i + 1;
+    } else {
+      if (GENERAL && act && !hb) resume = nd.skip;
+      i = hbm ? i + 1 : nd.skip;
+    }
+  }
+  return inv(bm);
+}
+#endif
+
 // The shadow test over a cell's candidate list (host_shadowgrid.cpp): the same box test and
 // shape tests as the walk, on the only leaves that can hold an occluder for this cell and light.
 // BUMP: a motion-blur pass (lists built with sg_ypad >= bump_pad): the exact bumped gather test
@@ -3817,8 +3952,8 @@ extern "C" hipError_t dt_launch_features_path(const void* dev_launch, int n_samp
   return hipGetLastError();
 }
 extern "C" const void* dt_features_path_kernel_ptr(void) { return (const void*)dt_features_path_kernel; }
-#elif DT_RAYQ || DT_MHIT
-// Ray queries (include/dt.h dt_trace_rays, dt_rays_occluded, dt_trace_rays_multi; no reference counterpart): rays the caller
+#elif DT_RAYQ || DT_MHIT || DT_TRANSMIT
+// Ray queries (include/dt.h dt_trace_rays, dt_rays_occluded, dt_trace_rays_multi, dt_rays_transmittance; no reference counterpart): rays the caller
 // hands over in memory, 3 doubles of start and of direction each, one ray per lane, 64 consecutive rays
 // per wave, grid-stride over the waves as dt_isect_kernel. The walks are the wave-uniform ones of the
 // trace kernel (node and shape data through scalar loads, the lanes' decisions as masks), so a wave
@@ -3988,6 +4123,91 @@ extern "C" hipError_t dt_launch_rayq_occl(const void* dev_launch, int64_t n, con
 }
 extern "C" const void* dt_rayq_kernel_ptr(void) { return (const void*)dt_rayq_kernel; }
 extern "C" const void* dt_rayq_occl_kernel_ptr(void) { return (const void*)dt_rayq_occl_kernel; }
+#elif DT_TRANSMIT
+// dt_rays_transmittance: dt_rayq_occl_kernel's rays, groups of equal skip_shape and walks (make_walk, the
+// inf_wave split), with transmit_walk in the place of occluded_walk: per ray -1 when a counting shape that is
+// not glass blocks it, else the number of counting glass shapes, and the k smallest of their indices from a
+// list of K >= k register slots per lane (K: 0, 1, 2, 4 or 8; the host launches the smallest that holds k). A
+// lane belongs to one group, so its count and list are written by one walk only. Every element of every
+// wanted plane is written: a void ray writes 0 and -1s, a blocked ray -1 and -1s. No workgroup waits on
+// another.
+template <int K>
+__global__ void __launch_bounds__(64)
+dt_rayq_transmit_kernel(const DLaunch* __restrict__ Lp, int64_t n, const double* __restrict__ start,
+                        const double* __restrict__ dir, const int32_t* __restrict__ skip_shape, int k,
+                        int32_t* __restrict__ panes_out, int32_t* __restrict__ pane_shape)
+{
+  const DScene& S = Lp->S;
+  const DParams& P = Lp->P;
+  const int lane = threadIdx.x;
+  unsigned long long traced = 0;   // wave-uniform
+  for (int64_t base = (int64_t)blockIdx.x * DT_WAVE; base < n; base += (int64_t)gridDim.x * DT_WAVE) {
+    const int64_t i = base + lane;
+    const bool in = i < n;
+    V3 org, sray;
+    const bool act = rayq_load(start, dir, i, in, org, sray);
+    const int skip = (act && skip_shape) ? skip_shape[i] : -1;
+    const float t_max = (float)norm(sray);
+    const V3 sn = act ? normalized(sray) : v3(1, 0, 0);
+    const V3 bstart = add(org, mul(1e-3, sray)), sstart = add(org, mul(1e-3, sn));
+    bool blocked = false;
+    int panes = 0;
+    PaneList<K> L;
+    panelist_clear(L);
+    unsigned long long todo = __ballot(act);
+    traced += (unsigned long long)__popcll(todo);
+    while (todo) {
+      const int k0 = __builtin_amdgcn_readlane(skip, (int)__builtin_ctzll(todo));
+      const bool mine = inv(todo) && skip == k0;
+      todo &= ~__ballot(mine);
+      const Walk w = make_walk(P, mine, sray, bstart, 0.0f);
+      const bool b = w.inf_wave ? transmit_walk<1>(S, P, w, mine, bstart, sn, sstart, t_max, k0, panes, L)
+                                : transmit_walk<0>(S, P, w, mine, bstart, sn, sstart, t_max, k0, panes, L);
+      blocked = blocked || (mine && b);
+    }
+    if (in && panes_out) panes_out[i] = blocked ? -1 : panes;
+    if constexpr (K > 0) {
+      if (pane_shape) {
+        for (int j = 0; j < k; ++j) {   // through slot 0: the runtime trip count indexes nothing
+          const int sj = panelist_pop(L);
+          if (in) pane_shape[(int64_t)k * i + j] = (!blocked && sj != 0x7fffffff) ? sj : -1;
+        }
+      }
+    }
+  }
+  if (lane == 0 && traced) atomicAdd(S.stats + ST_SHADOW, traced);
+}
+
+// the list capacity a launch with k takes: the smallest of 0, 1, 2, 4, 8 that holds it
+static int rayq_transmit_capacity(int k) { return k <= 0 ? 0 : k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
+
+extern "C" hipError_t dt_launch_rayq_transmit(const void* dev_launch, int64_t n, const double* start, const double* dir,
+                                              const int32_t* skip_shape, int k, int32_t* panes, int32_t* pane_shape,
+                                              int grid, hipStream_t stream)
+{
+#define DT_TRANSMIT_LAUNCH(K)                                                                                       \
+  hipLaunchKernelGGL(dt_rayq_transmit_kernel<K>, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n,    \
+                     start, dir, skip_shape, k, panes, pane_shape)
+  switch (rayq_transmit_capacity(pane_shape ? k : 0)) {
+    case 0: DT_TRANSMIT_LAUNCH(0); break;
+    case 1: DT_TRANSMIT_LAUNCH(1); break;
+    case 2: DT_TRANSMIT_LAUNCH(2); break;
+    case 4: DT_TRANSMIT_LAUNCH(4); break;
+    default: DT_TRANSMIT_LAUNCH(8); break;
+  }
+#undef DT_TRANSMIT_LAUNCH
+  return hipGetLastError();
+}
+extern "C" const void* dt_rayq_transmit_kernel_ptr(int k)
+{
+  switch (rayq_transmit_capacity(k)) {
+    case 0: return (const void*)dt_rayq_transmit_kernel<0>;
+    case 1: return (const void*)dt_rayq_transmit_kernel<1>;
+    case 2: return (const void*)dt_rayq_transmit_kernel<2>;
+    case 4: return (const void*)dt_rayq_transmit_kernel<4>;
+    default: return (const void*)dt_rayq_transmit_kernel<8>;
+  }
+}
 #else   // DT_MHIT
 // dt_trace_rays_multi: per ray the k nearest of the shapes dt_trace_rays gathers, each tested on its own
 // (multi_hit_walk: the fast tree for finite waves, the reference tree for a wave with an axis-parallel ray),
@@ -4260,7 +4480,7 @@ extern "C" hipError_t dt_launch_occlusion(const void* dev_launch, int n_samples,
   return hipGetLastError();
 }
 extern "C" const void* dt_occlusion_kernel_ptr(void) { return (const void*)dt_occlusion_kernel; }
-#elif DT_POCCL
+#elif DT_POCCL || DT_POCCLG
 // Occlusion queries at surface points (include/dt.h dt_points_occlusion; no reference counterpart): the probes
 // of dt_occlusion_kernel from points and normals the caller hands over, 3 doubles each, in place of the
 // camera's first hits. One point per lane, 64 consecutive points per wave, grid-stride over the waves as
@@ -4272,11 +4492,25 @@ extern "C" const void* dt_occlusion_kernel_ptr(void) { return (const void*)dt_oc
 // never one per lane. A lane counts its own unoccluded probes in a register and stores one float per row
 // (integers: no summation order). A tail lane or a void point (a non-finite component) is an inactive lane
 // of every walk: it stays in the wave, is never probed, and a void point stores 0.
+//
+// DT_POCCLG: the same source as dt_points_occl_glass_kernel (include/dt.h dt_points_occlusion_glass), a build of
+// its own; the preprocessor leaves DT_POCCL's build the tokens it had. There a probe is answered by
+// transmit_walk<0/1, 0> (a count, no list): it is unoccluded iff it is not blocked and crosses at most
+// max_panes panes; beside its unoccluded probes a lane sums their panes (integers again), for the two optional
+// pane planes, and every store is guarded, as a row runs for either of its two planes.
 extern "C" __global__ void __launch_bounds__(64)
+#if DT_POCCLG
+dt_points_occl_glass_kernel(const DLaunch* __restrict__ Lp, uint32_t seed, int32_t frame, int64_t n,
+                            const double* __restrict__ point, const double* __restrict__ normal, int n_samples,
+                            int ao_rays, float ao_radius, int n_lights, const dtd::OcclLight* __restrict__ lights,
+                            int max_panes, float* __restrict__ ao_out, float* __restrict__ light_out,
+                            float* __restrict__ ao_panes_out, float* __restrict__ light_panes_out)
+#else
 dt_points_occl_kernel(const DLaunch* __restrict__ Lp, uint32_t seed, int32_t frame, int64_t n,
                       const double* __restrict__ point, const double* __restrict__ normal, int n_samples, int ao_rays,
                       float ao_radius, int n_lights, const dtd::OcclLight* __restrict__ lights,
                       float* __restrict__ ao_out, float* __restrict__ light_out)
+#endif
 {
   const DScene& S = Lp->S;
   const DParams& P = Lp->P;
@@ -4314,6 +4548,9 @@ dt_points_occl_kernel(const DLaunch* __restrict__ Lp, uint32_t seed, int32_t fra
         skip = uni(L.shape_index);
       }
       unsigned int V = 0;
+#if DT_POCCLG
+      unsigned int VP = 0;   // the panes of the unoccluded probes
+#endif
       for (int t = 0; t < n_probes; ++t) {
         const int sample = t / per, r = t - sample * per;
         V3 sray = v3(0, 0, 0);
@@ -4332,6 +4569,20 @@ dt_points_occl_kernel(const DLaunch* __restrict__ Lp, uint32_t seed, int32_t fra
         const unsigned long long am = __ballot(act);
         traced += (unsigned long long)__popcll(am);
         bool occl = false;
+#if DT_POCCLG
+        int panes = 0;
+        if (am) {
+          const Walk w = make_walk(P, act, sray, bstart, 0.0f);
+          PaneList<0> none;
+          const bool b = w.inf_wave ? transmit_walk<1>(S, P, w, act, bstart, sn, sstart, t_max, skip, panes, none)
+                                    : transmit_walk<0>(S, P, w, act, bstart, sn, sstart, t_max, skip, panes, none);
+          occl = act && (b || panes > max_panes);
+        }
+        if (live && !occl) {
+          ++V;
+          VP += (unsigned int)panes;
+        }
+#else
         if (am) {
           const Walk w = make_walk(P, act, sray, bstart, 0.0f);
           const bool o = w.inf_wave ? occluded_walk<1>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt)
@@ -4339,15 +4590,41 @@ dt_points_occl_kernel(const DLaunch* __restrict__ Lp, uint32_t seed, int32_t fra
           occl = act && o;
         }
         if (live && !occl) ++V;
+#endif
       }
+#if DT_POCCLG
+      if (in) {
+        const double den = row == 0 ? (double)n_samples * (double)ao_rays : (double)n_samples;
+        float* const vis = row == 0 ? ao_out : light_out;
+        float* const pan = row == 0 ? ao_panes_out : light_panes_out;
+        const int64_t e = row == 0 ? i : (int64_t)n_lights * i + (row - 1);
+        if (vis) vis[e] = live ? (float)((double)V / den) : 0.0f;
+        if (pan) pan[e] = live ? (float)((double)VP / den) : 0.0f;
+      }
+#else
       if (in) {
         if (row == 0) ao_out[i] = live ? (float)((double)V / ((double)n_samples * (double)ao_rays)) : 0.0f;
         else light_out[(int64_t)n_lights * i + (row - 1)] = live ? (float)((double)V / (double)n_samples) : 0.0f;
       }
+#endif
     }
   }
   if (lane == 0 && traced) atomicAdd(S.stats + ST_SHADOW, traced);
 }
+#if DT_POCCLG
+extern "C" hipError_t dt_launch_points_occl_glass(const void* dev_launch, uint32_t seed, int32_t frame, int64_t n,
+                                                  const double* point, const double* normal, int n_samples,
+                                                  int ao_rays, float ao_radius, int n_lights, const void* lights,
+                                                  int max_panes, float* ao, float* light, float* ao_panes,
+                                                  float* light_panes, int grid, hipStream_t stream)
+{
+  hipLaunchKernelGGL(dt_points_occl_glass_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, seed,
+                     frame, n, point, normal, n_samples, ao_rays, ao_radius, n_lights, (const dtd::OcclLight*)lights,
+                     max_panes, ao, light, ao_panes, light_panes);
+  return hipGetLastError();
+}
+extern "C" const void* dt_points_occl_glass_kernel_ptr(void) { return (const void*)dt_points_occl_glass_kernel; }
+#else
 extern "C" hipError_t dt_launch_points_occl(const void* dev_launch, uint32_t seed, int32_t frame, int64_t n,
                                             const double* point, const double* normal, int n_samples, int ao_rays,
                                             float ao_radius, int n_lights, const void* lights, float* ao, float* light,
@@ -4358,6 +4635,7 @@ extern "C" hipError_t dt_launch_points_occl(const void* dev_launch, uint32_t see
   return hipGetLastError();
 }
 extern "C" const void* dt_points_occl_kernel_ptr(void) { return (const void*)dt_points_occl_kernel; }
+#endif
 #elif DT_MATTE
 // Object mattes (include/dt.h dt_render_mattes; no reference counterpart): for the samples 0 .. n_samples-1 of
 // every owned pixel the render's own primary ray to its closest hit, as dt_features_kernel takes it (items
@@ -5413,7 +5691,8 @@ extern "C" hipError_t dt_launch_unpack(const void* dev_launch, int world, int64_
 }
 #endif
 
-#if !DT_ISECT && !DT_FEAT && !DT_RAYQ && !DT_MATTE && !DT_FEATP && !DT_OCCL && !DT_POCCL && !DT_MHIT && !DT_CAMRAYS
+#if !DT_ISECT && !DT_FEAT && !DT_RAYQ && !DT_MATTE && !DT_FEATP && !DT_OCCL && !DT_POCCL && !DT_MHIT && !DT_CAMRAYS && \
+    !DT_TRANSMIT && !DT_POCCLG
 // every trace-kernel build: <kernel>_launch and <kernel>_ptr (dt_api.cpp's kernel table)
 #if DT_W5
 static_assert(DT_TRACE_MIN_WAVES == 5 && DT_PSUM_LDS == 2, "5-wave build: Makefile W5FLAGS");

@@ -55,6 +55,10 @@
 //                     samples per texel (default 16) of --ao-rays / --ao-radius / --occlusion-lights probes,
 //                     written as --bake-out P: P.ao.png and P.light<j>.png, W x H, row v, grey value*255 as
 //                     --occlusion. Without the flag every byte written is the same as before.
+//   --bake-through-glass N  with --bake-occlusion: the probes pass through glass (dt_points_occlusion_glass,
+//                     max_panes = N in 0..8): P.ao.png and P.light<j>.png by that rule, and P.ao_panes.png and
+//                     P.light_panes<j>.png, the pane planes, grey value/8*255 (8 panes are white). Without the flag
+//                     every byte written is the same as before.
 //   --peel K          after the frame, depth peeling of the frame's own view (K = 1..8 layers; --peel-out P is
 //                     needed; --peel-samples N rays per pixel, 1..1024, default 1): dt_camera_rays, then
 //                     dt_trace_rays_multi(K), then one dt_rays_resolve per rank, written as P.layer<j>.png: layer
@@ -69,6 +73,7 @@
 //                     switch): the steel doors, the floor and the checker cylinder of `final` then bounce guides
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -228,16 +233,21 @@ static bool occlusion_params(int ao_rays, double ao_radius, const std::string& l
 }
 
 // the grey PNGs of occlusion planes of w x h entries: prefix.ao.png (when ao) and prefix.light<j>.png, value*255
-static int write_occlusion_pngs(const std::string& prefix, int w, int h, const float* ao, const float* light, int n_lights)
+// panes: the pane planes of --bake-through-glass instead, prefix.ao_panes.png and prefix.light_panes<j>.png, value/8*255
+static int write_occlusion_pngs(const std::string& prefix, int w, int h, const float* ao, const float* light, int n_lights,
+                                bool panes = false)
 {
   const size_t n_px = (size_t)w * h;
   std::vector<float> pix(3 * n_px);
+  const std::string tag = panes ? "_panes" : "";
   for (int plane = ao ? -1 : 0; plane < n_lights; ++plane) {
     for (size_t q = 0; q < n_px; ++q) {
-      const float v = (plane < 0 ? ao[q] : light[(size_t)n_lights * q + plane]) * 255.0f;
+      const float x = plane < 0 ? ao[q] : light[(size_t)n_lights * q + plane];
+      const float v = panes ? (x / 8.0f) * 255.0f : x * 255.0f;
       pix[3 * q] = pix[3 * q + 1] = pix[3 * q + 2] = v;
     }
-    const std::string pf = prefix + (plane < 0 ? std::string(".ao") : ".light" + std::to_string(plane)) + ".png";
+    const std::string pf =
+        prefix + (plane < 0 ? ".ao" + tag : ".light" + tag + std::to_string(plane)) + ".png";
     const int rc = dt_write_png(pf.c_str(), w, h, pix.data());
     if (rc) return rc;
   }
@@ -260,7 +270,7 @@ int main(int argc, char** argv)
   std::string occl_prefix, occl_lights;
   int ao_rays = 4;
   double ao_radius = -1.0;   // < 0: dt_occlusion_params_default's
-  int bake_shape = -1, bake_w = 0, bake_h = 0, bake_samples = 16;
+  int bake_shape = -1, bake_w = 0, bake_h = 0, bake_samples = 16, bake_glass = -1;
   std::string bake_prefix;
   bool bake_asked = false;
   int peel = 0, peel_samples = 1;
@@ -295,6 +305,13 @@ int main(int argc, char** argv)
     else if (a == "--bake-size" && i + 1 < argc) sscanf(argv[++i], "%dx%d", &bake_w, &bake_h);
     else if (a == "--bake-out" && i + 1 < argc) bake_prefix = argv[++i];
     else if (a == "--bake-samples" && i + 1 < argc) bake_samples = atoi(argv[++i]);
+    else if (a == "--bake-through-glass" && i + 1 < argc) {
+      bake_glass = atoi(argv[++i]);
+      if (bake_glass < 0 || bake_glass > DT_TRANSMIT_MAX_PANES) {
+        fprintf(stderr, "usage: --bake-through-glass N: N in 0..%d\n", DT_TRANSMIT_MAX_PANES);
+        return 2;
+      }
+    }
     else if (a == "--peel" && i + 1 < argc) { peel = atoi(argv[++i]); peel_asked = true; }
     else if (a == "--peel-out" && i + 1 < argc) peel_prefix = argv[++i];
     else if (a == "--peel-samples" && i + 1 < argc) peel_samples = atoi(argv[++i]);
@@ -630,9 +647,22 @@ int main(int argc, char** argv)
     if (op.ao_rays != 0) o.ao = pao.data();
     if (nl > 0) o.light = plv.data();
     dt_stats bst;
-    rc = dt_points_occlusion(s, &g, frame, (int64_t)keep.size(), pts.data(), nrms.data(), bake_samples, &op, &o, 0, nullptr,
-                             &bst);
-    if (rc) return die("dt_points_occlusion", rc);
+    std::vector<float> ppao, pplv;   // --bake-through-glass: the pane planes
+    if (bake_glass >= 0) {
+      ppao.assign(pao.size(), 0.0f);
+      pplv.assign(plv.size(), 0.0f);
+      dt_occlusion_panes pn;
+      memset(&pn, 0, sizeof pn);
+      if (o.ao) pn.ao_panes = ppao.data();
+      if (o.light) pn.light_panes = pplv.data();
+      rc = dt_points_occlusion_glass(s, &g, frame, (int64_t)keep.size(), pts.data(), nrms.data(), bake_samples, &op,
+                                     bake_glass, &o, &pn, 0, nullptr, &bst);
+      if (rc) return die("dt_points_occlusion_glass", rc);
+    } else {
+      rc = dt_points_occlusion(s, &g, frame, (int64_t)keep.size(), pts.data(), nrms.data(), bake_samples, &op, &o, 0,
+                               nullptr, &bst);
+      if (rc) return die("dt_points_occlusion", rc);
+    }
     std::vector<float> ao(n_tex, 0.0f), lv(n_tex * (size_t)(nl > 0 ? nl : 1), 0.0f);
     for (size_t i = 0; i < keep.size(); ++i) {
       ao[keep[i]] = pao[i];
@@ -640,6 +670,17 @@ int main(int argc, char** argv)
     }
     rc = write_occlusion_pngs(bake_prefix, bake_w, bake_h, o.ao ? ao.data() : nullptr, lv.data(), nl);
     if (rc) return die("dt_write_png (bake)", rc);
+    if (bake_glass >= 0) {
+      std::fill(ao.begin(), ao.end(), 0.0f);
+      std::fill(lv.begin(), lv.end(), 0.0f);
+      for (size_t i = 0; i < keep.size(); ++i) {
+        ao[keep[i]] = ppao[i];
+        for (int j = 0; j < nl; ++j) lv[(size_t)nl * keep[i] + j] = pplv[(size_t)nl * i + j];
+      }
+      rc = write_occlusion_pngs(bake_prefix, bake_w, bake_h, o.ao ? ao.data() : nullptr, lv.data(), nl, true);
+      if (rc) return die("dt_write_png (bake panes)", rc);
+      printf("bake: probes pass through glass, at most %d panes\n", bake_glass);
+    }
     printf("bake: shape %d, %dx%d texels, %llu points, %llu probes (%d samples, %d ao rays of radius %g, %d lights) in "
            "%.3f ms (kernel) -> %s.*.png\n",
            bake_shape, bake_w, bake_h, (unsigned long long)keep.size(), (unsigned long long)bst.shadow_rays, bake_samples,

@@ -79,6 +79,9 @@ extern "C" {
  *    dt_ray_multihits -- multi-hit ray queries: the k nearest surfaces along caller-supplied rays) */
 /* (still 8, new exports only, no struct changed: dt_camera_rays_rows, dt_camera_rays, dt_rays_resolve --
  *    camera rays as arrays, and per-ray answers resolved back to pixels) */
+/* (still 8, new exports and two new structs, no struct changed: dt_rays_transmittance and its
+ *    dt_ray_transmittance, dt_points_occlusion_glass and its dt_occlusion_panes -- transmittance queries:
+ *    shadow probes that pass through glass) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -709,6 +712,50 @@ int dt_rays_occluded(const dt_scene* s, const dt_globals* g, int64_t n_rays, con
                      const int32_t* skip_shape /* optional, n_rays; -1: none */, uint8_t* occluded,
                      int32_t on_device, void* stream, dt_stats* stats);
 
+/* ---- transmittance ray queries: shadow probes that pass through glass ----
+ * No reference counterpart. dt_rays_occluded is the light loop's test, for which a glass pane shadows like a
+ * wall. This call is that test with a filter: a probe passes through glass shapes, counts them, and is stopped
+ * only by a shape that is not glass. Line of sight through windows, light visibility behind a pane and a
+ * caller's own tint or Beer's law start here. Rays, the void-ray rule, sides and staging, g, skip_shape (and
+ * the advice to group rays by it), synchrony, "a render afterwards is unaffected" and the thread rule are
+ * dt_rays_occluded's.
+ *
+ * Every answer is an integer defined per shape, bit for bit and independent of the order of the work:
+ *   CANDIDATES  the shapes dt_rays_occluded gathers: every leaf whose box the ray passes along dir from
+ *     start + 1e-3*dir.
+ *   PER-SHAPE TEST  a gathered shape h COUNTS iff h != skip_shape[i] and intersectShadow(sn, start + 1e-3*sn,
+ *     t_max) is true, with sn = normalized(dir) and t_max = (float)|dir|: exactly the values dt_rays_occluded
+ *     passes. Nothing is carried from shape to shape.
+ *   GLASS  a shape is glass iff its material is DT_MAT_GLASS.
+ *   PANES  panes[i] = -1 if any counting shape is not glass (blocked); otherwise the number of counting glass
+ *     shapes, 0: clear. A void ray writes 0. A shape counts once (a sphere, a prism or a pane alike: the test
+ *     is intersectShadow's yes or no, not its number of crossings).
+ *   PANE_SHAPE  (optional, k per ray, needs k >= 1) the min(k, panes) smallest shape indices among the counting
+ *     glass shapes, ascending, then -1s; every entry is -1 where panes[i] <= 0. No floating-point product is
+ *     defined here: tint, Beer's law or anything else is the caller's, from the ids.
+ * Relation to dt_rays_occluded: occluded[i] == (panes[i] != 0) for every ray, by construction (some shape
+ * counts there iff some shape counts here).
+ * stats (optional): shadow_rays = the rays tested (the non-void ones), kernel_ms; everything else 0.
+ *
+ * The walk is dt_rays_occluded's wave-uniform one (groups of equal skip_shape, the same box cull); a lane
+ * leaves it only when blocked, so a ray behind glass walks as far as a clear ray does. The list of pane ids is
+ * kept in registers, in a capacity of 0 (no pane_shape), 1, 2, 4 or 8 slots, the smallest that holds k.
+ * Cost: BASELINE.md "Transmittance queries".
+ *
+ * DT_E_INVALID, with a dt_last_error starting "dt_rays_transmittance: " and naming the argument: a null scene,
+ * globals, start, dir or out, an out with every plane NULL, n_rays < 0, k outside 0..DT_TRANSMIT_MAX_PANES,
+ * out->pane_shape given with k == 0; DT_E_UNSUPPORTED: a scene with a RectPrismWithCylinder; all before any
+ * device work. n_rays == 0: DT_OK, nothing is launched. */
+#define DT_TRANSMIT_MAX_PANES 8
+typedef struct dt_ray_transmittance {   /* each plane optional (NULL: not wanted), not both NULL; all on one side */
+  int32_t* panes;        /* 1 per ray: -1 blocked, else the counting glass shapes (0: clear) */
+  int32_t* pane_shape;   /* k per ray, entry k*i + j: the j-th smallest counting glass shape; -1 beyond */
+} dt_ray_transmittance;
+int dt_rays_transmittance(const dt_scene* s, const dt_globals* g, int64_t n_rays, const double* start,
+                          const double* dir, const int32_t* skip_shape /* optional, n_rays; -1: none */,
+                          int32_t k /* 0..DT_TRANSMIT_MAX_PANES */, const dt_ray_transmittance* out,
+                          int32_t on_device, void* stream, dt_stats* stats);
+
 /* ---- multi-hit ray queries: the k nearest surfaces along caller-supplied rays ----
  * No reference counterpart. dt_trace_rays says what a ray hits first; this call says what lies behind it: per
  * ray the k nearest shapes along it, ordered. Seeing through the panes of a scene, picking the object behind
@@ -1028,6 +1075,33 @@ int dt_points_occlusion(const dt_scene* s, const dt_globals* g, int32_t frame, i
                         int32_t n_samples,                           /* 1..DT_POCCL_MAX_SAMPLES */
                         const dt_occlusion_params* params, const dt_occlusion* out,
                         int32_t on_device, void* stream, dt_stats* stats);
+
+/* The baking mode whose probes pass through glass. Points, samples, the RNG counter, the probe generators, void
+ * points, sums, sides, synchrony and errors are dt_points_occlusion's (prefix "dt_points_occlusion_glass: ");
+ * dt_occlusion_params and dt_occlusion are unchanged. The differences:
+ *   each probe is answered by dt_rays_transmittance's rule (start = p, dir, the same skip_shape) in the place of
+ *     dt_rays_occluded's, and is UNOCCLUDED iff 0 <= panes <= max_panes (a void probe: panes 0, unoccluded);
+ *   panes (optional) takes two more planes, indexed like ao and light: with S the integer sum of `panes` over
+ *     the unoccluded AO probes of point i and S_j that over the unoccluded probes towards slot j,
+ *       ao_panes[i] = (float)((double)S / ((double)n_samples * (double)ao_rays)),
+ *       light_panes[n_lights*i + j] = (float)((double)S_j / (double)n_samples):
+ *     the mean number of panes crossed per probe, the denominators of ao and light. A void point writes 0.
+ * A row of probes runs iff one of its two planes is wanted (ao or ao_panes; light or light_panes): a plane that
+ * is not wanted costs nothing. out must still want a plane of its own, by dt_points_occlusion's rule.
+ * With max_panes = 0 a probe is unoccluded iff nothing counts, which is dt_rays_occluded's answer: the ao and
+ * light planes equal dt_points_occlusion's bit for bit.
+ * Additional DT_E_INVALID: max_panes outside 0..DT_TRANSMIT_MAX_PANES, panes->ao_panes given with ao_rays == 0,
+ * panes->light_panes given with n_lights == 0.
+ * Not covered: dt_render_occlusion (the camera-sample planes) keeps the wall rule. */
+typedef struct dt_occlusion_panes {   /* each plane optional; on the side of out */
+  float* ao_panes;      /* 1 per point            (needs ao_rays > 0) */
+  float* light_panes;   /* n_lights per point, entry n_lights*i + j (needs n_lights > 0) */
+} dt_occlusion_panes;
+int dt_points_occlusion_glass(const dt_scene* s, const dt_globals* g, int32_t frame, int64_t n_points,
+                              const double* point, const double* normal, int32_t n_samples,
+                              const dt_occlusion_params* params, int32_t max_panes /* 0..DT_TRANSMIT_MAX_PANES */,
+                              const dt_occlusion* out, const dt_occlusion_panes* panes /* optional */,
+                              int32_t on_device, void* stream, dt_stats* stats);
 
 /* ---- feature-guided denoising of previews: an edge-avoiding a-trous filter ----
  * No reference counterpart. The consumer of the feature buffers: (preview, albedo, normal, depth) ->
