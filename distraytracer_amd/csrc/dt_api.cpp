@@ -10,168 +10,20 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
-#include <string>
-#include <vector>
 
 #include "dt_adapt.h"
-#include "dt_guide.h"
-#include "dt_occl.h"
-#include "host_internal.h"
-#include "host_launch.h"
+#include "dt_api_internal.h"
 
 using namespace dth;
-
-extern "C" size_t dt_launch_size(void);
-extern "C" size_t dt_scene_struct_offset(void);
-extern "C" size_t dt_scene_struct_size(void);
-extern "C" size_t dt_params_struct_offset(void);
-extern "C" hipError_t dt_launch_sky(const void* dev_launch, float* out, int64_t n_threads, hipStream_t stream);
-extern "C" hipError_t dt_launch_sky_miss(const void* dev_launch, float* out, int64_t n_px, hipStream_t stream);
-extern "C" hipError_t dt_launch_chunk_sum(const void* dev_launch, float* out, int64_t n_px, hipStream_t stream);
-extern "C" hipError_t dt_launch_unpack(const void* dev_launch, int world, int64_t slab_floats, const float* slabs,
-                                       float* image, hipStream_t stream);
-extern "C" hipError_t dt_launch_normalize(const double* in, double* out, int64_t n, hipStream_t stream);
-extern "C" hipError_t dt_launch_vdiv(const double* in, const double* den, double* out, unsigned long long* fallback,
-                                     int64_t n, hipStream_t stream);
-extern "C" hipError_t dt_launch_vnorm(const double* in, double* out, unsigned long long* fallback, int64_t n,
-                                      hipStream_t stream);
-// The trace-kernel builds, named once (dt_kernels.hip DT_TRACE_KERNEL, Makefile TRACE_BUILDS, in its
-// order): per wave count (4, then 5) room, mesh, full (still frames), tunnel, blur (motion-blur frames)
-// and sky; then the work-sharing and the RectPrismWithCylinder build. Each exists in three modes: the
-// product build <k>, its window build <k>_win (DT_WINDOW, Makefile WIN_OBJ) and its adaptive window
-// build <k>_awin (DT_WINDOW=2, AWIN_OBJ). The declarations here and the table g_builds come from this list.
-#define DT_TRACE_BUILDS(X)                                                                               \
-  X(dt_trace_kernel) X(dt_trace_kernel_mesh) X(dt_trace_kernel_full) X(dt_trace_kernel_tunnel)           \
-  X(dt_trace_kernel_blur) X(dt_trace_kernel_sky) X(dt_trace_kernel_w5) X(dt_trace_kernel_w5_mesh)        \
-  X(dt_trace_kernel_w5_full) X(dt_trace_kernel_w5_tunnel) X(dt_trace_kernel_w5_blur)                     \
-  X(dt_trace_kernel_w5_sky) X(dt_trace_kernel_dn) X(dt_trace_kernel_rpc)
-#define DT_TRACE_DECL(k)                                                                               \
-  extern "C" hipError_t k##_launch(const void* dev_launch, float* out, int grid, hipStream_t stream); \
-  extern "C" const void* k##_ptr(void);                                                                \
-  extern "C" int k##_traits(void);
-#define DT_TRACE_DECL3(k) DT_TRACE_DECL(k) DT_TRACE_DECL(k##_win) DT_TRACE_DECL(k##_awin)
-DT_TRACE_BUILDS(DT_TRACE_DECL3)
-#undef DT_TRACE_DECL3
-#undef DT_TRACE_DECL
-extern "C" hipError_t dt_launch_resolve(const double* accum, float* out, int64_t n_px, int n_samples,
-                                        unsigned long long* nan_px, hipStream_t stream);
-extern "C" hipError_t dt_launch_resolve_adaptive(const double* accum, const uint32_t* count, float* out, int64_t n_px,
-                                                 unsigned long long* nan_px, hipStream_t stream);
-extern "C" int64_t dt_adapt_select_blocks(int64_t n_items);
-extern "C" hipError_t dt_launch_adapt_select(const void* dev_launch, int64_t n_items, hipStream_t stream);
-extern "C" hipError_t dt_launch_isect(const void* dev_launch, int64_t first, int64_t n, int32_t* hit_shape, float* hit_t,
-                                      int grid, hipStream_t stream);
-extern "C" const void* dt_isect_kernel_ptr(void);
-extern "C" hipError_t dt_launch_features(const void* dev_launch, int n_samples, float* albedo, float* normal, float* depth,
-                                         float* coverage, int32_t* shape, int grid, hipStream_t stream);
-extern "C" const void* dt_features_kernel_ptr(void);
-extern "C" hipError_t dt_launch_features_path(const void* dev_launch, int n_samples, int max_bounces, float* albedo,
-                                              float* normal, float* depth, float* coverage, int32_t* shape,
-                                              float* bounces, int grid, hipStream_t stream);
-extern "C" const void* dt_features_path_kernel_ptr(void);
-extern "C" hipError_t dt_launch_rayq(const void* dev_launch, int64_t n, const double* start, const double* dir,
-                                     int32_t* shape, float* t, double* point, double* normal, double* albedo, int grid,
-                                     hipStream_t stream);
-extern "C" hipError_t dt_launch_rayq_occl(const void* dev_launch, int64_t n, const double* start, const double* dir,
-                                          const int32_t* skip_shape, uint8_t* occluded, int grid, hipStream_t stream);
-extern "C" const void* dt_rayq_kernel_ptr(void);
-extern "C" const void* dt_rayq_occl_kernel_ptr(void);
-extern "C" hipError_t dt_launch_rayq_multi(const void* dev_launch, int64_t n, const double* start, const double* dir,
-                                           int k, int32_t* count, int32_t* shape, float* t, double* point,
-                                           double* normal, double* albedo, int grid, hipStream_t stream);
-extern "C" const void* dt_rayq_multi_kernel_ptr(int k);
-extern "C" hipError_t dt_launch_mattes(const void* dev_launch, int n_samples, const int32_t* gmap, int layers, int32_t* id,
-                                       float* weight, int32_t* distinct, unsigned long long* overflow, int grid,
-                                       hipStream_t stream);
-extern "C" const void* dt_mattes_kernel_ptr(void);
-extern "C" hipError_t dt_launch_occlusion(const void* dev_launch, int n_samples, int ao_rays, float ao_radius, int n_lights,
-                                          const void* lights, float* ao, float* light, int grid, hipStream_t stream);
-extern "C" const void* dt_occlusion_kernel_ptr(void);
-extern "C" hipError_t dt_launch_points_occl(const void* dev_launch, uint32_t seed, int32_t frame, int64_t n,
-                                            const double* point, const double* normal, int n_samples, int ao_rays,
-                                            float ao_radius, int n_lights, const void* lights, float* ao, float* light,
-                                            int grid, hipStream_t stream);
-extern "C" const void* dt_points_occl_kernel_ptr(void);
-extern "C" hipError_t dt_launch_rayq_transmit(const void* dev_launch, int64_t n, const double* start, const double* dir,
-                                              const int32_t* skip_shape, int k, int32_t* panes, int32_t* pane_shape,
-                                              int grid, hipStream_t stream);
-extern "C" const void* dt_rayq_transmit_kernel_ptr(int k);
-extern "C" hipError_t dt_launch_points_occl_glass(const void* dev_launch, uint32_t seed, int32_t frame, int64_t n,
-                                                  const double* point, const double* normal, int n_samples,
-                                                  int ao_rays, float ao_radius, int n_lights, const void* lights,
-                                                  int max_panes, float* ao, float* light, float* ao_panes,
-                                                  float* light_panes, int grid, hipStream_t stream);
-extern "C" const void* dt_points_occl_glass_kernel_ptr(void);
-extern "C" hipError_t dt_launch_camera_rays(const void* dev_launch, int sample_begin, int ns, int64_t n_rows,
-                                            double* start, double* dir, hipStream_t stream);
 
 namespace {
 
 thread_local std::string g_err;
 
-// must match the device-side DScene (dt_kernels.hip)
-struct HScene {
-  const void* nodes;
-  const void* fnodes;
-  const uint32_t* sg_cells;
-  const int32_t* sg_list;
-  const int32_t* leaf_idx;
-  const void* hdr;
-  const double* geom;
-  const void* mat;
-  const void* lights;
-  const uint8_t* tex;
-  const float* cloud_z;
-  unsigned long long* stats;
-  unsigned long long* queue;
-  const void* bnodes;       // motion-blur bump tree (host_fasttree.cpp)
-  const int32_t* bparent;   // parent of every reference-tree node
-  const uint32_t* pl_cells; // primary-ray candidate lists (host_primlists.cpp)
-  const uint32_t* pl_list;
-  uint8_t* sky_miss;
-  void* dn_pool;
-  uint32_t* again_list;
-  unsigned int* again_n;
-  const void* sub_nodes;      // shadow-grid block subtrees
-  const uint32_t* sub_blocks;
-  unsigned long long* clear0;   // the other parity's counters, zeroed by the launch (dt_kernels.hip)
-  unsigned long long* clear1;
-  int32_t n_clear0, n_clear1;
-  double* chunk_cols;           // chunk items: per-pixel sample colours (dt_kernels.hip)
-  uint32_t* item_cost;          // diagnostic builds: per-item durations (dt_debug_item_costs)
-  double* accum;                // window launches: the caller's accumulator (dt_render_window)
-};
-
-// DT_N_STAMPS (dt_scene_dev.h): diagnostic counter slots of -DDT_STAMPS builds (dt_debug_counters):
-// phases, then (waves, lanes, hits) per (light, shape) shadow test
-enum { ST_RAYS = 0, ST_SHADOW = 1, ST_SKY = 2, ST_UV = 3, ST_GLOSSY = 4, ST_SPHL = 5, ST_PRISM = 6,
-       ST_REFL = 7, ST_NAN = 8, ST_PIXELS = 9, ST_SAMPLES = 10, ST_STACK = 11, ST_TEX = 12, ST_BOX = 13, ST_PRIM = 14, ST_WNODES = 15,
-       ST_DONATE = 16, ST_DN_OVF = 17, ST_N = 18 };
 // one parity's counter block: the trace launch's (counters, queue word, stamps slots, segment
 // counters), the sky-item launch's (counters, queue word, list count)
 constexpr size_t STATS1 = ST_N + DT_STAT_SLOT_OFF + (DT_STAT_SLOTS - 1) * DT_STAT_SLOT_STRIDE, STATS2 = ST_N + 2;
 
-int fail(int code, const std::string& msg)
-{
-  g_err = msg;
-  return code;
-}
-
-#define HIPCHK(expr)                                                                   \
-  do {                                                                                 \
-    hipError_t _e = (expr);                                                            \
-    if (_e != hipSuccess)                                                              \
-      return fail(DT_E_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));  \
-  } while (0)
-
-// the lazily grown device buffers of a scene (host_launch.h DevBuf) over the HIP calls
-struct HipMem {
-  typedef hipStream_t Stream;
-  static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
-  static void free(void* p) { (void)hipFree(p); }
-  static int sync(hipStream_t st) { return (int)hipStreamSynchronize(st); }
-};
-typedef DevBuf<HipMem> DevMem;
 hipError_t reserve(DevMem& b, size_t bytes, hipStream_t st, bool* grew = nullptr) { return (hipError_t)b.reserve(bytes, st, grew); }
 
 // Scene uploads go through a non-blocking stream of the calling thread: a plain hipMemcpy runs on
@@ -206,6 +58,17 @@ int upload(const std::vector<T>& v, void** dptr)
   return DT_OK;
 }
 
+}  // namespace
+
+namespace dth {
+void set_error(const std::string& e) { g_err = e; }
+
+int fail(int code, const std::string& msg)
+{
+  g_err = msg;
+  return code;
+}
+
 int max_resident_waves(const void* kernel_fn, int block)
 {
   int dev = 0;
@@ -217,93 +80,7 @@ int max_resident_waves(const void* kernel_fn, int block)
     per_cu = 1;
   return per_cu * prop.multiProcessorCount;
 }
-
-}  // namespace
-
-namespace dth {
-void set_error(const std::string& e) { g_err = e; }
 }  // namespace dth
-
-struct dt_scene {
-  int device = 0;
-  FlatScene flat;
-  void* d_nodes = nullptr;
-  void* d_fnodes = nullptr;
-  int n_fnodes = 0;
-  void* d_bnodes = nullptr;    // bump tree for motion-blur passes (0 nodes: they walk the reference tree)
-  void* d_bparent = nullptr;
-  int n_bnodes = 0;
-  float bump_pad = 0;          // y padding of its leaves: the largest |shift| a blur pass can draw
-  bool bump_up_only = false;   // bump tree / blur-padded lists built for shifts >= 0 only
-  bool no_cull = false;        // a RectPrismWithCylinder: no t-culling, no grid, no primary lists
-  unsigned features = ~0u;     // the scene's feature mask (dt_scene_dev.h): which builds can render it
-  int kernel = DT_KERNEL_AUTO; // dt_scene_set_kernel
-  ShadowGrid sg;
-  void* d_sg_cells = nullptr;
-  void* d_sg_list = nullptr;
-  void* d_sub_nodes = nullptr;    // shadow-grid block subtrees (ShadowGrid::sub_*)
-  void* d_sub_blocks = nullptr;
-  int ftree_mode = 0;
-  int boxes_ordered = 0;   // lb <= ub on every axis of every node (both trees), no NaN bound
-  void* d_leaf = nullptr;
-  void* d_hdr = nullptr;
-  void* d_geom = nullptr;
-  void* d_mat = nullptr;
-  void* d_lights = nullptr;
-  void* d_tex = nullptr;
-  // the cloud z table (2048 floats); like every DevMem below grown by the launch that needs it
-  // (host_launch.h DevBuf: a failed allocation leaves it empty, so the next launch allocates again)
-  DevMem zs;
-  // ST_N counters + queue word (+ the stamps builds' slots), twice: launches alternate between the
-  // two (parity), and each zeroes the other for the next one (HScene::clear0)
-  unsigned long long* d_stats = nullptr;
-  int n_launch = 0;     // trace launches enqueued (the parity of the next: n_launch & 1)
-  int last_parity = 0;  // the parity of the last one (dt_collect_stats)
-  // the launch record's device copy, one per parity, uploaded only when its bytes changed (a still
-  // frame rendered again uploads nothing: no copy kernel between its launches)
-  void* d_launch = nullptr;
-  std::vector<uint8_t> rec_last[2], rec2_last[2];
-  std::vector<uint8_t> zs_last;   // the z table in zs
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t ev_copy = nullptr;   // staging buffers may be rewritten once this has fired
-  uint8_t* h_launch = nullptr;    // pinned staging for the launch record
-  float* h_zs = nullptr;          // pinned staging for the cloud z sequence
-  bool copy_pending = false;
-  bool timed = false;
-  bool launched = false;   // a trace launch was enqueued (may still read device-side lists)
-  bool uploaded = false;   // dt_scene_upload ran (dt_scene_prepare builds on the host only)
-  bool pl_dirty = false;   // the host primary lists changed since their last upload
-  Accel acc;               // host acceleration structures until the upload
-  // primary-ray candidate lists, rebuilt when the camera / resolution changes (host_primlists.cpp)
-  std::vector<dtd::DNodeDev> fnodes_host, bnodes_host;
-  std::vector<std::vector<P3>> fhull, bhull;   // leaf hull points per fast / bump tree node (host_hull.cpp)
-  bool pl_bump = false;                        // lists for the blur passes follow the pass-0 lists
-  std::vector<double> pl_key;
-  DevMem sky_miss;   // 1-spp launches: missed-pixel flags (dt_sky_miss_kernel clears them)
-  // sky items (dt_kernels.hip DT_SKY_AGAIN): the list a still build leaves to its *_sky build, that
-  // launch's record (pinned staging h_launch2, guarded by ev_copy like h_launch) and its counters
-  DevMem again;
-  void* d_launch2 = nullptr;
-  uint8_t* h_launch2 = nullptr;
-  unsigned long long* d_stats2 = nullptr;   // ST_N counters + queue word + list count, twice (parity)
-  bool again_used = false;                  // the last render ran the second launch
-  DevMem dn_pool;      // dt_trace_kernel_dn: DT_DN_POOL_REC work-sharing records per wave
-  DevMem chunk_cols;   // chunk items: spp sample colours (double) per pixel item
-  DevMem item_cost;    // DT_ITEM_COSTS=1 (diagnostic builds): per-item durations (uint32_t),
-  int64_t item_cost_n = 0;   // of the last launch that recorded them
-  PrimLists pl;
-  bool pl_ok = false;
-  void* d_pl_cells = nullptr;
-  void* d_pl_list = nullptr;
-  dtd::DParams last;
-  int last_px_samples = 0;   // samples per pixel of the last launch: spp, or a window's end - begin
-  // adaptive window launches (dt_render_window_adaptive): the selection's buffers in one allocation
-  // (the list's length, the list, the per-wave offsets and keep bits; adapt_layout); ev_sel fires
-  // when the selection kernels have run (dt_adapt_select_ms)
-  DevMem adapt;
-  hipEvent_t ev_sel = nullptr;
-  bool last_adaptive = false;   // the last launch ran over the selection's list: stats.pixels is its length
-};
 
 extern "C" {
 
@@ -371,12 +148,7 @@ void dt_globals_default(dt_globals* g)
   g->seed = 0;
 }
 
-static int prepare_render(const dt_scene* sc, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
-                          dtd::DParams& P, std::vector<float>& zs);
-static int update_primary_lists(dt_scene* sc, dtd::DParams& P, bool upload_now);
 static int upload_primary_lists(dt_scene* sc);
-
-static int scene_upload(dt_scene* s);
 
 // Host half of dt_scene_create: flatten, BVH, acceleration structures, hulls and the primary-ray
 // lists for the globals' camera. No device work, so it can run on a worker thread beside a render
@@ -478,7 +250,7 @@ static void release_device(dt_scene* s)
 
 // Device half: allocations and uploads of everything dt_scene_prepare built (a few ms). On a
 // failure everything allocated so far is released, so the next render's lazy upload retries cleanly.
-static int scene_upload(dt_scene* s)
+extern "C++" int scene_upload(dt_scene* s)
 {
   if (s->uploaded) return DT_OK;
   const FlatScene& f = s->flat;
@@ -665,8 +437,8 @@ int64_t dt_slab_floats_max(const dt_globals* g, const dt_tiles* tiles)
   return dt_slab_floats(g, &t);
 }
 
-static int prepare_render(const dt_scene* sc, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
-                          dtd::DParams& P, std::vector<float>& zs)
+extern "C++" int prepare_render(const dt_scene* sc, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
+                                dtd::DParams& P, std::vector<float>& zs)
 {
   std::string err;
   int rc = fill_params(*g, frame, tiles, P, err);
@@ -723,7 +495,7 @@ static int prepare_render(const dt_scene* sc, const dt_globals* g, int32_t frame
 // Primary-ray candidate lists for P's camera (DT_PRIM_LISTS=0 disables them; DT_PL_BLOCK: pixels
 // per block side, default 8). Rebuilt only when the camera or resolution changes; the device copy
 // is replaced after the device has drained, since earlier launches may still read it.
-static int update_primary_lists(dt_scene* sc, dtd::DParams& P, bool upload_now)
+extern "C++" int update_primary_lists(dt_scene* sc, dtd::DParams& P, bool upload_now)
 {
   P.pl_block = P.pl_nbx = P.pl_nby = P.pl_bump = 0;
   const char* e = getenv("DT_PRIM_LISTS");
@@ -796,7 +568,7 @@ static int upload_primary_lists(dt_scene* sc)
 
 // the device pointers of a scene's uploaded structures, as the kernels' DScene sees them; every
 // other field zero (enqueue_render sets the pointers its launch uses and leaves the rest null)
-static void fill_hscene(const dt_scene* sc, HScene& hs)
+extern "C++" void fill_hscene(const dt_scene* sc, HScene& hs)
 {
   memset(&hs, 0, sizeof(hs));
   hs.nodes = sc->d_nodes;
@@ -1518,811 +1290,6 @@ int dt_resolve_adaptive(const dt_globals* g, const dt_tiles* tiles, const double
   (void)hipFree(d_nan);
   if (e != hipSuccess) return fail(DT_E_NO_DEVICE, std::string("dt_resolve_adaptive: ") + hipGetErrorString(e));
   *nan_pixels = h_nan;
-  return DT_OK;
-}
-
-// One synchronous launch of an auxiliary kernel (the Makefile's AUX_BUILDS: the intersection benchmark, the
-// feature buffers, the mattes, the ray queries). The launch record, the counters and the two events are
-// the call's own, so it may run beside renders of the same scene on other streams. The caller checks its
-// arguments and calls prepare_render; then begin(), plane() per array, start(), the kernel's launch
-// wrapper as finish()'s argument. Everything is released on every return path, after the stream's work
-// that may use it; the record's host bytes live as long.
-struct AuxLaunch {
-  hipStream_t st;
-  void* launch = nullptr;                     // the launch record on the device
-  unsigned long long* counters = nullptr;     // device: ST_N counters, the queue word, begin()'s `extra` words
-  std::vector<unsigned long long> h;          // ... as finish() read them back
-  float kernel_ms = 0;
-
-  explicit AuxLaunch(void* stream) : st((hipStream_t)stream) {}
-  AuxLaunch(const AuxLaunch&) = delete;
-  ~AuxLaunch()
-  {
-    if (!bufs.empty()) (void)hipStreamSynchronize(st);
-    for (void* b : bufs) (void)hipFree(b);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-
-  // The scene on the device and the record of (scene, P) with zeroed counters of the call's own.
-  // primary_lists: the launch shoots P's camera rays and shares the scene's primary-ray lists; without
-  // them (rays that are not the camera's) the lists are neither read nor rebuilt.
-  int begin(dt_scene* sc, dtd::DParams& P, bool primary_lists, int extra = 0)
-  {
-    if (int rc = scene_upload(sc)) return rc;
-    if (primary_lists) {
-      if (int rc = update_primary_lists(sc, P, true)) return rc;
-    } else {
-      P.pl_block = P.pl_nbx = P.pl_nby = P.pl_bump = 0;
-    }
-    h.assign(ST_N + 1 + extra, 0);
-    void* d = nullptr;
-    if (int rc = alloc(dt_launch_size(), &launch)) return rc;
-    if (int rc = alloc(h.size() * sizeof(h[0]), &d)) return rc;
-    counters = (unsigned long long*)d;
-    HIPCHK(hipMemsetAsync(counters, 0, h.size() * sizeof(h[0]), st));
-    HScene hs;
-    fill_hscene(sc, hs);
-    if (!primary_lists) hs.pl_cells = hs.pl_list = nullptr;
-    hs.stats = counters;
-    hs.queue = hs.stats + ST_N;
-    record.assign(dt_launch_size(), 0);
-    memcpy(record.data() + dt_scene_struct_offset(), &hs, sizeof(hs));
-    memcpy(record.data() + dt_params_struct_offset(), &P, sizeof(P));
-    HIPCHK(hipMemcpyAsync(launch, record.data(), record.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    return DT_OK;
-  }
-
-  // The same without a scene (dt_camera_rays: a kernel that reads the record's parameters only): the record
-  // of P with a zeroed scene, and counters nobody adds to, so that finish() stays as it is.
-  int begin_sceneless(const dtd::DParams& P)
-  {
-    h.assign(ST_N + 1, 0);
-    void* d = nullptr;
-    if (int rc = alloc(dt_launch_size(), &launch)) return rc;
-    if (int rc = alloc(h.size() * sizeof(h[0]), &d)) return rc;
-    counters = (unsigned long long*)d;
-    HIPCHK(hipMemsetAsync(counters, 0, h.size() * sizeof(h[0]), st));
-    record.assign(dt_launch_size(), 0);
-    memcpy(record.data() + dt_params_struct_offset(), &P, sizeof(P));
-    HIPCHK(hipMemcpyAsync(launch, record.data(), record.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    return DT_OK;
-  }
-
-  // The device side of one of the caller's arrays: p itself when it is null or on the device, else a
-  // temporary of `bytes`, holding p's bytes first (copy_in) and copied back to p by finish() (copy_out).
-  int plane(const void* p, size_t bytes, bool on_device, bool copy_in, bool copy_out, void** dev)
-  {
-    *dev = const_cast<void*>(p);
-    if (!p || on_device) return DT_OK;
-    if (int rc = alloc(bytes, dev)) return rc;
-    if (copy_in) HIPCHK(hipMemcpyAsync(*dev, p, bytes, hipMemcpyHostToDevice, st));
-    if (copy_out) back.push_back({const_cast<void*>(p), *dev, bytes});
-    return DT_OK;
-  }
-
-  int start()
-  {
-    HIPCHK(hipEventRecord(e0, st));
-    return DT_OK;
-  }
-
-  // after the launch: the staged arrays and the counters back, the stream drained, the kernel's time
-  int finish(hipError_t launched)
-  {
-    if (launched != hipSuccess)
-      return fail(DT_E_NO_DEVICE, std::string("auxiliary kernel launch: ") + hipGetErrorString(launched));
-    HIPCHK(hipEventRecord(e1, st));
-    for (const Back& b : back) HIPCHK(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(h.data(), counters, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipEventElapsedTime(&kernel_ms, e0, e1));
-    return DT_OK;
-  }
-
- private:
-  struct Back {
-    void *host, *dev;
-    size_t bytes;
-  };
-  std::vector<void*> bufs;
-  std::vector<Back> back;
-  std::vector<uint8_t> record;   // the launch record's host bytes
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-
-  int alloc(size_t bytes, void** dev)
-  {
-    HIPCHK(hipMalloc(dev, bytes));
-    bufs.push_back(*dev);
-    return DT_OK;
-  }
-};
-
-// the grid of a persistent launch over `work` items or waves: the kernel's resident waves at the most
-// (cached by the caller per kernel), one block at the least
-static int aux_grid(const void* kernel_fn, int& resident, int64_t work)
-{
-  if (!resident) resident = max_resident_waves(kernel_fn, 64);
-  const int grid = (int)(work < resident ? work : resident);
-  return grid > 0 ? grid : 1;
-}
-
-// prepare_render for the whole image on one rank
-static int prepare_whole(const dt_scene* sc, const dt_globals* g, int32_t frame, dtd::DParams& P)
-{
-  std::vector<float> zs;
-  dt_tiles whole;
-  memset(&whole, 0, sizeof(whole));
-  whole.world = 1;
-  return prepare_render(sc, g, frame, &whole, P, zs);
-}
-
-// the pixels a launch over P's items produces: the owned tiles' pixels inside the window (pixel_of's `valid`)
-static uint64_t owned_pixels(const dtd::DParams& P)
-{
-  uint64_t pixels = 0;
-  for (int64_t slot = 0; slot < P.n_owned_tiles; ++slot) {
-    const int64_t t = dtd::tile_of(slot, P.rank, P.world);
-    if (t >= P.n_tiles) continue;
-    const int ty = (int)(t / P.tiles_x), tx = (int)(t - (int64_t)ty * P.tiles_x);
-    const int xa = P.x0 + tx * P.tw, ya = P.y0 + ty * P.th;
-    const int xb = xa + P.tw < P.x1 ? xa + P.tw : P.x1, yb = ya + P.th < P.y1 ? ya + P.th : P.y1;
-    if (xb > xa && yb > ya) pixels += (uint64_t)(xb - xa) * (uint64_t)(yb - ya);
-  }
-  return pixels;
-}
-
-// Intersection micro-benchmark: dt_isect_kernel over rays first_ray .. first_ray+n_rays-1
-// of the globals' camera.
-int dt_intersect_primary(const dt_scene* sc_c, const dt_globals* g, int32_t frame, int64_t first_ray, int64_t n_rays,
-                         int32_t* hit_shape, float* hit_t, int32_t out_on_device, void* stream, float* kernel_ms)
-{
-  dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  if (!sc || !g || !hit_shape || !hit_t) return fail(DT_E_INVALID, "null argument");
-  if (first_ray < 0 || n_rays < 0) return fail(DT_E_INVALID, "negative ray range");
-  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_intersect_primary: scenes with a RectPrismWithCylinder");
-  if (n_rays == 0) {
-    if (kernel_ms) *kernel_ms = 0;
-    return DT_OK;
-  }
-  dtd::DParams P;
-  if (int rc = prepare_whole(sc, g, frame, P)) return rc;
-  AuxLaunch aux(stream);
-  if (int rc = aux.begin(sc, P, true)) return rc;
-  void *dshape = nullptr, *dt_ = nullptr;
-  if (int rc = aux.plane(hit_shape, (size_t)n_rays * sizeof(int32_t), out_on_device, false, true, &dshape)) return rc;
-  if (int rc = aux.plane(hit_t, (size_t)n_rays * sizeof(float), out_on_device, false, true, &dt_)) return rc;
-  static int resident = 0;
-  const int grid = aux_grid(dt_isect_kernel_ptr(), resident, (n_rays + 63) / 64);
-  if (int rc = aux.start()) return rc;
-  if (int rc = aux.finish(dt_launch_isect(aux.launch, first_ray, n_rays, (int32_t*)dshape, (float*)dt_, grid, aux.st)))
-    return rc;
-  if (kernel_ms) *kernel_ms = aux.kernel_ms;
-  return DT_OK;
-}
-
-// Camera rays as arrays: dt_camera_rays_kernel over the rows of (g, tiles, the sample range). The camera is
-// fill_params' (the renders'), no scene is involved: the launch record holds the parameters alone.
-static int camera_rays_check(const char* who, const dt_globals* g, const dt_tiles* tiles, int32_t sample_begin,
-                             int32_t sample_end, int32_t frame, dtd::DParams& P, int64_t& n_rows)
-{
-  const std::string w = std::string(who) + ": ";
-  if (!g) return fail(DT_E_INVALID, w + "null globals");
-  if (!(0 <= sample_begin && sample_begin < sample_end && sample_end - sample_begin <= DT_CAMERA_RAYS_MAX_SAMPLES))
-    return fail(DT_E_INVALID, w + "samples [" + std::to_string(sample_begin) + "," + std::to_string(sample_end) +
-                                  "): need 0 <= sample_begin < sample_end, at most " +
-                                  std::to_string(DT_CAMERA_RAYS_MAX_SAMPLES) + " samples");
-  std::string err;
-  if (int rc = fill_params(*g, frame, tiles, P, err)) return fail(rc, w + "globals or tiles: " + err);
-  const int64_t slots = P.layout == DT_OUT_SLAB ? P.n_owned_tiles * P.tw * P.th : (int64_t)P.xRes * P.yRes;
-  n_rows = slots * (sample_end - sample_begin);
-  return DT_OK;
-}
-
-int64_t dt_camera_rays_rows(const dt_globals* g, const dt_tiles* tiles, int32_t sample_begin, int32_t sample_end)
-{
-  dtd::DParams P;
-  int64_t n_rows = 0;
-  if (camera_rays_check("dt_camera_rays_rows", g, tiles, sample_begin, sample_end, 0, P, n_rows)) return -1;
-  return n_rows;
-}
-
-int dt_camera_rays(const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t sample_begin, int32_t sample_end,
-                   double* start, double* dir, int32_t on_device, void* stream, float* kernel_ms)
-{
-  if (g && !start) return fail(DT_E_INVALID, "dt_camera_rays: null start");
-  if (g && !dir) return fail(DT_E_INVALID, "dt_camera_rays: null dir");
-  dtd::DParams P;
-  int64_t n_rows = 0;
-  if (int rc = camera_rays_check("dt_camera_rays", g, tiles, sample_begin, sample_end, frame, P, n_rows)) return rc;
-  AuxLaunch aux(stream);
-  if (int rc = aux.begin_sceneless(P)) return rc;
-  // host arrays are staged through device copies of the caller's arrays: unowned rows go back as they came
-  void *dstart = nullptr, *ddir = nullptr;
-  const size_t bytes = (size_t)n_rows * 3 * sizeof(double);
-  if (int rc = aux.plane(start, bytes, on_device, true, true, &dstart)) return rc;
-  if (int rc = aux.plane(dir, bytes, on_device, true, true, &ddir)) return rc;
-  if (int rc = aux.start()) return rc;
-  if (int rc = aux.finish(dt_launch_camera_rays(aux.launch, sample_begin, sample_end - sample_begin, n_rows,
-                                                (double*)dstart, (double*)ddir, aux.st)))
-    return rc;
-  if (kernel_ms) *kernel_ms = aux.kernel_ms;
-  return DT_OK;
-}
-
-// First-hit feature buffers: dt_features_kernel over the samples 0 .. n_samples-1 of every owned pixel.
-// It shares only the scene's primary-ray lists. Every argument check comes before the scene is looked at.
-// Specular-path feature buffers (dt_render_features_path, `path`): the same call with
-// dt_features_path_kernel, max_bounces and one more plane; its errors carry its own prefix.
-static int render_features_common(bool path, const dt_scene* sc_c, const dt_globals* g, int32_t frame,
-                                  const dt_tiles* tiles, int32_t n_samples, int32_t max_bounces, const dt_features* out,
-                                  float* bounces, int32_t out_on_device, void* stream, dt_stats* stats)
-{
-  dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  const std::string who = path ? "dt_render_features_path: " : "dt_render_features: ";
-  if (!sc) return fail(DT_E_INVALID, who + "null scene");
-  if (!g) return fail(DT_E_INVALID, who + "null globals");
-  if (!out) return fail(DT_E_INVALID, who + "null planes");
-  if (!out->albedo && !out->normal && !out->depth && !out->coverage && !out->shape && !bounces)
-    return fail(DT_E_INVALID, who + "no plane wanted (every pointer is null)");
-  if (int rc = dt_window_check(g, 0, n_samples)) return path ? fail(rc, who + "n_samples: " + g_err) : rc;
-  if (path && (max_bounces < 0 || max_bounces > DT_GUIDE_MAX_BOUNCES))
-    return fail(DT_E_INVALID, who + "max_bounces must be in 0.." + std::to_string(DT_GUIDE_MAX_BOUNCES) + ", got " +
-                                  std::to_string(max_bounces));
-  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, who + "scenes with a RectPrismWithCylinder");
-  dtd::DParams P;
-  std::vector<float> zs;
-  if (int rc = prepare_render(sc, g, frame, tiles, P, zs)) return rc;
-  AuxLaunch aux(stream);
-  if (int rc = aux.begin(sc, P, true)) return rc;
-  // the planes' lengths (dt_accum_doubles). Host planes are staged through device copies of the caller's
-  // arrays: the entries of pixels this rank does not own go back as they came
-  const size_t n3 = P.layout == DT_OUT_SLAB ? (size_t)(P.n_owned_tiles * P.tw * P.th * 3) : (size_t)3 * P.xRes * P.yRes;
-  const size_t n1 = n3 / 3;
-  void* host[6] = {out->albedo, out->normal, out->depth, out->coverage, out->shape, bounces};
-  void* dev[6];
-  const size_t bytes[6] = {n3 * sizeof(float), n3 * sizeof(float), n1 * sizeof(float),
-                           n1 * sizeof(float), n1 * sizeof(int32_t), n1 * sizeof(float)};
-  for (int k = 0; k < 6; ++k)
-    if (int rc = aux.plane(host[k], bytes[k], out_on_device, true, true, &dev[k])) return rc;
-  static int resident_first = 0, resident_path = 0;
-  const int grid = path ? aux_grid(dt_features_path_kernel_ptr(), resident_path, P.n_items)
-                        : aux_grid(dt_features_kernel_ptr(), resident_first, P.n_items);
-  if (int rc = aux.start()) return rc;
-  const hipError_t launched =
-      path ? dt_launch_features_path(aux.launch, n_samples, max_bounces, (float*)dev[0], (float*)dev[1], (float*)dev[2],
-                                     (float*)dev[3], (int32_t*)dev[4], (float*)dev[5], grid, aux.st)
-           : dt_launch_features(aux.launch, n_samples, (float*)dev[0], (float*)dev[1], (float*)dev[2], (float*)dev[3],
-                                (int32_t*)dev[4], grid, aux.st);
-  if (int rc = aux.finish(launched)) return rc;
-  if (stats) {
-    memset(stats, 0, sizeof(*stats));
-    stats->pixels = owned_pixels(P);
-    stats->samples = stats->pixels * (uint64_t)n_samples;
-    stats->rays = path ? aux.h[ST_RAYS] : stats->samples;   // path: the segments traced
-    if (path) stats->reflect_errors = aux.h[ST_REFL];
-    stats->tex_fetches = aux.h[ST_TEX];
-    stats->uv_out_of_range = aux.h[ST_UV];
-    stats->prism_norm_fallback = aux.h[ST_PRISM];
-    stats->kernel_ms = aux.kernel_ms;
-  }
-  return DT_OK;
-}
-
-int dt_render_features(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t n_samples,
-                       const dt_features* out, int32_t out_on_device, void* stream, dt_stats* stats)
-{
-  return render_features_common(false, s, g, frame, tiles, n_samples, 0, out, nullptr, out_on_device, stream, stats);
-}
-
-int dt_render_features_path(const dt_scene* s, const dt_globals* g, int32_t frame, const dt_tiles* tiles,
-                            int32_t n_samples, int32_t max_bounces, const dt_features* out, float* bounces,
-                            int32_t out_on_device, void* stream, dt_stats* stats)
-{
-  return render_features_common(true, s, g, frame, tiles, n_samples, max_bounces, out, bounces, out_on_device, stream,
-                                stats);
-}
-
-// The bounce rule of dt_render_features_path for one hit (dt_guide.h), for tests and callers.
-int dt_guide_bounce(const dt_globals* g, int32_t material, uint32_t flags, int32_t inside, const double in[3],
-                    const double n[3], const double p[3], double next_dir[3], double next_start[3])
-{
-  if (!g || !in || !n || !p || !next_dir || !next_start) return fail(DT_E_INVALID, "dt_guide_bounce: null argument");
-  dtm::V3 nd = dtm::v3(0, 0, 0), ns = dtm::v3(0, 0, 0);
-  bool refl_err = false;
-  const int rc = dtd::guide_bounce(g->reflect, g->nogloss, g->refr_air, g->refr_glass, material, flags, inside,
-                                   dtm::v3a(in), dtm::v3a(n), dtm::v3a(p), nd, ns, refl_err);
-  if (rc != dtd::DT_GUIDE_STOP) {
-    next_dir[0] = nd.x; next_dir[1] = nd.y; next_dir[2] = nd.z;
-    next_start[0] = ns.x; next_start[1] = ns.y; next_start[2] = ns.z;
-  }
-  return rc;
-}
-
-// Object mattes: dt_mattes_kernel over the samples 0 .. n_samples-1 of every owned pixel. As
-// dt_render_features it shares only the scene's primary-ray lists. Every argument check, the map's
-// entries included, comes before any device work.
-int dt_render_mattes(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t n_samples,
-                     const int32_t* group_of_shape, int32_t n_shapes, int32_t layers, const dt_mattes* out,
-                     int32_t out_on_device, void* stream, dt_stats* stats, uint64_t* overflow_pixels)
-{
-  dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  if (!sc) return fail(DT_E_INVALID, "dt_render_mattes: null scene");
-  if (!g) return fail(DT_E_INVALID, "dt_render_mattes: null globals");
-  if (!out) return fail(DT_E_INVALID, "dt_render_mattes: null out");
-  if (!out->id && !out->weight && !out->distinct)
-    return fail(DT_E_INVALID, "dt_render_mattes: out wants no plane (every pointer is null)");
-  if (int rc = dt_window_check(g, 0, n_samples)) return fail(rc, "dt_render_mattes: n_samples: " + g_err);
-  if (layers < 1 || layers > DT_MATTE_MAX_LAYERS)
-    return fail(DT_E_INVALID, "dt_render_mattes: layers " + std::to_string(layers) + " outside 1.." +
-                                  std::to_string(DT_MATTE_MAX_LAYERS));
-  if (n_shapes < 0) return fail(DT_E_INVALID, "dt_render_mattes: n_shapes " + std::to_string(n_shapes) + " is negative");
-  if (group_of_shape)
-    for (int32_t i = 0; i < n_shapes; ++i)
-      if (group_of_shape[i] < 0)
-        return fail(DT_E_INVALID, "dt_render_mattes: group_of_shape[" + std::to_string(i) + "] is negative");
-  // (the scene is looked at only from here on)
-  if ((size_t)n_shapes != sc->flat.hdr.size())
-    return fail(DT_E_INVALID, "dt_render_mattes: n_shapes " + std::to_string(n_shapes) + ", the scene has " +
-                                  std::to_string(sc->flat.hdr.size()) + " shapes");
-  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_render_mattes: scenes with a RectPrismWithCylinder");
-  dtd::DParams P;
-  std::vector<float> zs;
-  if (int rc = prepare_render(sc, g, frame, tiles, P, zs)) return rc;
-  AuxLaunch aux(stream);
-  if (int rc = aux.begin(sc, P, true, /*extra: the overflow count*/ 1)) return rc;
-  void* map = nullptr;
-  if (n_shapes > 0)
-    if (int rc = aux.plane(group_of_shape, (size_t)n_shapes * sizeof(int32_t), false, true, false, &map)) return rc;
-  // the planes, staged as dt_render_features stages its own
-  const size_t n1 = P.layout == DT_OUT_SLAB ? (size_t)(P.n_owned_tiles * P.tw * P.th) : (size_t)P.xRes * P.yRes;
-  void* host[3] = {out->id, out->weight, out->distinct};
-  void* dev[3];
-  const size_t bytes[3] = {n1 * layers * sizeof(int32_t), n1 * layers * sizeof(float), n1 * sizeof(int32_t)};
-  for (int k = 0; k < 3; ++k)
-    if (int rc = aux.plane(host[k], bytes[k], out_on_device, true, true, &dev[k])) return rc;
-  static int resident = 0;
-  const int grid = aux_grid(dt_mattes_kernel_ptr(), resident, P.n_items);
-  if (int rc = aux.start()) return rc;
-  if (int rc = aux.finish(dt_launch_mattes(aux.launch, n_samples, (const int32_t*)map, layers, (int32_t*)dev[0],
-                                           (float*)dev[1], (int32_t*)dev[2], aux.counters + ST_N + 1, grid, aux.st)))
-    return rc;
-  if (overflow_pixels) *overflow_pixels = aux.h[ST_N + 1];
-  if (stats) {
-    memset(stats, 0, sizeof(*stats));
-    stats->pixels = owned_pixels(P);
-    stats->samples = stats->pixels * (uint64_t)n_samples;
-    stats->rays = stats->samples;
-    stats->kernel_ms = aux.kernel_ms;
-  }
-  return DT_OK;
-}
-
-// Ray queries (dt_trace_rays, dt_rays_occluded): dt_rayq_kernel / dt_rayq_occl_kernel over rays the caller
-// hands over. A query takes only the traversal parameters from g (prepare_render; the camera it fills in
-// is not read): it neither reads nor rebuilds the scene's primary-ray lists, and a render afterwards
-// finds the scene as it was.
-int dt_trace_rays(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
-                  const dt_ray_hits* out, int32_t on_device, void* stream, dt_stats* stats)
-{
-  dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  if (!sc) return fail(DT_E_INVALID, "dt_trace_rays: null scene");
-  if (!g) return fail(DT_E_INVALID, "dt_trace_rays: null globals");
-  if (!start) return fail(DT_E_INVALID, "dt_trace_rays: null start");
-  if (!dir) return fail(DT_E_INVALID, "dt_trace_rays: null dir");
-  if (!out) return fail(DT_E_INVALID, "dt_trace_rays: null out");
-  if (!out->shape && !out->t && !out->point && !out->normal && !out->albedo)
-    return fail(DT_E_INVALID, "dt_trace_rays: out wants no plane (every pointer is null)");
-  if (n_rays < 0) return fail(DT_E_INVALID, "dt_trace_rays: n_rays < 0");
-  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_trace_rays: scenes with a RectPrismWithCylinder");
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (n_rays == 0) return DT_OK;
-  dtd::DParams P;
-  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
-  AuxLaunch aux(stream);
-  if (int rc = aux.begin(sc, P, false)) return rc;
-  const size_t n = (size_t)n_rays;
-  void *dstart = nullptr, *ddir = nullptr;
-  if (int rc = aux.plane(start, 3 * n * sizeof(double), on_device, true, false, &dstart)) return rc;
-  if (int rc = aux.plane(dir, 3 * n * sizeof(double), on_device, true, false, &ddir)) return rc;
-  void* host[5] = {out->shape, out->t, out->point, out->normal, out->albedo};
-  void* dev[5];
-  const size_t bytes[5] = {n * sizeof(int32_t), n * sizeof(float), 3 * n * sizeof(double), 3 * n * sizeof(double),
-                           3 * n * sizeof(double)};
-  for (int k = 0; k < 5; ++k)
-    if (int rc = aux.plane(host[k], bytes[k], on_device, false, true, &dev[k])) return rc;
-  static int resident = 0;
-  const int grid = aux_grid(dt_rayq_kernel_ptr(), resident, (n_rays + 63) / 64);
-  if (int rc = aux.start()) return rc;
-  if (int rc = aux.finish(dt_launch_rayq(aux.launch, n_rays, (const double*)dstart, (const double*)ddir, (int32_t*)dev[0],
-                                         (float*)dev[1], (double*)dev[2], (double*)dev[3], (double*)dev[4], grid, aux.st)))
-    return rc;
-  if (stats) {
-    stats->rays = aux.h[ST_RAYS];
-    stats->tex_fetches = aux.h[ST_TEX];
-    stats->uv_out_of_range = aux.h[ST_UV];
-    stats->prism_norm_fallback = aux.h[ST_PRISM];
-    stats->kernel_ms = aux.kernel_ms;
-  }
-  return DT_OK;
-}
-
-// dt_trace_rays_multi: dt_rayq_multi_kernel in the smallest list capacity (1, 2, 4, 8) that holds k; the
-// resident waves are cached per capacity, as each is a kernel of its own
-int dt_trace_rays_multi(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, const double* start,
-                        const double* dir, int32_t k, const dt_ray_multihits* out, int32_t on_device, void* stream,
-                        dt_stats* stats)
-{
-  dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  if (!sc) return fail(DT_E_INVALID, "dt_trace_rays_multi: null scene");
-  if (!g) return fail(DT_E_INVALID, "dt_trace_rays_multi: null globals");
-  if (!start) return fail(DT_E_INVALID, "dt_trace_rays_multi: null start");
-  if (!dir) return fail(DT_E_INVALID, "dt_trace_rays_multi: null dir");
-  if (!out) return fail(DT_E_INVALID, "dt_trace_rays_multi: null out");
-  if (!out->count && !out->shape && !out->t && !out->point && !out->normal && !out->albedo)
-    return fail(DT_E_INVALID, "dt_trace_rays_multi: out wants no plane (every pointer is null)");
-  if (n_rays < 0) return fail(DT_E_INVALID, "dt_trace_rays_multi: n_rays < 0");
-  if (k < 1 || k > DT_MULTIHIT_MAX)
-    return fail(DT_E_INVALID, "dt_trace_rays_multi: k = " + std::to_string(k) + " outside 1.." +
-                                  std::to_string(DT_MULTIHIT_MAX));
-  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_trace_rays_multi: scenes with a RectPrismWithCylinder");
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (n_rays == 0) return DT_OK;
-  dtd::DParams P;
-  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
-  AuxLaunch aux(stream);
-  if (int rc = aux.begin(sc, P, false)) return rc;
-  const size_t n = (size_t)n_rays, nk = n * (size_t)k;
-  void *dstart = nullptr, *ddir = nullptr;
-  if (int rc = aux.plane(start, 3 * n * sizeof(double), on_device, true, false, &dstart)) return rc;
-  if (int rc = aux.plane(dir, 3 * n * sizeof(double), on_device, true, false, &ddir)) return rc;
-  void* host[6] = {out->count, out->shape, out->t, out->point, out->normal, out->albedo};
-  void* dev[6];
-  const size_t bytes[6] = {n * sizeof(int32_t),      nk * sizeof(int32_t),     nk * sizeof(float),
-                           3 * nk * sizeof(double),  3 * nk * sizeof(double),  3 * nk * sizeof(double)};
-  for (int p = 0; p < 6; ++p)
-    if (int rc = aux.plane(host[p], bytes[p], on_device, false, true, &dev[p])) return rc;
-  static int resident[4] = {0, 0, 0, 0};   // per capacity 1, 2, 4, 8
-  const int slot = k <= 1 ? 0 : k <= 2 ? 1 : k <= 4 ? 2 : 3;
-  const int grid = aux_grid(dt_rayq_multi_kernel_ptr(k), resident[slot], (n_rays + 63) / 64);
-  if (int rc = aux.start()) return rc;
-  if (int rc = aux.finish(dt_launch_rayq_multi(aux.launch, n_rays, (const double*)dstart, (const double*)ddir, k,
-                                               (int32_t*)dev[0], (int32_t*)dev[1], (float*)dev[2], (double*)dev[3],
-                                               (double*)dev[4], (double*)dev[5], grid, aux.st)))
-    return rc;
-  if (stats) {
-    stats->rays = aux.h[ST_RAYS];
-    stats->tex_fetches = aux.h[ST_TEX];
-    stats->uv_out_of_range = aux.h[ST_UV];
-    stats->prism_norm_fallback = aux.h[ST_PRISM];
-    stats->kernel_ms = aux.kernel_ms;
-  }
-  return DT_OK;
-}
-
-int dt_rays_occluded(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
-                     const int32_t* skip_shape, uint8_t* occluded, int32_t on_device, void* stream, dt_stats* stats)
-{
-  dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  if (!sc) return fail(DT_E_INVALID, "dt_rays_occluded: null scene");
-  if (!g) return fail(DT_E_INVALID, "dt_rays_occluded: null globals");
-  if (!start) return fail(DT_E_INVALID, "dt_rays_occluded: null start");
-  if (!dir) return fail(DT_E_INVALID, "dt_rays_occluded: null dir");
-  if (!occluded) return fail(DT_E_INVALID, "dt_rays_occluded: null occluded");
-  if (n_rays < 0) return fail(DT_E_INVALID, "dt_rays_occluded: n_rays < 0");
-  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, "dt_rays_occluded: scenes with a RectPrismWithCylinder");
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (n_rays == 0) return DT_OK;
-  dtd::DParams P;
-  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
-  AuxLaunch aux(stream);
-  if (int rc = aux.begin(sc, P, false)) return rc;
-  const size_t n = (size_t)n_rays;
-  void *dstart = nullptr, *ddir = nullptr, *dskip = nullptr, *docc = nullptr;
-  if (int rc = aux.plane(start, 3 * n * sizeof(double), on_device, true, false, &dstart)) return rc;
-  if (int rc = aux.plane(dir, 3 * n * sizeof(double), on_device, true, false, &ddir)) return rc;
-  if (int rc = aux.plane(skip_shape, n * sizeof(int32_t), on_device, true, false, &dskip)) return rc;
-  if (int rc = aux.plane(occluded, n, on_device, false, true, &docc)) return rc;
-  static int resident = 0;
-  const int grid = aux_grid(dt_rayq_occl_kernel_ptr(), resident, (n_rays + 63) / 64);
-  if (int rc = aux.start()) return rc;
-  if (int rc = aux.finish(dt_launch_rayq_occl(aux.launch, n_rays, (const double*)dstart, (const double*)ddir,
-                                              (const int32_t*)dskip, (uint8_t*)docc, grid, aux.st)))
-    return rc;
-  if (stats) {
-    stats->shadow_rays = aux.h[ST_SHADOW];
-    stats->kernel_ms = aux.kernel_ms;
-  }
-  return DT_OK;
-}
-
-// dt_rays_transmittance: dt_rayq_transmit_kernel in the smallest list capacity (0, 1, 2, 4, 8) that holds the
-// pane ids wanted (0 without out->pane_shape); the resident waves are cached per capacity, as each is a kernel
-// of its own
-int dt_rays_transmittance(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, const double* start,
-                          const double* dir, const int32_t* skip_shape, int32_t k, const dt_ray_transmittance* out,
-                          int32_t on_device, void* stream, dt_stats* stats)
-{
-  dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  const std::string who = "dt_rays_transmittance: ";
-  if (!sc) return fail(DT_E_INVALID, who + "null scene");
-  if (!g) return fail(DT_E_INVALID, who + "null globals");
-  if (!start) return fail(DT_E_INVALID, who + "null start");
-  if (!dir) return fail(DT_E_INVALID, who + "null dir");
-  if (!out) return fail(DT_E_INVALID, who + "null out");
-  if (!out->panes && !out->pane_shape) return fail(DT_E_INVALID, who + "out wants no plane (every pointer is null)");
-  if (n_rays < 0) return fail(DT_E_INVALID, who + "n_rays < 0");
-  if (k < 0 || k > DT_TRANSMIT_MAX_PANES)
-    return fail(DT_E_INVALID, who + "k = " + std::to_string(k) + " outside 0.." + std::to_string(DT_TRANSMIT_MAX_PANES));
-  if (out->pane_shape && k == 0) return fail(DT_E_INVALID, who + "out->pane_shape given with k == 0");
-  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, who + "scenes with a RectPrismWithCylinder");
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (n_rays == 0) return DT_OK;
-  dtd::DParams P;
-  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
-  AuxLaunch aux(stream);
-  if (int rc = aux.begin(sc, P, false)) return rc;
-  const size_t n = (size_t)n_rays;
-  void *dstart = nullptr, *ddir = nullptr, *dskip = nullptr, *dpanes = nullptr, *dshape = nullptr;
-  if (int rc = aux.plane(start, 3 * n * sizeof(double), on_device, true, false, &dstart)) return rc;
-  if (int rc = aux.plane(dir, 3 * n * sizeof(double), on_device, true, false, &ddir)) return rc;
-  if (int rc = aux.plane(skip_shape, n * sizeof(int32_t), on_device, true, false, &dskip)) return rc;
-  if (int rc = aux.plane(out->panes, n * sizeof(int32_t), on_device, false, true, &dpanes)) return rc;
-  if (int rc = aux.plane(out->pane_shape, n * (size_t)k * sizeof(int32_t), on_device, false, true, &dshape)) return rc;
-  static int resident[5] = {0, 0, 0, 0, 0};   // per capacity 0, 1, 2, 4, 8
-  const int cap_k = out->pane_shape ? k : 0;
-  const int slot = cap_k <= 0 ? 0 : cap_k <= 1 ? 1 : cap_k <= 2 ? 2 : cap_k <= 4 ? 3 : 4;
-  const int grid = aux_grid(dt_rayq_transmit_kernel_ptr(cap_k), resident[slot], (n_rays + 63) / 64);
-  if (int rc = aux.start()) return rc;
-  if (int rc = aux.finish(dt_launch_rayq_transmit(aux.launch, n_rays, (const double*)dstart, (const double*)ddir,
-                                                  (const int32_t*)dskip, k, (int32_t*)dpanes, (int32_t*)dshape, grid,
-                                                  aux.st)))
-    return rc;
-  if (stats) {
-    stats->shadow_rays = aux.h[ST_SHADOW];
-    stats->kernel_ms = aux.kernel_ms;
-  }
-  return DT_OK;
-}
-
-// Occlusion feature buffers: dt_occlusion_kernel over the samples 0 .. n_samples-1 of every owned pixel. As
-// dt_render_features it shares only the scene's primary-ray lists. Every argument check, the light indices
-// included, comes before any device work. The lights' records (dt_occl.h OcclLight, from the scene's flattened
-// lights) travel with the launch.
-void dt_occlusion_params_default(dt_occlusion_params* p)
-{
-  if (!p) return;
-  memset(p, 0, sizeof(*p));
-  p->ao_rays = 4;
-  p->ao_radius = 1.0f;   // one world unit (include/dt.h: a choice, not a measurement)
-}
-
-// The rules dt_render_occlusion and dt_points_occlusion share for params and out (both non-null), under the
-// caller's prefix: the counts and the radius, planes given without their count, every plane NULL, then (the
-// scene is looked at only from there on) the light indices and the RectPrismWithCylinder rule.
-static int check_occlusion(const std::string& who, const dt_scene* sc, const dt_occlusion_params* params,
-                           const dt_occlusion* out)
-{
-  if (params->ao_rays < 0 || params->ao_rays > DT_OCCL_MAX_AO_RAYS)
-    return fail(DT_E_INVALID, who + "ao_rays " + std::to_string(params->ao_rays) + " outside 0.." +
-                                  std::to_string(DT_OCCL_MAX_AO_RAYS));
-  if (params->n_lights < 0 || params->n_lights > DT_OCCL_MAX_LIGHTS)
-    return fail(DT_E_INVALID, who + "n_lights " + std::to_string(params->n_lights) + " outside 0.." +
-                                  std::to_string(DT_OCCL_MAX_LIGHTS));
-  if (params->ao_rays > 0 && !(std::isfinite(params->ao_radius) && params->ao_radius > 0))
-    return fail(DT_E_INVALID, who + "ao_radius must be finite and > 0");
-  if (out->ao && params->ao_rays == 0) return fail(DT_E_INVALID, who + "out->ao given with ao_rays == 0");
-  if (out->light && params->n_lights == 0) return fail(DT_E_INVALID, who + "out->light given with n_lights == 0");
-  if (!out->ao && !out->light) return fail(DT_E_INVALID, who + "out wants no plane (every pointer is null)");
-  // (the scene is looked at only from here on)
-  const int32_t scene_lights = (int32_t)sc->flat.lights.size();
-  for (int32_t j = 0; j < params->n_lights; ++j)
-    if (params->lights[j] < 0 || params->lights[j] >= scene_lights)
-      return fail(DT_E_INVALID, who + "lights[" + std::to_string(j) + "] = " + std::to_string(params->lights[j]) +
-                                    ", the scene has " + std::to_string(scene_lights) + " lights");
-  if (sc->no_cull) return fail(DT_E_UNSUPPORTED, who + "scenes with a RectPrismWithCylinder");
-  return DT_OK;
-}
-
-// the records of the chosen lights that travel with a launch (dt_occl.h OcclLight, from the scene's flattened lights)
-static void occlusion_lights(const dt_scene* sc, const dt_occlusion_params* params, int n_lights,
-                             dtd::OcclLight recs[DT_OCCL_MAX_LIGHTS])
-{
-  memset(recs, 0, sizeof(dtd::OcclLight) * DT_OCCL_MAX_LIGHTS);
-  for (int j = 0; j < n_lights; ++j) {
-    const dtd::DLight& L = sc->flat.lights[params->lights[j]];
-    dtd::OcclLight& o = recs[j];
-    o.type = L.type;
-    o.shape_index = L.shape_index;
-    o.radius = L.radius;
-    for (int k = 0; k < 3; ++k) { o.center[k] = L.center[k]; o.A[k] = L.A[k]; o.B[k] = L.B[k]; o.D[k] = L.D[k]; }
-  }
-}
-
-int dt_render_occlusion(const dt_scene* sc_c, const dt_globals* g, int32_t frame, const dt_tiles* tiles, int32_t n_samples,
-                        const dt_occlusion_params* params, const dt_occlusion* out, int32_t out_on_device, void* stream,
-                        dt_stats* stats)
-{
-  dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  const std::string who = "dt_render_occlusion: ";
-  if (!sc) return fail(DT_E_INVALID, who + "null scene");
-  if (!g) return fail(DT_E_INVALID, who + "null globals");
-  if (!params) return fail(DT_E_INVALID, who + "null params");
-  if (!out) return fail(DT_E_INVALID, who + "null out");
-  if (int rc = dt_window_check(g, 0, n_samples)) return fail(rc, who + "n_samples: " + g_err);
-  if (int rc = check_occlusion(who, sc, params, out)) return rc;
-  // a plane that is not wanted costs no probes
-  const int ao_rays = out->ao ? params->ao_rays : 0, n_lights = out->light ? params->n_lights : 0;
-  dtd::DParams P;
-  std::vector<float> zs;
-  if (int rc = prepare_render(sc, g, frame, tiles, P, zs)) return rc;
-  AuxLaunch aux(stream);
-  if (int rc = aux.begin(sc, P, true)) return rc;
-  dtd::OcclLight recs[DT_OCCL_MAX_LIGHTS];
-  occlusion_lights(sc, params, n_lights, recs);
-  void* dlights = nullptr;
-  if (n_lights > 0)
-    if (int rc = aux.plane(recs, sizeof(recs), false, true, false, &dlights)) return rc;
-  // the planes, staged as dt_render_features stages its own
-  const size_t n1 = P.layout == DT_OUT_SLAB ? (size_t)(P.n_owned_tiles * P.tw * P.th) : (size_t)P.xRes * P.yRes;
-  void *dao = nullptr, *dlight = nullptr;
-  if (int rc = aux.plane(out->ao, n1 * sizeof(float), out_on_device, true, true, &dao)) return rc;
-  if (int rc = aux.plane(out->light, n1 * (size_t)params->n_lights * sizeof(float), out_on_device, true, true, &dlight))
-    return rc;
-  static int resident = 0;
-  const int grid = aux_grid(dt_occlusion_kernel_ptr(), resident, P.n_items);
-  if (int rc = aux.start()) return rc;
-  if (int rc = aux.finish(dt_launch_occlusion(aux.launch, n_samples, ao_rays, params->ao_radius, n_lights, dlights,
-                                              (float*)dao, (float*)dlight, grid, aux.st)))
-    return rc;
-  if (stats) {
-    memset(stats, 0, sizeof(*stats));
-    stats->pixels = owned_pixels(P);
-    stats->samples = stats->pixels * (uint64_t)n_samples;
-    stats->rays = stats->samples;
-    stats->shadow_rays = aux.h[ST_SHADOW];
-    stats->prism_norm_fallback = aux.h[ST_PRISM];
-    stats->kernel_ms = aux.kernel_ms;
-  }
-  return DT_OK;
-}
-
-// Occlusion queries at surface points: dt_points_occl_kernel over the caller's points, one lane per point. As a
-// ray query it takes only the traversal parameters from g (prepare_whole at frame 0, as dt_rays_occluded, so
-// that a probe is answered as that call answers it); the RNG key (g->seed, frame) travels as kernel
-// arguments. It neither reads nor rebuilds the primary-ray lists.
-//
-// dt_points_occlusion_glass is the same call with dt_points_occl_glass_kernel (glass: max_panes and the optional
-// pane planes; a row of probes runs for either of its two planes).
-static int points_occlusion_common(bool glass, const dt_scene* sc_c, const dt_globals* g, int32_t frame, int64_t n_points,
-                                   const double* point, const double* normal, int32_t n_samples,
-                                   const dt_occlusion_params* params, int32_t max_panes, const dt_occlusion* out,
-                                   const dt_occlusion_panes* panes, int32_t on_device, void* stream, dt_stats* stats)
-{
-  dt_scene* sc = const_cast<dt_scene*>(sc_c);
-  const std::string who = glass ? "dt_points_occlusion_glass: " : "dt_points_occlusion: ";
-  if (!sc) return fail(DT_E_INVALID, who + "null scene");
-  if (!g) return fail(DT_E_INVALID, who + "null globals");
-  if (!point) return fail(DT_E_INVALID, who + "null point");
-  if (!normal) return fail(DT_E_INVALID, who + "null normal");
-  if (!params) return fail(DT_E_INVALID, who + "null params");
-  if (!out) return fail(DT_E_INVALID, who + "null out");
-  if (n_points < 0) return fail(DT_E_INVALID, who + "n_points < 0");
-  if (n_points >= (int64_t)1 << 32) return fail(DT_E_INVALID, who + "n_points >= 2^32 (a point is the RNG counter's pixel)");
-  if (n_samples < 1 || n_samples > DT_POCCL_MAX_SAMPLES)
-    return fail(DT_E_INVALID, who + "n_samples " + std::to_string(n_samples) + " outside 1.." +
-                                  std::to_string(DT_POCCL_MAX_SAMPLES));
-  if (glass) {
-    if (max_panes < 0 || max_panes > DT_TRANSMIT_MAX_PANES)
-      return fail(DT_E_INVALID, who + "max_panes " + std::to_string(max_panes) + " outside 0.." +
-                                    std::to_string(DT_TRANSMIT_MAX_PANES));
-    if (panes && panes->ao_panes && params->ao_rays == 0)
-      return fail(DT_E_INVALID, who + "panes->ao_panes given with ao_rays == 0");
-    if (panes && panes->light_panes && params->n_lights == 0)
-      return fail(DT_E_INVALID, who + "panes->light_panes given with n_lights == 0");
-  }
-  if (int rc = check_occlusion(who, sc, params, out)) return rc;
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (n_points == 0) return DT_OK;
-  // a plane that is not wanted costs no probes
-  float* const ao_panes = glass && panes ? panes->ao_panes : nullptr;
-  float* const light_panes = glass && panes ? panes->light_panes : nullptr;
-  const int ao_rays = (out->ao || ao_panes) ? params->ao_rays : 0;
-  const int n_lights = (out->light || light_panes) ? params->n_lights : 0;
-  dtd::DParams P;
-  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
-  AuxLaunch aux(stream);
-  if (int rc = aux.begin(sc, P, false)) return rc;
-  dtd::OcclLight recs[DT_OCCL_MAX_LIGHTS];
-  occlusion_lights(sc, params, n_lights, recs);
-  void* dlights = nullptr;
-  if (n_lights > 0)
-    if (int rc = aux.plane(recs, sizeof(recs), false, true, false, &dlights)) return rc;
-  const size_t n = (size_t)n_points;
-  void *dpoint = nullptr, *dnormal = nullptr, *dao = nullptr, *dlight = nullptr;
-  if (int rc = aux.plane(point, 3 * n * sizeof(double), on_device, true, false, &dpoint)) return rc;
-  if (int rc = aux.plane(normal, 3 * n * sizeof(double), on_device, true, false, &dnormal)) return rc;
-  if (int rc = aux.plane(out->ao, n * sizeof(float), on_device, false, true, &dao)) return rc;
-  if (int rc = aux.plane(out->light, n * (size_t)params->n_lights * sizeof(float), on_device, false, true, &dlight))
-    return rc;
-  if (glass) {
-    void *daop = nullptr, *dlp = nullptr;
-    if (int rc = aux.plane(ao_panes, n * sizeof(float), on_device, false, true, &daop)) return rc;
-    if (int rc = aux.plane(light_panes, n * (size_t)params->n_lights * sizeof(float), on_device, false, true, &dlp))
-      return rc;
-    static int resident_glass = 0;
-    const int grid = aux_grid(dt_points_occl_glass_kernel_ptr(), resident_glass, (n_points + 63) / 64);
-    if (int rc = aux.start()) return rc;
-    if (int rc = aux.finish(dt_launch_points_occl_glass(aux.launch, (uint32_t)g->seed, frame, n_points,
-                                                        (const double*)dpoint, (const double*)dnormal, n_samples, ao_rays,
-                                                        params->ao_radius, n_lights, dlights, max_panes, (float*)dao,
-                                                        (float*)dlight, (float*)daop, (float*)dlp, grid, aux.st)))
-      return rc;
-  } else {
-    static int resident = 0;
-    const int grid = aux_grid(dt_points_occl_kernel_ptr(), resident, (n_points + 63) / 64);
-    if (int rc = aux.start()) return rc;
-    if (int rc = aux.finish(dt_launch_points_occl(aux.launch, (uint32_t)g->seed, frame, n_points, (const double*)dpoint,
-                                                  (const double*)dnormal, n_samples, ao_rays, params->ao_radius, n_lights,
-                                                  dlights, (float*)dao, (float*)dlight, grid, aux.st)))
-      return rc;
-  }
-  if (stats) {
-    stats->shadow_rays = aux.h[ST_SHADOW];
-    stats->kernel_ms = aux.kernel_ms;
-  }
-  return DT_OK;
-}
-
-int dt_points_occlusion(const dt_scene* s, const dt_globals* g, int32_t frame, int64_t n_points, const double* point,
-                        const double* normal, int32_t n_samples, const dt_occlusion_params* params,
-                        const dt_occlusion* out, int32_t on_device, void* stream, dt_stats* stats)
-{
-  return points_occlusion_common(false, s, g, frame, n_points, point, normal, n_samples, params, 0, out, nullptr,
-                                 on_device, stream, stats);
-}
-
-int dt_points_occlusion_glass(const dt_scene* s, const dt_globals* g, int32_t frame, int64_t n_points, const double* point,
-                              const double* normal, int32_t n_samples, const dt_occlusion_params* params,
-                              int32_t max_panes, const dt_occlusion* out, const dt_occlusion_panes* panes,
-                              int32_t on_device, void* stream, dt_stats* stats)
-{
-  return points_occlusion_common(true, s, g, frame, n_points, point, normal, n_samples, params, max_panes, out, panes,
-                                 on_device, stream, stats);
-}
-
-// The two probe generators of dt_render_occlusion for one hit (dt_occl.h), for tests and callers.
-int dt_occlusion_ao_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint32_t sample, int32_t r, float ao_radius,
-                        const double p[3], const double n[3], double dir[3])
-{
-  if (!p || !n || !dir) return fail(DT_E_INVALID, "dt_occlusion_ao_ray: null argument");
-  if (r < 0 || r >= DT_OCCL_MAX_AO_RAYS)
-    return fail(DT_E_INVALID, "dt_occlusion_ao_ray: r " + std::to_string(r) + " outside 0.." +
-                                  std::to_string(DT_OCCL_MAX_AO_RAYS - 1));
-  const dtm::V3 d = dtd::occl_ao_dir(seed, frame, pixel, sample, r, ao_radius, dtm::v3a(n));
-  dir[0] = d.x; dir[1] = d.y; dir[2] = d.z;
-  return DT_OK;
-}
-
-int dt_occlusion_light_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint32_t sample, int32_t j,
-                           const dt_light_desc* light, const double p[3], double dir[3])
-{
-  if (!light || !p || !dir) return fail(DT_E_INVALID, "dt_occlusion_light_ray: null argument");
-  if (j < 0 || j >= DT_OCCL_MAX_LIGHTS)
-    return fail(DT_E_INVALID, "dt_occlusion_light_ray: j " + std::to_string(j) + " outside 0.." +
-                                  std::to_string(DT_OCCL_MAX_LIGHTS - 1));
-  dtd::OcclLight o;
-  memset(&o, 0, sizeof(o));
-  o.type = light->type;
-  o.shape_index = light->shape_index;
-  o.radius = (double)light->radius;
-  for (int k = 0; k < 3; ++k) { o.center[k] = light->center[k]; o.A[k] = light->A[k]; o.B[k] = light->B[k]; o.D[k] = light->D[k]; }
-  const dtm::V3 d = dtd::occl_light_dir(seed, frame, pixel, sample, j, o, dtm::v3a(p));
-  dir[0] = d.x; dir[1] = d.y; dir[2] = d.z;
   return DT_OK;
 }
 

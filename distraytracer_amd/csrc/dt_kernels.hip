@@ -26,6 +26,7 @@
 #include "dt_math.h"
 #include "dt_scene_dev.h"
 #include "dt_adapt.h"
+#include "dt_kernel_iface.h"
 
 using namespace dtm;
 using namespace dtd;
