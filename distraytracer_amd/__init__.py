@@ -15,6 +15,7 @@ an error (there is no CPU path in this package).
 import ctypes
 
 from ._lib import (DATA_DIR, DT_KERNEL_AUTO, DT_KERNEL_DONATE, DT_KERNEL_PRODUCT, DT_OUT_IMAGE, DT_OUT_SLAB, AccelInfo, BVHNode, Camera, DenoiseParams, DenoiseVarParams, DTError, Globals, SceneDesc,
+                   DT_PATH_CUT, DT_PATH_MISS, DT_PATH_SURFACE, DT_PATH_VOID,
                    SHAPE_TYPES, OcclusionParams, RayOrderParams, DT_RAY_ORDER_TILE, Stats, TemporalParams, Tiles, UpsampleParams, check, lib)
 
 __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_scene", "Scene",
@@ -30,6 +31,8 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "trace_rays", "rays_occluded", "RAY_PLANES",
            "trace_rays_multi", "segment_through_glass", "RAY_MULTI_PLANES",
            "rays_transmittance", "RAY_TRANSMIT_PLANES",
+           "trace_rays_path", "ray_polyline", "pick", "RAY_PATH_PLANES",
+           "DT_PATH_VOID", "DT_PATH_MISS", "DT_PATH_SURFACE", "DT_PATH_CUT",
            "camera_rays", "camera_rays_rows", "rays_resolve", "peel_layers", "RESOLVE_MODES",
            "RayOrderParams", "RayOrder", "ray_order_params_default", "ray_order_key", "ray_order", "DT_RAY_ORDER_TILE",
            "render_mattes", "matte_mask", "shape_groups", "MATTE_PLANES",
@@ -944,6 +947,99 @@ def rays_transmittance(scene, g, start, dir, skip_shape=None, k=0, order=None, p
                                     ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)),
           "dt_rays_transmittance")
     return out, st
+
+
+RAY_PATH_PLANES = ("end", "segments", "shape", "length", "point", "normal", "albedo", "last_start", "last_dir",
+                   "seg_shape", "seg_point")
+# plane -> (torch dtype, numpy dtype, values per entry, per segment)
+_RAY_PATH_TYPES = {"end": ("torch.int32", "int32", 1, False), "segments": ("torch.int32", "int32", 1, False),
+                   "shape": ("torch.int32", "int32", 1, False), "length": ("torch.float64", "float64", 1, False),
+                   "point": ("torch.float64", "float64", 3, False), "normal": ("torch.float64", "float64", 3, False),
+                   "albedo": ("torch.float64", "float64", 3, False),
+                   "last_start": ("torch.float64", "float64", 3, False),
+                   "last_dir": ("torch.float64", "float64", 3, False),
+                   "seg_shape": ("torch.int32", "int32", 1, True), "seg_point": ("torch.float64", "float64", 3, True)}
+
+
+def trace_rays_path(scene, g, start, dir, max_bounces=4, planes=("end", "segments", "shape", "point"), order=None,
+                    stream=None):
+    """Caller-supplied rays followed through mirrors and glass (include/dt.h dt_trace_rays_path): start and dir as
+    for trace_rays, max_bounces in 0..8. Every ray runs render_features' specular-path chain (guide_bounce) with
+    itself as segment 0. Returns (paths, stats): paths is a dict plane name -> array on the side of start for the
+    planes asked for: end (int32: DT_PATH_VOID, _MISS, _SURFACE, _CUT), segments (int32, the segments traced),
+    shape (int32, the shape the path ended on, -1: none), length (float64, the whole path's), point, normal,
+    albedo (float64 (n, 3): the terminal hit's, zeros unless the path ended on a shape), last_start, last_dir
+    (float64 (n, 3): the ray of the last segment traced), and per segment seg_shape (int32 (n, max_bounces+1),
+    -1: not traced or a miss) and seg_point (float64 (n, max_bounces+1, 3)). paths["start"] is the caller's start
+    as (n, 3), for ray_polyline. `order` as for trace_rays (True, or a RayOrder of these rays): the same bits.
+    Geometry only: glossy reflectors (nogloss = 0) stop the chain, glass follows transmission, no Fresnel weights."""
+    what = "trace_rays_path"
+    n, sp, dp, side = _ray_arrays(what, start, dir)
+    from ._lib import DT_RAY_PATH_MAX_BOUNCES, RayPaths
+    K = max_bounces
+    if isinstance(K, bool) or not isinstance(K, int) or not 0 <= K <= DT_RAY_PATH_MAX_BOUNCES:
+        raise DTError("%s: max_bounces must be an integer in 0..%d, not %r" % (what, DT_RAY_PATH_MAX_BOUNCES, K))
+    for name in planes:
+        if name not in RAY_PATH_PLANES:
+            raise DTError("%s: unknown plane %r" % (what, name))
+
+    def new(name):
+        tt, nt, per, seg = _RAY_PATH_TYPES[name]
+        return _ray_new(start, (n,) + ((K + 1,) if seg else ()) + ((3,) if per == 3 else ()), tt, nt)
+
+    out = {name: new(name) for name in planes}
+    if order is not None:
+        order = _order_for(what, order, start, dir, n, side, stream)
+        tmp, st = trace_rays_path(scene, g, order.apply(start), order.apply(dir), max_bounces=K, planes=planes,
+                                  stream=stream)
+        for name, a in out.items():
+            row = _numel_any(a) * (a.element_size() if hasattr(a, "data_ptr") else a.itemsize) // n if n else 1
+            if row <= 64:
+                order.restore(tmp[name], out=a)
+            else:
+                _restore_wide(order, tmp[name], a)
+    else:
+        h = RayPaths()
+        for name, a in out.items():
+            setattr(h, name, _data_ptr(a))
+        st = Stats()
+        check(lib.dt_trace_rays_path(scene.handle, ctypes.byref(g), n, sp, dp, K, ctypes.byref(h), side,
+                                     ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)),
+              "dt_trace_rays_path")
+    out["start"] = start.reshape(n, 3)
+    return out, st
+
+
+def ray_polyline(paths, i):
+    """The vertices of ray i of trace_rays_path's answer (which must hold seg_shape and seg_point): its start,
+    then the hit point of every segment that hit a shape, in order -- a float64 numpy array (m, 3), m >= 1. A
+    path that ended as a miss leaves along paths["last_dir"] from its last vertex."""
+    import numpy as np
+    for name in ("seg_shape", "seg_point", "start"):
+        if name not in paths:
+            raise DTError("ray_polyline: paths holds no %r (ask trace_rays_path for seg_shape and seg_point)" % name)
+
+    def host(a):
+        return a.cpu().numpy() if hasattr(a, "data_ptr") else np.asarray(a)
+
+    shape, point = host(paths["seg_shape"][i]), host(paths["seg_point"][i])
+    return np.concatenate([host(paths["start"][i]).reshape(1, 3), point[shape >= 0].reshape(-1, 3)]).astype(np.float64)
+
+
+def pick(scene, g, frame, x, y, max_bounces=4):
+    """What the pixel (x, y) of the frame shows, mirrors and panes followed: sample 0's camera ray of the pixel
+    (camera_rays; x from the left, y from the top, as in the written images) through trace_rays_path with every
+    plane. Returns (paths, stats) of that one ray: paths["shape"][0] is the shape seen, ray_polyline(paths, 0) the
+    way there. Only that pixel's camera ray is made (a one-pixel window of camera_rays; the arrays it fills are
+    the frame's)."""
+    x, y = int(x), int(y)
+    if not (0 <= x < g.xRes and 0 <= y < g.yRes):
+        raise DTError("pick: pixel (%d, %d) outside the %d x %d frame" % (x, y, g.xRes, g.yRes))
+    py = g.yRes - 1 - y   # the window counts rows from the bottom, the image's slots from the top
+    start, dir = camera_rays(g, frame, samples=(0, 1), tile=tiles(x0=x, y0=py, x1=x + 1, y1=py + 1))
+    q = y * g.xRes + x
+    return trace_rays_path(scene, g, start[q, 0].reshape(1, 3).contiguous(), dir[q, 0].reshape(1, 3).contiguous(),
+                           max_bounces=max_bounces, planes=RAY_PATH_PLANES)
 
 
 def segment_through_glass(scene, desc, g, start, dir, k=8):

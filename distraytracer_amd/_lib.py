@@ -150,6 +150,18 @@ class RayTransmittance(ctypes.Structure):
     _fields_ = [("panes", ctypes.c_void_p), ("pane_shape", ctypes.c_void_p)]
 
 
+DT_RAY_PATH_MAX_BOUNCES = 8   # the largest max_bounces of dt_trace_rays_path (== DT_GUIDE_MAX_BOUNCES)
+DT_PATH_VOID, DT_PATH_MISS, DT_PATH_SURFACE, DT_PATH_CUT = 0, 1, 2, 3   # how a path ended (include/dt.h)
+
+
+class RayPaths(ctypes.Structure):
+    """dt_ray_paths: the planes of dt_trace_rays_path (a null pointer: not wanted)"""
+    _fields_ = [("end", ctypes.c_void_p), ("segments", ctypes.c_void_p), ("shape", ctypes.c_void_p),
+                ("length", ctypes.c_void_p), ("point", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("albedo", ctypes.c_void_p), ("last_start", ctypes.c_void_p), ("last_dir", ctypes.c_void_p),
+                ("seg_shape", ctypes.c_void_p), ("seg_point", ctypes.c_void_p)]
+
+
 class OcclusionPanes(ctypes.Structure):
     """dt_occlusion_panes: the pane planes of dt_points_occlusion_glass (a null pointer: not wanted)"""
     _fields_ = [("ao_panes", ctypes.c_void_p), ("light_panes", ctypes.c_void_p)]
@@ -245,7 +257,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_permute_rows",
            "dt_trace_rays_multi",
            "dt_camera_rays_rows", "dt_camera_rays", "dt_rays_resolve",
-           "dt_rays_transmittance", "dt_points_occlusion_glass"]
+           "dt_rays_transmittance", "dt_points_occlusion_glass",
+           "dt_trace_rays_path"]
 
 
 class DTError(RuntimeError):
@@ -350,6 +363,8 @@ def _load():
         "dt_rays_transmittance": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, c_int32, P(RayTransmittance), c_int32, ctypes.c_void_p,
                                             P(Stats)]),
+        "dt_trace_rays_path": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, ctypes.c_void_p, c_int32,
+                                         P(RayPaths), c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_points_occlusion_glass": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, c_int64, ctypes.c_void_p,
                                                 ctypes.c_void_p, c_int32, P(OcclusionParams), c_int32, P(Occlusion),
                                                 P(OcclusionPanes), c_int32, ctypes.c_void_p, P(Stats)]),

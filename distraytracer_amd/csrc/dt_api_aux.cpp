@@ -560,6 +560,52 @@ int dt_rays_transmittance(const dt_scene* sc_c, const dt_globals* g, int64_t n_r
   return DT_OK;
 }
 
+// dt_trace_rays_path: dt_rayq_path_kernel over the caller's rays, a ray query as dt_trace_rays is one; the
+// per-segment planes hold max_bounces + 1 entries per ray. The kernel takes the planes' device side in a
+// dt_ray_paths of its own.
+int dt_trace_rays_path(const dt_scene* sc_c, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
+                       int32_t max_bounces, const dt_ray_paths* out, int32_t on_device, void* stream, dt_stats* stats)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  const std::string who = "dt_trace_rays_path: ";
+  if (int rc = query_pointers(who, sc, g, "start", start, "dir", dir)) return rc;
+  if (!out) return fail(DT_E_INVALID, who + "null out");
+  void* const host[11] = {out->end,    out->segments, out->shape,      out->length,   out->point,    out->normal,
+                          out->albedo, out->last_start, out->last_dir, out->seg_shape, out->seg_point};
+  bool wanted = false;
+  for (void* p : host) wanted = wanted || p;
+  if (!wanted) return fail(DT_E_INVALID, who + "out wants no plane (every pointer is null)");
+  if (n_rays < 0) return fail(DT_E_INVALID, who + "n_rays < 0");
+  if (max_bounces < 0 || max_bounces > DT_RAY_PATH_MAX_BOUNCES)
+    return fail(DT_E_INVALID, who + "max_bounces must be in 0.." + std::to_string(DT_RAY_PATH_MAX_BOUNCES) + ", got " +
+                                  std::to_string(max_bounces));
+  bool done;
+  if (int rc = query_ready(who, sc, n_rays, stats, &done); rc || done) return rc;
+  dtd::DParams P;
+  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, false)) return rc;
+  const size_t n = (size_t)n_rays, ns = n * (size_t)(max_bounces + 1);
+  const double *dstart = nullptr, *ddir = nullptr;
+  if (int rc = aux.plane_pair(start, dir, n, on_device, &dstart, &ddir)) return rc;
+  const size_t i32 = sizeof(int32_t), f64 = sizeof(double);
+  const size_t bytes[11] = {n * i32,     n * i32,     n * i32,     n * f64,  3 * n * f64,  3 * n * f64,
+                            3 * n * f64, 3 * n * f64, 3 * n * f64, ns * i32, 3 * ns * f64};
+  void* dev[11];
+  for (int p = 0; p < 11; ++p)
+    if (int rc = aux.plane(host[p], bytes[p], on_device, false, true, &dev[p])) return rc;
+  const dt_ray_paths planes = {(int32_t*)dev[0], (int32_t*)dev[1], (int32_t*)dev[2], (double*)dev[3],
+                               (double*)dev[4],  (double*)dev[5],  (double*)dev[6],  (double*)dev[7],
+                               (double*)dev[8],  (int32_t*)dev[9], (double*)dev[10]};
+  if (int rc = aux.run(dt_rayq_path_kernel_ptr(), (n_rays + 63) / 64, [&](int grid) {
+        return dt_launch_rayq_path(aux.launch, n_rays, dstart, ddir, max_bounces, &planes, grid, aux.st);
+      }))
+    return rc;
+  aux.hit_stats(stats);
+  if (stats) stats->reflect_errors = aux.h[ST_REFL];
+  return DT_OK;
+}
+
 // Occlusion feature buffers: dt_occlusion_kernel over the samples 0 .. n_samples-1 of every owned pixel. As
 // dt_render_features it shares only the scene's primary-ray lists. Every argument check, the light indices
 // included, comes before any device work. The lights' records (dt_occl.h OcclLight, from the scene's flattened

@@ -86,5 +86,11 @@ extern "C" hipError_t dt_launch_points_occl_glass(const void* dev_launch, uint32
                                                   int max_panes, float* ao, float* light, float* ao_panes,
                                                   float* light_panes, int grid, hipStream_t stream);
 extern "C" const void* dt_points_occl_glass_kernel_ptr(void);
+// planes: include/dt.h dt_ray_paths holding the device side of every plane (null: not wanted)
+struct dt_ray_paths;
+extern "C" hipError_t dt_launch_rayq_path(const void* dev_launch, int64_t n, const double* start, const double* dir,
+                                          int max_bounces, const struct dt_ray_paths* planes, int grid,
+                                          hipStream_t stream);
+extern "C" const void* dt_rayq_path_kernel_ptr(void);
 extern "C" hipError_t dt_launch_camera_rays(const void* dev_launch, int sample_begin, int ns, int64_t n_rows,
                                             double* start, double* dir, hipStream_t stream);

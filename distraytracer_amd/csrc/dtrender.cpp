@@ -65,6 +65,11 @@
 //                     j's coverage-premultiplied albedo times 255 (the mean over the pixel's rays of the
 //                     (j+1)-th surface's albedo, a ray with fewer surfaces adding nothing), as
 //                     distraytracer_amd.peel_layers. Without the flag every byte written is the same as before.
+//   --pick X,Y        after the frame, what pixel (X, Y) shows (X from the left, Y from the top), mirrors and glass
+//                     followed (--pick-bounces K, 0..8, default 4): sample 0's camera ray of the pixel
+//                     (dt_camera_rays) through dt_trace_rays_path, printed one line per segment (k, the shape it
+//                     hit, its material, the point), then the end (void, miss, surface, cut) and the path's
+//                     length L. Without the flag every byte written and printed is the same as before.
 //   --guide-bounces K the feature buffers of --features, --denoise, --denoise-variance and --upsample are the
 //                     specular-path ones (dt_render_features_path, K = 1..8 perfect specular bounces): the
 //                     guides describe what mirrors and glass show, not the reflector. Without it (or with 0)
@@ -276,6 +281,8 @@ int main(int argc, char** argv)
   int peel = 0, peel_samples = 1;
   bool peel_asked = false;
   std::string peel_prefix;
+  int pick_x = -1, pick_y = -1, pick_bounces = 4;
+  bool pick_asked = false, pick_given = false;
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i];
     if (a == "--out" && i + 1 < argc) out = argv[++i];
@@ -315,6 +322,16 @@ int main(int argc, char** argv)
     else if (a == "--peel" && i + 1 < argc) { peel = atoi(argv[++i]); peel_asked = true; }
     else if (a == "--peel-out" && i + 1 < argc) peel_prefix = argv[++i];
     else if (a == "--peel-samples" && i + 1 < argc) peel_samples = atoi(argv[++i]);
+    else if (a == "--pick" && i + 1 < argc) { pick_asked = sscanf(argv[++i], "%d,%d", &pick_x, &pick_y) == 2; pick_given = true; }
+    else if (a == "--pick-bounces" && i + 1 < argc) pick_bounces = atoi(argv[++i]);
+  }
+  if (pick_given && (!pick_asked || pick_bounces < 0 || pick_bounces > DT_RAY_PATH_MAX_BOUNCES)) {
+    fprintf(stderr, "usage: --pick X,Y [--pick-bounces K] needs a pixel and K in 0..%d\n", DT_RAY_PATH_MAX_BOUNCES);
+    return 2;
+  }
+  if (pick_given && mode == "perlin") {
+    fprintf(stderr, "usage: --pick needs a mode that renders a scene (perlin has none)\n");
+    return 2;
   }
   if (guide_bounces < 0 || guide_bounces > DT_GUIDE_MAX_BOUNCES) {
     fprintf(stderr, "usage: --guide-bounces K needs K in 0..%d\n", DT_GUIDE_MAX_BOUNCES);
@@ -387,6 +404,10 @@ int main(int argc, char** argv)
   if (depth > 0) g.max_depth = depth;
   if (nogloss) g.nogloss = 1;
   if (W > 0) { g.xRes = W; g.yRes = H; }
+  if (pick_asked && (pick_x < 0 || pick_x >= g.xRes || pick_y < 0 || pick_y >= g.yRes)) {
+    fprintf(stderr, "usage: --pick %d,%d: outside the %dx%d frame\n", pick_x, pick_y, g.xRes, g.yRes);
+    return 2;
+  }
   if (upsample && (upsample < 2 || upsample > 4 || g.xRes % upsample || g.yRes % upsample)) {
     fprintf(stderr, "usage: --upsample S needs S = 2, 3 or 4 and a resolution that S divides (%dx%d)\n", g.xRes, g.yRes);
     return 2;
@@ -722,6 +743,34 @@ int main(int argc, char** argv)
     }
     printf("peel: %lld rays (%d per pixel), %d layers: rays %.3f ms, hits %.3f ms (kernels) -> %s.layer<j>.png\n",
            (long long)rows, n, K, cam_ms, pst.kernel_ms, peel_prefix.c_str());
+  }
+  if (pick_asked) {
+    const int64_t rows = dt_camera_rays_rows(&g, nullptr, 0, 1);
+    if (rows < 0) return die("dt_camera_rays_rows", (int)rows);
+    std::vector<double> start((size_t)rows * 3, 0.0), dir((size_t)rows * 3, 0.0);
+    rc = dt_camera_rays(&g, frame, nullptr, 0, 1, start.data(), dir.data(), 0, nullptr, nullptr);
+    if (rc) return die("dt_camera_rays", rc);
+    const size_t q = (size_t)pick_y * g.xRes + pick_x;   // the pixel's slot: row 0 is the top row of the image
+    const int K = pick_bounces;
+    int32_t end = 0, segments = 0, seg_shape[DT_RAY_PATH_MAX_BOUNCES + 1];
+    double length = 0, seg_point[3 * (DT_RAY_PATH_MAX_BOUNCES + 1)];
+    dt_ray_paths rp;
+    memset(&rp, 0, sizeof rp);
+    rp.end = &end; rp.segments = &segments; rp.length = &length; rp.seg_shape = seg_shape; rp.seg_point = seg_point;
+    rc = dt_trace_rays_path(s, &g, 1, &start[3 * q], &dir[3 * q], K, &rp, 0, nullptr, nullptr);
+    if (rc) return die("dt_trace_rays_path", rc);
+    for (int k = 0; k < segments; ++k) {
+      const int h = seg_shape[k];
+      if (h < 0) printf("pick %d,%d: segment %d shape -1 material -1 (no hit)\n", pick_x, pick_y, k);
+      else printf("pick %d,%d: segment %d shape %d material %d point %.9g %.9g %.9g\n", pick_x, pick_y, k, h,
+                  desc->shapes[h].material, seg_point[3 * k], seg_point[3 * k + 1], seg_point[3 * k + 2]);
+    }
+    static const char* const ends[4] = {"void", "miss", "surface", "cut"};
+    if (end < DT_PATH_VOID || end > DT_PATH_CUT) {
+      fprintf(stderr, "dt_trace_rays_path returned the end code %d\n", end);
+      return 1;
+    }
+    printf("pick %d,%d: end %s L %.9g\n", pick_x, pick_y, ends[end], length);
   }
   double msps = st.samples / (st.kernel_ms * 1e-3) / 1e6;
   printf("Rendered %s frame %d: %dx%d, %d spp, depth %d in %.2f ms (kernel, %.1f Mpixel-samples/s) -> %s\n",

@@ -82,6 +82,8 @@ extern "C" {
 /* (still 8, new exports and two new structs, no struct changed: dt_rays_transmittance and its
  *    dt_ray_transmittance, dt_points_occlusion_glass and its dt_occlusion_panes -- transmittance queries:
  *    shadow probes that pass through glass) */
+/* (still 8, one new export and one new struct, no struct changed: dt_trace_rays_path and its dt_ray_paths --
+ *    path ray queries: caller-supplied rays followed through mirrors and glass) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -755,6 +757,66 @@ int dt_rays_transmittance(const dt_scene* s, const dt_globals* g, int64_t n_rays
                           const double* dir, const int32_t* skip_shape /* optional, n_rays; -1: none */,
                           int32_t k /* 0..DT_TRANSMIT_MAX_PANES */, const dt_ray_transmittance* out,
                           int32_t on_device, void* stream, dt_stats* stats);
+
+/* ---- path ray queries: caller-supplied rays followed through mirrors and glass ----
+ * No reference counterpart. dt_trace_rays stops at the first surface; dt_render_features_path follows the
+ * render's own camera samples through the scene's perfect reflectors and reports per-pixel means. This call
+ * runs that chain for rays the caller hands over and answers per ray: where the ray ends up after the mirrors
+ * and panes, the vertices on the way, the length of the path. Picking the object seen in a mirror, a polyline
+ * of a ray through the scene's optics, a caller's own next bounce (the last segment's ray is returned, and
+ * `inside` is handled here) start from it. Geometry only: no Fresnel weights, no radiance.
+ * Rays, the void-ray rule, sides and staging, g, synchrony, "a render afterwards is unaffected" and the thread
+ * rule are dt_trace_rays's.
+ *
+ * Per ray, segment k = 0, 1, ... (segment 0 is the caller's ray (dir, start)) -- exactly the per-sample chain of
+ * dt_render_features_path:
+ *   a VOID segment (dt_trace_rays's rule on (dir_k, start_k); tested before every segment, the caller's own
+ *   included) is not traced: the path ends as DT_PATH_VOID. This is the caller's ray, or the successor of
+ *   normal incidence on glass, whose next_dir is not finite (dt_guide_bounce).
+ *   Otherwise the segment is traced to its closest hit as dt_trace_rays specifies it (shift 0, dir
+ *   unnormalised): shape h_k, t_k, inside_k. No hit: the path ends as DT_PATH_MISS. On a hit
+ *     L   = L + (double)t_k * |dir_k|                      (f64, from +0)
+ *     p_k = start_k + (double)t_k * dir_k,   n_k = fixNorm(normalized(dir_k), getNorm(p_k))
+ *   and iff k < max_bounces the bounce rule (dt_guide_bounce) is evaluated at (h_k's material and flags,
+ *   inside_k, normalized(dir_k), n_k, p_k): reflect or refract gives segment k+1 = (next_dir, next_start); stop
+ *   ends the path as DT_PATH_SURFACE on h_k. The hit of segment max_bounces ends it as DT_PATH_CUT on h_k, the
+ *   rule not evaluated. n_k is computed iff k < max_bounces or the normal plane is wanted; the colour
+ *   (dt_render_features's rule at (h_k, p_k)) only at the terminal hit, and only if albedo is wanted.
+ * max_bounces = 0 is dt_trace_rays in shape, point, normal and albedo, and length = (double)t * |dir|.
+ * Every element of every wanted plane is written. The per-segment planes hold max_bounces + 1 entries per ray:
+ * entry (max_bounces+1)*i + k describes segment k of ray i, -1 and zeros where the segment was not traced or
+ * hit nothing.
+ * stats (optional): rays = the segments traced, reflect_errors (the rule's refl_err), prism_norm_fallback (per
+ * normal computed), tex_fetches and uv_out_of_range (the terminal colour only), kernel_ms; everything else 0.
+ *
+ * The walk is dt_trace_rays's wave-uniform one: 64 consecutive rays share a wave, and the wave runs segment k
+ * for the rays still travelling while the others wait. After the first bounce a wave's rays scatter, so a later
+ * segment costs what dt_trace_rays costs on scattered rays (BASELINE.md "Path ray queries").
+ * Limits, as dt_render_features_path: glossy reflectors (DT_F_GLOSSY with nogloss = 0) stop the chain, glass
+ * follows transmission only (total internal reflection takes the mirror rule), never its reflection.
+ *
+ * DT_E_INVALID, with a dt_last_error starting "dt_trace_rays_path: " and naming the argument: a null scene,
+ * globals, start, dir or out, an out with every plane NULL, n_rays < 0, max_bounces outside
+ * 0..DT_RAY_PATH_MAX_BOUNCES; DT_E_UNSUPPORTED: a scene with a RectPrismWithCylinder; all before any device
+ * work. n_rays == 0: DT_OK, nothing is launched. */
+#define DT_RAY_PATH_MAX_BOUNCES 8          /* == DT_GUIDE_MAX_BOUNCES */
+enum { DT_PATH_VOID = 0, DT_PATH_MISS = 1, DT_PATH_SURFACE = 2, DT_PATH_CUT = 3 };
+typedef struct dt_ray_paths {   /* every plane optional (NULL: not wanted), not all NULL; all on one side */
+  int32_t* end;        /* n: one of DT_PATH_* */
+  int32_t* segments;   /* n: segments traced, 0 .. max_bounces+1 (0: the caller's ray was void) */
+  int32_t* shape;      /* n: the shape the path ended on (SURFACE, CUT), else -1 */
+  double*  length;     /* n: L, the f64 sum over the path's hits of (double)t_k * |dir_k|, from +0 */
+  double*  point;      /* 3n: the terminal hit p_k; zeros unless SURFACE or CUT */
+  double*  normal;     /* 3n: the terminal hit's fixNorm'ed normal n_k; zeros unless SURFACE or CUT */
+  double*  albedo;     /* 3n: dt_render_features's colour rule at the terminal hit; zeros unless SURFACE or CUT */
+  double*  last_start; /* 3n: the ray of the last segment traced (zeros when segments == 0) */
+  double*  last_dir;   /* 3n */
+  int32_t* seg_shape;  /* (max_bounces+1) per ray, entry (max_bounces+1)*i + k: the shape segment k hit, else -1 */
+  double*  seg_point;  /* 3 per entry, same indexing: p_k; zeros where seg_shape is -1 */
+} dt_ray_paths;
+int dt_trace_rays_path(const dt_scene* s, const dt_globals* g, int64_t n_rays, const double* start, const double* dir,
+                       int32_t max_bounces /* 0..DT_RAY_PATH_MAX_BOUNCES */, const dt_ray_paths* out,
+                       int32_t on_device, void* stream, dt_stats* stats);
 
 /* ---- multi-hit ray queries: the k nearest surfaces along caller-supplied rays ----
  * No reference counterpart. dt_trace_rays says what a ray hits first; this call says what lies behind it: per
