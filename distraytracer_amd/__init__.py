@@ -38,7 +38,9 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "render_mattes", "matte_mask", "shape_groups", "MATTE_PLANES",
            "UpsampleParams", "upsample_params_default", "upsample", "low_res_globals",
            "OcclusionParams", "occlusion_params_default", "render_occlusion", "occlusion_ao_ray", "occlusion_light_ray",
-           "occlusion_images", "points_occlusion", "shape_texels", "bake_occlusion"]
+           "occlusion_images", "points_occlusion", "shape_texels", "bake_occlusion",
+           "points_irradiance", "irradiance_gather_ray", "irradiance_cosine", "bake_irradiance", "irradiance_images",
+           "IRRADIANCE_PLANES"]
 
 
 def globals_default():
@@ -493,6 +495,99 @@ def bake_occlusion(scene, desc, g, shape_index, width, height, side=1, through_g
         img[keep] = a
         out[name] = img.reshape((int(height), int(width)) + a.shape[1:])
     return out, st
+
+
+IRRADIANCE_PLANES = ("direct", "direct_rgb", "indirect_rgb", "sky")
+
+
+def irradiance_gather_ray(g, frame, pixel, sample, r, point, normal):
+    """Gather probe r of sample `sample` of point `pixel` of points_irradiance (include/dt.h
+    dt_irradiance_gather_ray): (start, dir), two tuples of 3 floats; a void probe has dir (0, 0, 0)"""
+    D3 = ctypes.c_double * 3
+    start, dir = D3(), D3()
+    check(lib.dt_irradiance_gather_ray(g.seed, int(frame), int(pixel), int(sample), int(r),
+                                       D3(*[float(v) for v in point]), D3(*[float(v) for v in normal]), start, dir),
+          "dt_irradiance_gather_ray")
+    return tuple(start), tuple(dir)
+
+
+def irradiance_cosine(normal, dir):
+    """max(0, dot(normal, normalized(dir))) as points_irradiance weights a probe (include/dt.h
+    dt_irradiance_cosine); 0.0 for a void dir"""
+    D3 = ctypes.c_double * 3
+    c = ctypes.c_double()
+    check(lib.dt_irradiance_cosine(D3(*[float(v) for v in normal]), D3(*[float(v) for v in dir]), ctypes.byref(c)),
+          "dt_irradiance_cosine")
+    return c.value
+
+
+def points_irradiance(scene, g, points, normals, frame=0, n_samples=16, lights=(), gather_rays=0, planes=None,
+                      stream=None):
+    """Irradiance at surface points the caller supplies (include/dt.h dt_points_irradiance), for light baking:
+    points and normals as points_occlusion takes them. Per point the cosine-weighted visibility of each light of
+    `lights` (`direct`, float32 (n, len(lights))), its sum with the lights' colours (`direct_rgb`, (n, 3)), one
+    diffuse bounce gathered with gather_rays probes per sample (`indirect_rgb`, (n, 3); needs lights) and the share
+    of gather probes that hit nothing (`sky`, (n,)). planes: the names wanted (None: every plane that lights and
+    gather_rays allow); a plane that is not wanted costs no probes. Returns (dict, stats) on the side of points;
+    stats.shadow_rays counts the shadow probes, stats.rays the gather probes. No distance falloff, one bounce,
+    a specular surface met by a gather probe is shaded as diffuse."""
+    from ._lib import Irradiance, IrradianceParams
+    n, pp, np_, side = _ray_arrays("points_irradiance", points, normals)
+    p = IrradianceParams()
+    p.n_lights, p.gather_rays = len(lights), int(gather_rays)
+    if len(lights) > len(p.light):
+        raise DTError("points_irradiance: %d lights, at most %d" % (len(lights), len(p.light)))
+    for j, l in enumerate(lights):
+        p.light[j] = int(l)
+    if planes is None:
+        planes = tuple(name for name, ok in zip(IRRADIANCE_PLANES, (bool(lights), bool(lights),
+                                                                    bool(lights) and p.gather_rays > 0,
+                                                                    p.gather_rays > 0)) if ok)
+    shapes = {"direct": (n, len(lights)), "direct_rgb": (n, 3), "indirect_rgb": (n, 3), "sky": (n,)}
+    out, o = {}, Irradiance()
+    none = ctypes.cast(_NO_RAYS, ctypes.c_void_p)
+    for name in planes:
+        if name not in shapes:
+            raise DTError("points_irradiance: unknown plane %r" % (name,))
+        out[name] = _ray_new(points, shapes[name], "torch.float32", "float32")
+        setattr(o, name, _ptr(out[name])[0].value or none.value)
+    st = Stats()
+    check(lib.dt_points_irradiance(scene.handle, ctypes.byref(g), int(frame), n, pp, np_, int(n_samples),
+                                   ctypes.byref(p), ctypes.byref(o), side, ctypes.c_void_p(stream) if stream else None,
+                                   ctypes.byref(st)), "dt_points_irradiance")
+    return out, st
+
+
+def bake_irradiance(scene, desc, g, shape_index, width, height, side=1, **kw):
+    """A lightmap of one shape: points_irradiance(scene, g, *shape_texels(desc, shape_index, width, height, side),
+    **kw) as numpy images, row v, column u: direct (height, width, n_lights), direct_rgb and indirect_rgb (height,
+    width, 3), sky (height, width). A triangle's texels outside it are 0."""
+    import numpy as np
+    points, normals, keep = _shape_texels(desc, shape_index, width, height, side)
+    planes, st = points_irradiance(scene, g, points, normals, **kw)
+    out = {}
+    for name, a in planes.items():
+        img = np.zeros((int(height) * int(width),) + a.shape[1:], np.float32)
+        img[keep] = a
+        out[name] = img.reshape((int(height), int(width)) + a.shape[1:])
+    return out, st
+
+
+def irradiance_images(g, planes):
+    """The images `dtrender --bake-light` writes, as float32 arrays for write_png: {"direct": direct_rgb,
+    "indirect": indirect_rgb, "sky": sky}, RGB clamped to 0..1, times 255. planes: full-frame image-layout planes
+    of bake_irradiance (numpy); g.xRes x g.yRes is the lightmap's size."""
+    import numpy as np
+    n1 = g.xRes * g.yRes
+    out = {}
+    for name, key in (("direct", "direct_rgb"), ("indirect", "indirect_rgb")):
+        if key in planes:
+            v = np.asarray(planes[key], np.float32).reshape(n1 * 3)
+            out[name] = np.minimum(np.maximum(v, np.float32(0)), np.float32(1)) * np.float32(255)
+    if "sky" in planes:
+        v = np.asarray(planes["sky"], np.float32).reshape(n1)
+        out["sky"] = np.repeat(np.minimum(np.maximum(v, np.float32(0)), np.float32(1)) * np.float32(255), 3)
+    return out
 
 
 def occlusion_images(g, planes):

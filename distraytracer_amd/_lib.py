@@ -167,6 +167,18 @@ class OcclusionPanes(ctypes.Structure):
     _fields_ = [("ao_panes", ctypes.c_void_p), ("light_panes", ctypes.c_void_p)]
 
 
+class IrradianceParams(ctypes.Structure):
+    """dt_irradiance_params: n_lights 0..8 and their indices into the scene's lights in slot order, gather_rays 0..16
+    gather probes per sample"""
+    _fields_ = [("n_lights", c_int32), ("light", c_int32 * 8), ("gather_rays", c_int32)]
+
+
+class Irradiance(ctypes.Structure):
+    """dt_irradiance: the planes of dt_points_irradiance (a null pointer: not wanted)"""
+    _fields_ = [("direct", ctypes.c_void_p), ("direct_rgb", ctypes.c_void_p), ("indirect_rgb", ctypes.c_void_p),
+                ("sky", ctypes.c_void_p)]
+
+
 DT_OCCL_MAX_AO_RAYS = 16
 DT_OCCL_MAX_LIGHTS = 8
 DT_OCCL_TRIES = 16
@@ -258,7 +270,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_trace_rays_multi",
            "dt_camera_rays_rows", "dt_camera_rays", "dt_rays_resolve",
            "dt_rays_transmittance", "dt_points_occlusion_glass",
-           "dt_trace_rays_path"]
+           "dt_trace_rays_path",
+           "dt_points_irradiance", "dt_irradiance_gather_ray", "dt_irradiance_cosine"]
 
 
 class DTError(RuntimeError):
@@ -368,6 +381,12 @@ def _load():
         "dt_points_occlusion_glass": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, c_int64, ctypes.c_void_p,
                                                 ctypes.c_void_p, c_int32, P(OcclusionParams), c_int32, P(Occlusion),
                                                 P(OcclusionPanes), c_int32, ctypes.c_void_p, P(Stats)]),
+        "dt_points_irradiance": (c_int32, [ctypes.c_void_p, P(Globals), c_int32, c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p, c_int32, P(IrradianceParams), P(Irradiance), c_int32,
+                                           ctypes.c_void_p, P(Stats)]),
+        "dt_irradiance_gather_ray": (c_int32, [ctypes.c_uint32, c_int32, ctypes.c_uint32, ctypes.c_uint32, c_int32,
+                                               P(c_double), P(c_double), P(c_double), P(c_double)]),
+        "dt_irradiance_cosine": (c_int32, [P(c_double), P(c_double), P(c_double)]),
         "dt_camera_rays_rows": (c_int64, [P(Globals), P(Tiles), c_int32, c_int32]),
         "dt_camera_rays": (c_int32, [P(Globals), c_int32, P(Tiles), c_int32, c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                      c_int32, ctypes.c_void_p, P(c_float)]),

@@ -7,6 +7,7 @@
 
 #include "dt_api_internal.h"
 #include "dt_guide.h"
+#include "dt_irr.h"
 #include "dt_occl.h"
 
 using namespace dth;
@@ -820,6 +821,111 @@ int dt_occlusion_light_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint32_
   for (int k = 0; k < 3; ++k) { o.center[k] = light->center[k]; o.A[k] = light->A[k]; o.B[k] = light->B[k]; o.D[k] = light->D[k]; }
   const dtm::V3 d = dtd::occl_light_dir(seed, frame, pixel, sample, j, o, dtm::v3a(p));
   dir[0] = d.x; dir[1] = d.y; dir[2] = d.z;
+  return DT_OK;
+}
+
+// Irradiance queries at surface points: dt_points_irr_kernel over the caller's points, one lane per point. The
+// front, the traversal parameters, the RNG key and the staging are dt_points_occlusion's; the lights' records
+// (dt_irr.h IrrLight: the probe's OcclLight and the light's colour) travel with the launch. Every argument
+// check comes before any device work.
+int dt_points_irradiance(const dt_scene* sc_c, const dt_globals* g, int32_t frame, int64_t n_points, const double* point,
+                         const double* normal, int32_t n_samples, const dt_irradiance_params* params,
+                         const dt_irradiance* out, int32_t on_device, void* stream, dt_stats* stats)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  const std::string who = "dt_points_irradiance: ";
+  if (int rc = query_pointers(who, sc, g, "point", point, "normal", normal)) return rc;
+  if (!params) return fail(DT_E_INVALID, who + "null params");
+  if (!out) return fail(DT_E_INVALID, who + "null out");
+  if (n_points < 0) return fail(DT_E_INVALID, who + "n_points < 0");
+  if (n_points >= (int64_t)1 << 32) return fail(DT_E_INVALID, who + "n_points >= 2^32 (a point is the RNG counter's pixel)");
+  if (n_samples < 1 || n_samples > DT_POCCL_MAX_SAMPLES)
+    return fail(DT_E_INVALID, who + "n_samples " + std::to_string(n_samples) + " outside 1.." +
+                                  std::to_string(DT_POCCL_MAX_SAMPLES));
+  if (params->n_lights < 0 || params->n_lights > DT_OCCL_MAX_LIGHTS)
+    return fail(DT_E_INVALID, who + "n_lights " + std::to_string(params->n_lights) + " outside 0.." +
+                                  std::to_string(DT_OCCL_MAX_LIGHTS));
+  if (params->gather_rays < 0 || params->gather_rays > DT_OCCL_MAX_AO_RAYS)
+    return fail(DT_E_INVALID, who + "gather_rays " + std::to_string(params->gather_rays) + " outside 0.." +
+                                  std::to_string(DT_OCCL_MAX_AO_RAYS));
+  if (out->direct && params->n_lights == 0) return fail(DT_E_INVALID, who + "out->direct given with n_lights == 0");
+  if (out->direct_rgb && params->n_lights == 0)
+    return fail(DT_E_INVALID, who + "out->direct_rgb given with n_lights == 0");
+  if (out->indirect_rgb && params->gather_rays == 0)
+    return fail(DT_E_INVALID, who + "out->indirect_rgb given with gather_rays == 0");
+  if (out->indirect_rgb && params->n_lights == 0)
+    return fail(DT_E_INVALID, who + "out->indirect_rgb given with n_lights == 0");
+  if (out->sky && params->gather_rays == 0) return fail(DT_E_INVALID, who + "out->sky given with gather_rays == 0");
+  if (!out->direct && !out->direct_rgb && !out->indirect_rgb && !out->sky)
+    return fail(DT_E_INVALID, who + "out wants no plane (every pointer is null)");
+  // (the scene is looked at only from here on)
+  const int32_t scene_lights = (int32_t)sc->flat.lights.size();
+  for (int32_t j = 0; j < params->n_lights; ++j)
+    if (params->light[j] < 0 || params->light[j] >= scene_lights)
+      return fail(DT_E_INVALID, who + "light[" + std::to_string(j) + "] = " + std::to_string(params->light[j]) +
+                                    ", the scene has " + std::to_string(scene_lights) + " lights");
+  bool done;
+  if (int rc = query_ready(who, sc, n_points, stats, &done); rc || done) return rc;
+  dtd::DParams P;
+  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, false)) return rc;
+  // the chosen lights' records, which the copy reads until the stream is drained
+  dtd::IrrLight recs[DT_OCCL_MAX_LIGHTS];
+  memset(recs, 0, sizeof(recs));
+  for (int j = 0; j < params->n_lights; ++j) {
+    const dtd::DLight& L = sc->flat.lights[params->light[j]];
+    dtd::IrrLight& o = recs[j];
+    o.L.type = L.type;
+    o.L.shape_index = L.shape_index;
+    o.L.radius = L.radius;
+    for (int k = 0; k < 3; ++k) {
+      o.L.center[k] = L.center[k]; o.L.A[k] = L.A[k]; o.L.B[k] = L.B[k]; o.L.D[k] = L.D[k];
+      o.color[k] = L.color[k];
+    }
+  }
+  void* dlights = nullptr;
+  if (params->n_lights > 0)
+    if (int rc = aux.plane(recs, sizeof(recs), false, true, false, &dlights)) return rc;
+  const size_t n = (size_t)n_points;
+  const double *dpoint = nullptr, *dnormal = nullptr;
+  if (int rc = aux.plane_pair(point, normal, n, on_device, &dpoint, &dnormal)) return rc;
+  void* host[4] = {out->direct, out->direct_rgb, out->indirect_rgb, out->sky};
+  void* dev[4];
+  const size_t bytes[4] = {n * (size_t)params->n_lights * sizeof(float), 3 * n * sizeof(float), 3 * n * sizeof(float),
+                           n * sizeof(float)};
+  for (int k = 0; k < 4; ++k)
+    if (int rc = aux.plane(host[k], bytes[k], on_device, false, true, &dev[k])) return rc;
+  if (int rc = aux.run(dt_points_irr_kernel_ptr(), (n_points + 63) / 64, [&](int grid) {
+        return dt_launch_points_irr(aux.launch, (uint32_t)g->seed, frame, n_points, dpoint, dnormal, n_samples,
+                                    params->n_lights, dlights, params->gather_rays, (float*)dev[0], (float*)dev[1],
+                                    (float*)dev[2], (float*)dev[3], grid, aux.st);
+      }))
+    return rc;
+  aux.shadow_stats(stats);
+  if (stats) stats->rays = aux.h[ST_RAYS];   // the gather probes traced, as dt_trace_rays counts its rays
+  return DT_OK;
+}
+
+// The gather probe and the cosine weight of dt_points_irradiance for one point (dt_irr.h), for tests and callers.
+int dt_irradiance_gather_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint32_t sample, int32_t r, const double p[3],
+                             const double n[3], double start[3], double dir[3])
+{
+  if (!p || !n || !start || !dir) return fail(DT_E_INVALID, "dt_irradiance_gather_ray: null argument");
+  if (r < 0 || r >= DT_OCCL_MAX_AO_RAYS)
+    return fail(DT_E_INVALID, "dt_irradiance_gather_ray: r " + std::to_string(r) + " outside 0.." +
+                                  std::to_string(DT_OCCL_MAX_AO_RAYS - 1));
+  dtm::V3 s, d;
+  dtd::irr_gather_ray(seed, frame, pixel, sample, r, dtm::v3a(p), dtm::v3a(n), s, d);
+  start[0] = s.x; start[1] = s.y; start[2] = s.z;
+  dir[0] = d.x; dir[1] = d.y; dir[2] = d.z;
+  return DT_OK;
+}
+
+int dt_irradiance_cosine(const double n[3], const double dir[3], double* c)
+{
+  if (!n || !dir || !c) return fail(DT_E_INVALID, "dt_irradiance_cosine: null argument");
+  *c = dtd::irr_cosine(dtm::v3a(n), dtm::v3a(dir));
   return DT_OK;
 }
 

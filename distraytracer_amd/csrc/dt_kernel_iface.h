@@ -86,6 +86,11 @@ extern "C" hipError_t dt_launch_points_occl_glass(const void* dev_launch, uint32
                                                   int max_panes, float* ao, float* light, float* ao_panes,
                                                   float* light_panes, int grid, hipStream_t stream);
 extern "C" const void* dt_points_occl_glass_kernel_ptr(void);
+extern "C" hipError_t dt_launch_points_irr(const void* dev_launch, uint32_t seed, int32_t frame, int64_t n,
+                                           const double* point, const double* normal, int n_samples, int n_lights,
+                                           const void* lights, int gather_rays, float* direct, float* direct_rgb,
+                                           float* indirect_rgb, float* sky, int grid, hipStream_t stream);
+extern "C" const void* dt_points_irr_kernel_ptr(void);
 // planes: include/dt.h dt_ray_paths holding the device side of every plane (null: not wanted)
 struct dt_ray_paths;
 extern "C" hipError_t dt_launch_rayq_path(const void* dev_launch, int64_t n, const double* start, const double* dir,

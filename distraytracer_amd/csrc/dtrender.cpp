@@ -59,6 +59,12 @@
 //                     max_panes = N in 0..8): P.ao.png and P.light<j>.png by that rule, and P.ao_panes.png and
 //                     P.light_panes<j>.png, the pane planes, grey value/8*255 (8 panes are white). Without the flag
 //                     every byte written is the same as before.
+//   --bake-light SHAPE  after the frame, a lightmap of light on shape SHAPE (dt_points_irradiance) over the texels of
+//                     --bake-occlusion (--bake-size WxH, --bake-out P, --bake-samples N): the cosine-weighted
+//                     direct light of the lights of --occlusion-lights 0,1,... (needed) as P.direct.png and, with
+//                     --bake-gather K (1..16 gather probes per sample, default 0), one diffuse bounce as
+//                     P.indirect.png and the share of probes that left the scene as P.sky.png; RGB clamped to
+//                     0..1, times 255. Without the flag every byte written and printed is the same as before.
 //   --peel K          after the frame, depth peeling of the frame's own view (K = 1..8 layers; --peel-out P is
 //                     needed; --peel-samples N rays per pixel, 1..1024, default 1): dt_camera_rays, then
 //                     dt_trace_rays_multi(K), then one dt_rays_resolve per rank, written as P.layer<j>.png: layer
@@ -259,6 +265,33 @@ static int write_occlusion_pngs(const std::string& prefix, int w, int h, const f
   return 0;
 }
 
+// The texel centres of a w x h lightmap over a rectangle, checkerboard or triangle and their normal, each operation
+// one rounded f64 one (distraytracer_amd.shape_texels computes the same bits): 3 doubles per kept texel in pts and
+// nrms, its index v*w + u in keep (a triangle keeps the texels whose centre lies inside it). false: no area.
+static bool bake_texels(const dt_shape_desc& sh, int w, int h, std::vector<double>& pts, std::vector<double>& nrms,
+                        std::vector<size_t>& keep)
+{
+  const bool tri = sh.type == DT_SHAPE_TRIANGLE;
+  double e1[3], e2[3], nrm[3];
+  for (int k = 0; k < 3; ++k) { e1[k] = sh.v[1][k] - sh.v[0][k]; e2[k] = sh.v[tri ? 2 : 3][k] - sh.v[0][k]; }
+  nrm[0] = e1[1] * e2[2] - e1[2] * e2[1];
+  nrm[1] = e1[2] * e2[0] - e1[0] * e2[2];
+  nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
+  const double len = sqrt((nrm[0] * nrm[0] + nrm[1] * nrm[1]) + nrm[2] * nrm[2]);
+  if (!(std::isfinite(len) && len > 0)) return false;
+  for (int v = 0; v < h; ++v)
+    for (int u = 0; u < w; ++u) {
+      const double a = ((double)u + 0.5) / (double)w, b = ((double)v + 0.5) / (double)h;
+      if (tri && !(a + b <= 1.0)) continue;
+      keep.push_back((size_t)v * w + u);
+      for (int k = 0; k < 3; ++k) {
+        pts.push_back((sh.v[0][k] + a * e1[k]) + b * e2[k]);
+        nrms.push_back(1.0 * (nrm[k] / len));
+      }
+    }
+  return true;
+}
+
 int main(int argc, char** argv)
 {
   dt_globals g;
@@ -278,6 +311,8 @@ int main(int argc, char** argv)
   int bake_shape = -1, bake_w = 0, bake_h = 0, bake_samples = 16, bake_glass = -1;
   std::string bake_prefix;
   bool bake_asked = false;
+  int light_shape = -1, bake_gather = 0;
+  bool light_asked = false;
   int peel = 0, peel_samples = 1;
   bool peel_asked = false;
   std::string peel_prefix;
@@ -309,6 +344,8 @@ int main(int argc, char** argv)
     else if (a == "--ao-radius" && i + 1 < argc) ao_radius = atof(argv[++i]);
     else if (a == "--occlusion-lights" && i + 1 < argc) occl_lights = argv[++i];
     else if (a == "--bake-occlusion" && i + 1 < argc) { bake_shape = atoi(argv[++i]); bake_asked = true; }
+    else if (a == "--bake-light" && i + 1 < argc) { light_shape = atoi(argv[++i]); light_asked = true; }
+    else if (a == "--bake-gather" && i + 1 < argc) bake_gather = atoi(argv[++i]);
     else if (a == "--bake-size" && i + 1 < argc) sscanf(argv[++i], "%dx%d", &bake_w, &bake_h);
     else if (a == "--bake-out" && i + 1 < argc) bake_prefix = argv[++i];
     else if (a == "--bake-samples" && i + 1 < argc) bake_samples = atoi(argv[++i]);
@@ -339,6 +376,12 @@ int main(int argc, char** argv)
   }
   if (bake_asked && (bake_shape < 0 || bake_w < 1 || bake_h < 1 || bake_prefix.empty())) {
     fprintf(stderr, "usage: --bake-occlusion SHAPE (>= 0) needs --bake-size WxH and --bake-out PREFIX\n");
+    return 2;
+  }
+  if (light_asked && (light_shape < 0 || bake_w < 1 || bake_h < 1 || bake_prefix.empty() || occl_lights.empty() ||
+                      bake_gather < 0 || bake_gather > DT_OCCL_MAX_AO_RAYS)) {
+    fprintf(stderr, "usage: --bake-light SHAPE (>= 0) needs --bake-size WxH, --bake-out PREFIX, --occlusion-lights and "
+                    "--bake-gather in 0..%d\n", DT_OCCL_MAX_AO_RAYS);
     return 2;
   }
   if (peel_asked && (peel < 1 || peel > DT_MULTIHIT_MAX || peel_prefix.empty() || peel_samples < 1 ||
@@ -417,6 +460,14 @@ int main(int argc, char** argv)
     if (t != DT_SHAPE_RECTANGLE && t != DT_SHAPE_CHECKERBOARD && t != DT_SHAPE_TRIANGLE) {
       fprintf(stderr, "usage: --bake-occlusion %d: a rectangle, checkerboard or triangle of the scene's %d shapes is needed\n",
               bake_shape, desc->n_shapes);
+      return 2;
+    }
+  }
+  if (light_asked) {
+    const int t = light_shape < desc->n_shapes ? desc->shapes[light_shape].type : 0;
+    if (t != DT_SHAPE_RECTANGLE && t != DT_SHAPE_CHECKERBOARD && t != DT_SHAPE_TRIANGLE) {
+      fprintf(stderr, "usage: --bake-light %d: a rectangle, checkerboard or triangle of the scene's %d shapes is needed\n",
+              light_shape, desc->n_shapes);
       return 2;
     }
   }
@@ -635,32 +686,13 @@ int main(int argc, char** argv)
   if (bake_shape >= 0) {
     dt_occlusion_params op;
     if (!occlusion_params(ao_rays, ao_radius, occl_lights, op)) return 2;
-    const dt_shape_desc& sh = desc->shapes[bake_shape];
-    const bool tri = sh.type == DT_SHAPE_TRIANGLE;
-    // the texel centres and the normal, each operation one rounded f64 one (shape_texels computes the same bits)
-    double e1[3], e2[3], nrm[3];
-    for (int k = 0; k < 3; ++k) { e1[k] = sh.v[1][k] - sh.v[0][k]; e2[k] = sh.v[tri ? 2 : 3][k] - sh.v[0][k]; }
-    nrm[0] = e1[1] * e2[2] - e1[2] * e2[1];
-    nrm[1] = e1[2] * e2[0] - e1[0] * e2[2];
-    nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
-    const double len = sqrt((nrm[0] * nrm[0] + nrm[1] * nrm[1]) + nrm[2] * nrm[2]);
-    if (!(std::isfinite(len) && len > 0)) {
-      fprintf(stderr, "usage: --bake-occlusion: shape %d has no area\n", bake_shape);
-      return 2;
-    }
     const size_t n_tex = (size_t)bake_w * bake_h;
     std::vector<double> pts, nrms;
     std::vector<size_t> keep;   // texel v*W + u of every point
-    for (int v = 0; v < bake_h; ++v)
-      for (int u = 0; u < bake_w; ++u) {
-        const double a = ((double)u + 0.5) / (double)bake_w, b = ((double)v + 0.5) / (double)bake_h;
-        if (tri && !(a + b <= 1.0)) continue;
-        keep.push_back((size_t)v * bake_w + u);
-        for (int k = 0; k < 3; ++k) {
-          pts.push_back((sh.v[0][k] + a * e1[k]) + b * e2[k]);
-          nrms.push_back(1.0 * (nrm[k] / len));
-        }
-      }
+    if (!bake_texels(desc->shapes[bake_shape], bake_w, bake_h, pts, nrms, keep)) {
+      fprintf(stderr, "usage: --bake-occlusion: shape %d has no area\n", bake_shape);
+      return 2;
+    }
     const int nl = op.n_lights;
     std::vector<float> pao(keep.size() + 1, 0.0f), plv(keep.size() * (size_t)(nl > 0 ? nl : 1) + 1, 0.0f);
     dt_occlusion o;
@@ -706,6 +738,47 @@ int main(int argc, char** argv)
            "%.3f ms (kernel) -> %s.*.png\n",
            bake_shape, bake_w, bake_h, (unsigned long long)keep.size(), (unsigned long long)bst.shadow_rays, bake_samples,
            op.ao_rays, (double)op.ao_radius, nl, bst.kernel_ms, bake_prefix.c_str());
+  }
+  if (light_shape >= 0) {
+    dt_occlusion_params op;
+    if (!occlusion_params(0, -1.0, occl_lights, op)) return 2;
+    dt_irradiance_params ip;
+    memset(&ip, 0, sizeof ip);
+    ip.n_lights = op.n_lights;
+    for (int j = 0; j < op.n_lights; ++j) ip.light[j] = op.lights[j];
+    ip.gather_rays = bake_gather;
+    const size_t n_tex = (size_t)bake_w * bake_h;
+    std::vector<double> pts, nrms;
+    std::vector<size_t> keep;   // texel v*W + u of every point
+    if (!bake_texels(desc->shapes[light_shape], bake_w, bake_h, pts, nrms, keep)) {
+      fprintf(stderr, "usage: --bake-light: shape %d has no area\n", light_shape);
+      return 2;
+    }
+    std::vector<float> pd(3 * keep.size() + 1, 0.0f), pi(3 * keep.size() + 1, 0.0f), ps(keep.size() + 1, 0.0f);
+    dt_irradiance o;
+    memset(&o, 0, sizeof o);
+    o.direct_rgb = pd.data();
+    if (bake_gather > 0) { o.indirect_rgb = pi.data(); o.sky = ps.data(); }
+    dt_stats bst;
+    rc = dt_points_irradiance(s, &g, frame, (int64_t)keep.size(), pts.data(), nrms.data(), bake_samples, &ip, &o, 0,
+                              nullptr, &bst);
+    if (rc) return die("dt_points_irradiance", rc);
+    // RGB clamped to 0..1, times 255 (distraytracer_amd.irradiance_images restates it)
+    const auto byte = [](float v) { return (v < 0.0f ? 0.0f : v > 1.0f ? 1.0f : v) * 255.0f; };
+    std::vector<float> pix(3 * n_tex);
+    const char* names[3] = {".direct.png", ".indirect.png", ".sky.png"};
+    for (int plane = 0; plane < (bake_gather > 0 ? 3 : 1); ++plane) {
+      std::fill(pix.begin(), pix.end(), 0.0f);
+      for (size_t i = 0; i < keep.size(); ++i)
+        for (int k = 0; k < 3; ++k)
+          pix[3 * keep[i] + k] = byte(plane == 0 ? pd[3 * i + k] : plane == 1 ? pi[3 * i + k] : ps[i]);
+      rc = dt_write_png((bake_prefix + names[plane]).c_str(), bake_w, bake_h, pix.data());
+      if (rc) return die("dt_write_png (bake light)", rc);
+    }
+    printf("bake light: shape %d, %dx%d texels, %llu points, %llu shadow probes, %llu gather probes (%d samples, %d "
+           "lights, %d gather rays) in %.3f ms (kernel) -> %s.*.png\n",
+           light_shape, bake_w, bake_h, (unsigned long long)keep.size(), (unsigned long long)bst.shadow_rays,
+           (unsigned long long)bst.rays, bake_samples, ip.n_lights, bake_gather, bst.kernel_ms, bake_prefix.c_str());
   }
   if (peel_asked) {
     const int K = peel, n = peel_samples;

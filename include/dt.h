@@ -84,6 +84,9 @@ extern "C" {
  *    shadow probes that pass through glass) */
 /* (still 8, one new export and one new struct, no struct changed: dt_trace_rays_path and its dt_ray_paths --
  *    path ray queries: caller-supplied rays followed through mirrors and glass) */
+/* (still 8, new exports and two new structs, no struct changed: dt_points_irradiance and its
+ *    dt_irradiance_params and dt_irradiance, dt_irradiance_gather_ray, dt_irradiance_cosine -- irradiance
+ *    queries at surface points: cosine-weighted direct light and one diffuse gather bounce, for light baking) */
 #define DT_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------- */
@@ -1164,6 +1167,99 @@ int dt_points_occlusion_glass(const dt_scene* s, const dt_globals* g, int32_t fr
                               const dt_occlusion_params* params, int32_t max_panes /* 0..DT_TRANSMIT_MAX_PANES */,
                               const dt_occlusion* out, const dt_occlusion_panes* panes /* optional */,
                               int32_t on_device, void* stream, dt_stats* stats);
+
+/* ---- irradiance queries at surface points: direct light and one gather bounce, for light baking ----
+ * No reference counterpart. dt_points_occlusion returns fractions of unoccluded probes; this call turns the same
+ * probes into light: per point the cosine-weighted visibility of each chosen light, its sum with the lights'
+ * colours, and one diffuse bounce gathered over the hemisphere. No recursion, no glossy cascade, no libm beyond
+ * the square root of `normalized`.
+ *
+ * Points, samples, RNG key and counter (pixel = (uint32_t)i, sample = s), void points, host/device sides,
+ * staging and synchrony are dt_points_occlusion's. n = normal[3i..3i+2] is taken as given: no fixNorm, no
+ * normalisation. A void point is never probed, counts no probes and writes 0 to every plane entry of its own.
+ *
+ * Cosine (dt_irradiance_cosine; csrc/dt_irr.h, one definition for host and kernel): for a normal n and a
+ * direction dir,
+ *   c(n, dir) = dmax(0.0, dot(n, normalized(dir)))       (csrc/dt_math.h: dot = (x*x' + y*y') + z*z',
+ *                                                         normalized = dir / sqrt(dot(dir, dir)), dmax = std::max)
+ * and c = 0.0 for a void dir (a non-finite component, or all zero).
+ *
+ * Direct: the probe of slot j (light L = light[j] of the scene) of sample s of point i is
+ * dt_occlusion_light_ray(seed, frame, i, s, j, L, p), unchanged (purpose P_OLIGHT = 7), answered exactly as
+ * dt_rays_occluded(start = p, dir, skip_shape = L.shape_index) answers it, its void-ray rule included: its
+ * visibility is the probe behind dt_points_occlusion's light plane. With
+ *   C_j = the f64 sum over s = 0 .. n_samples-1, ascending, from 0.0, of (unoccluded ? c(n, dir) : 0.0),
+ *   direct[n_lights*i + j] = (float)(C_j / (double)n_samples),
+ *   direct_rgb[3i + k]     = (float)(the f64 sum over j ascending, from 0.0, of
+ *                                    L_j.color[k] * (C_j / (double)n_samples)).
+ * There is no distance falloff (the render's lights have none), and the render's division by the number of
+ * lights that contribute (rayColor's `hits`) is NOT applied: the planes are sums over the chosen slots.
+ *
+ * Gather (gather_rays = K > 0): probe r = 0 .. K-1 of sample s (dt_irradiance_gather_ray):
+ *   ball = v(P_GATHER = 8, base = r)            the ball point of dt_render_occlusion, under a purpose of its own
+ *   u = normalized(ball),  dir = n + u,  start = p + 1e-3*dir      (each operation one rounded f64 one)
+ * which is cosine-weighted about a unit n. The probe is VOID if ball is the zero vector or dir is void
+ * (dt_irradiance_gather_ray then gives dir = 0 and start = p); a void probe is not traced, contributes nothing
+ * and still counts in the denominators. Otherwise it is answered exactly as dt_trace_rays(start, dir) answers
+ * it: shape, q = point, nq = the fixNorm'ed normal, a = albedo (the base colour, texture and checker included).
+ *   a miss:                         counts towards sky, contributes 0 light
+ *   a shape with DT_F_LIGHT:        contributes a, and runs no light loop
+ *   any other shape:                per slot j one probe from q by the light-probe rule of dt_render_occlusion
+ *     under the purpose P_GLIGHT = 9 and the generalised slot r*DT_OCCL_MAX_LIGHTS + j in the place of j (the
+ *     words at sub = slot*16, the ball at base = slot), dir2 = T - q, answered as
+ *     dt_rays_occluded(q, dir2, L_j.shape_index);
+ *       E[k] = the f64 sum over j ascending, from 0.0, of L_j.color[k] * (unoccluded ? c(nq, dir2) : 0.0)
+ *     and the contribution is a[k] * E[k].
+ * With S[k] the f64 sum of the contributions over s ascending, then r ascending, from 0.0, and M the number
+ * of probes that missed,
+ *   indirect_rgb[3i + k] = (float)(S[k] / ((double)n_samples * (double)gather_rays)),
+ *   sky[i]               = (float)((double)M / ((double)n_samples * (double)gather_rays)).
+ * The estimator needs no pi: the cosine density of the probes cancels the Lambertian 1/pi. All sums are f64 per
+ * point in a fixed order, so every plane is specified bit for bit.
+ *
+ * Limits: one bounce only; a mirror or a pane of glass met by a gather probe is shaded as diffuse with its base
+ * colour; no probe passes through glass (a glass shape occludes, as in the light loop's shadow test); a light's
+ * own shape shadows nothing of that light, but a baked emitter still shadows itself against its own light's
+ * probes from behind its surface, as in dt_points_occlusion.
+ *
+ * A plane that is not wanted costs nothing: the direct probes run iff direct or direct_rgb is given, the gather
+ * probes iff indirect_rgb or sky is, their light probes (and the hit's attributes) iff indirect_rgb is.
+ * stats (optional): shadow_rays = the shadow probes tested (the non-void ones, direct and from gather hits),
+ * rays = the gather probes traced (the non-void ones), kernel_ms; everything else 0.
+ *
+ * Errors, with a dt_last_error starting "dt_points_irradiance: " and naming the argument, all before any
+ * device work: DT_E_INVALID for a null scene, globals, point, normal, params or out, n_points < 0 or
+ * n_points >= 2^32, n_samples outside 1..DT_POCCL_MAX_SAMPLES, n_lights outside 0..DT_OCCL_MAX_LIGHTS,
+ * gather_rays outside 0..DT_OCCL_MAX_AO_RAYS, out->direct or out->direct_rgb given with n_lights == 0,
+ * out->indirect_rgb given with gather_rays == 0 or with n_lights == 0, out->sky given with gather_rays == 0,
+ * every plane NULL, a light index outside the scene; DT_E_UNSUPPORTED for a scene with a
+ * RectPrismWithCylinder. n_points == 0: DT_OK, nothing is launched.
+ *
+ * The walks are dt_points_occlusion's wave-uniform ones, 64 consecutive points per wave: one shadow walk per
+ * (slot, sample), then per (sample, gather probe) one closest-hit walk and one shadow walk per slot. Points
+ * that are neighbours in the arrays should be neighbours in space (README.md). */
+typedef struct dt_irradiance_params {
+  int32_t n_lights;                    /* 0..DT_OCCL_MAX_LIGHTS */
+  int32_t light[DT_OCCL_MAX_LIGHTS];   /* scene light indices, slot order */
+  int32_t gather_rays;                 /* 0..DT_OCCL_MAX_AO_RAYS gather probes per sample */
+} dt_irradiance_params;
+typedef struct dt_irradiance {         /* each plane optional, not all NULL; all on one side */
+  float* direct;       /* n_lights per point: entry n_lights*i + j, cosine-weighted visibility of slot j */
+  float* direct_rgb;   /* 3 per point: sum over slots of colour_j * that mean */
+  float* indirect_rgb; /* 3 per point (needs gather_rays > 0 and n_lights > 0) */
+  float* sky;          /* 1 per point (needs gather_rays > 0): share of gather probes that hit nothing */
+} dt_irradiance;
+int dt_points_irradiance(const dt_scene* s, const dt_globals* g, int32_t frame, int64_t n_points,
+                         const double* point, const double* normal,   /* 3 doubles per point each */
+                         int32_t n_samples,                           /* 1..DT_POCCL_MAX_SAMPLES */
+                         const dt_irradiance_params* params, const dt_irradiance* out,
+                         int32_t on_device, void* stream, dt_stats* stats);
+/* The gather probe r (0..DT_OCCL_MAX_AO_RAYS-1) of one sample and the cosine weight (csrc/dt_irr.h), for tests
+ * and callers. No device work. DT_OK; a null argument or r outside its range: DT_E_INVALID. A void gather
+ * probe gives dir = (0, 0, 0) and start = p. */
+int dt_irradiance_gather_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint32_t sample, int32_t r,
+                             const double p[3], const double n[3], double start[3], double dir[3]);
+int dt_irradiance_cosine(const double n[3], const double dir[3], double* c);
 
 /* ---- feature-guided denoising of previews: an edge-avoiding a-trous filter ----
  * No reference counterpart. The consumer of the feature buffers: (preview, albedo, normal, depth) ->
