@@ -40,7 +40,8 @@ __all__ = ["Globals", "Tiles", "Stats", "DTError", "globals_default", "build_sce
            "OcclusionParams", "occlusion_params_default", "render_occlusion", "occlusion_ao_ray", "occlusion_light_ray",
            "occlusion_images", "points_occlusion", "shape_texels", "bake_occlusion",
            "points_irradiance", "irradiance_gather_ray", "irradiance_cosine", "bake_irradiance", "irradiance_images",
-           "IRRADIANCE_PLANES"]
+           "IRRADIANCE_PLANES",
+           "points_visibility", "visibility_matrix", "bake_visibility", "VISIBILITY_PLANES"]
 
 
 def globals_default():
@@ -570,6 +571,95 @@ def bake_irradiance(scene, desc, g, shape_index, width, height, side=1, **kw):
         img = np.zeros((int(height) * int(width),) + a.shape[1:], np.float32)
         img[keep] = a
         out[name] = img.reshape((int(height), int(width)) + a.shape[1:])
+    return out, st
+
+
+VISIBILITY_PLANES = ("bits", "count_a", "count_b", "weight_a")
+
+
+def points_visibility(scene, g, a, b, skip_b=None, normals_a=None, normals_b=None, falloff=False,
+                      planes=("bits", "count_a", "count_b"), stream=None):
+    """Which of the targets b can each of the sources a see (include/dt.h dt_points_visibility)? a and b are float64,
+    shaped (n, 3) or flat, numpy arrays or torch tensors, all arrays of a call on one side. Pair (i, j) is answered
+    as rays_occluded answers (a[i], b[j] - a[i], skip_b[j]): skip_b is int32 per target, the shape the target is or
+    lies on (-1: none). Returns (dict, stats) on the side of a for the planes asked for: `bits` (n_a, ceil(n_b/32))
+    uint32 in numpy, the same bits as int32 in torch (visibility_matrix unpacks them), `count_a` int32 (n_a,) the
+    targets each source sees, `count_b` int32 (n_b,) the sources that see each target, `weight_a` float64 (n_a,)
+    the sum over the visible targets of cos_a * cos_b (falloff: divided by the squared distance), which needs
+    normals_a and normals_b (as given: not normalised) and has a fixed summation order. A point with a non-finite
+    component sees nothing and is seen by nothing. 64 consecutive sources share a wave and walk towards one target
+    at a time: keep both arrays spatially ordered."""
+    from ._lib import Visibility, VisibilityParams
+    sp, side = _ptr_typed(a, "torch.float64", "float64")
+    tp, tside = _ptr_typed(b, "torch.float64", "float64")
+    na3, nb3 = _numel_any(a), _numel_any(b)
+    if na3 % 3 or nb3 % 3 or side != tside:
+        raise DTError("points_visibility: a and b hold 3 doubles per point, on the same side")
+    n_a, n_b = na3 // 3, nb3 // 3
+    none = ctypes.cast(_NO_RAYS, ctypes.c_void_p)
+    p = VisibilityParams()
+    lib.dt_visibility_params_default(ctypes.byref(p))
+    p.falloff = 1 if falloff else 0
+    if skip_b is not None:
+        p.skip_b = _ray_out("points_visibility", "skip_b", skip_b, n_b, 1, "torch.int32", "int32", side).value
+    if "weight_a" in planes and (normals_a is None or normals_b is None):
+        raise DTError("points_visibility: weight_a needs normals_a and normals_b")
+    if normals_a is not None:
+        p.normal_a = _ray_out("points_visibility", "normals_a", normals_a, n_a, 3, "torch.float64", "float64", side).value
+    if normals_b is not None:
+        p.normal_b = _ray_out("points_visibility", "normals_b", normals_b, n_b, 3, "torch.float64", "float64", side).value
+    words = (n_b + 31) // 32
+    types = {"bits": ((n_a, words), "torch.int32", "uint32"), "count_a": ((n_a,), "torch.int32", "int32"),
+             "count_b": ((n_b,), "torch.int32", "int32"), "weight_a": ((n_a,), "torch.float64", "float64")}
+    out, o = {}, Visibility()
+    for name in planes:
+        if name not in types:
+            raise DTError("points_visibility: unknown plane %r" % (name,))
+        out[name] = _ray_new(a, *types[name])
+        setattr(o, name, _data_ptr(out[name]).value)
+    st = Stats()
+    check(lib.dt_points_visibility(scene.handle if scene is not None else None, ctypes.byref(g), n_a,
+                                   sp if sp.value else none, n_b, tp if tp.value else none, ctypes.byref(p),
+                                   ctypes.byref(o), side, ctypes.c_void_p(stream) if stream else None, ctypes.byref(st)),
+          "dt_points_visibility")
+    return out, st
+
+
+def visibility_matrix(bits, n_b):
+    """The bool (n_a, n_b) matrix of points_visibility's `bits` (numpy uint32 or a torch int32 tensor, shaped
+    (n_a, ceil(n_b/32))): entry (i, j) is bit (j & 31) of word j >> 5 of row i. numpy, on the host."""
+    import numpy as np
+    w = bits.cpu().numpy() if hasattr(bits, "data_ptr") else np.asarray(bits)
+    n_b = int(n_b)
+    words = (n_b + 31) // 32
+    w = np.ascontiguousarray(w).view(np.uint32).reshape(-1, words) if words else np.zeros((w.shape[0], 0), np.uint32)
+    shifts = np.arange(32, dtype=np.uint32)
+    return (((w[:, :, None] >> shifts[None, None, :]) & np.uint32(1)) != 0).reshape(w.shape[0], words * 32)[:, :n_b]
+
+
+def bake_visibility(scene, desc, g, shape_a, shape_b, width, height, target_size=(8, 8), side=1, **kw):
+    """How much of shape_b does each texel of shape_a see? Sources are shape_texels(desc, shape_a, width, height,
+    side), targets shape_texels(desc, shape_b, *target_size) with skip_b = shape_b (the target shape hides none of
+    its own texels). Returns (dict, stats) of numpy images, row v, column u: `visible` float32 (height, width) =
+    count_a / n_b, the share of shape_b's texels the texel sees, and with planes holding "weight_a" (normals are the
+    texels') `weight` float64 (height, width). A triangle's texels outside it are 0. kw: falloff, planes, stream
+    of points_visibility; count_a is always computed."""
+    import numpy as np
+    pa, na, keep = _shape_texels(desc, shape_a, width, height, side)
+    pb, nb, _ = _shape_texels(desc, shape_b, int(target_size[0]), int(target_size[1]), 1)
+    planes = tuple(kw.pop("planes", ("count_a",)))
+    if "count_a" not in planes:
+        planes += ("count_a",)
+    got, st = points_visibility(scene, g, pa, pb, skip_b=np.full(len(pb), int(shape_b), np.int32), normals_a=na,
+                                normals_b=nb, planes=planes, **kw)
+    n_px = int(height) * int(width)
+    vis = np.zeros(n_px, np.float32)
+    vis[keep] = (got["count_a"].astype(np.float64) / float(len(pb))).astype(np.float32)
+    out = {"visible": vis.reshape(int(height), int(width))}
+    if "weight_a" in got:
+        wgt = np.zeros(n_px, np.float64)
+        wgt[keep] = got["weight_a"]
+        out["weight"] = wgt.reshape(int(height), int(width))
     return out, st
 
 

@@ -179,6 +179,22 @@ class Irradiance(ctypes.Structure):
                 ("sky", ctypes.c_void_p)]
 
 
+DT_PVIS_TILE = 256   # targets per work item of dt_points_visibility, the tile of weight_a's sum order (include/dt.h)
+
+
+class VisibilityParams(ctypes.Structure):
+    """dt_visibility_params: skip_b (int32 per target, null: none), normal_a and normal_b (3 doubles per point, both
+    needed for weight_a), falloff 0/1"""
+    _fields_ = [("skip_b", ctypes.c_void_p), ("normal_a", ctypes.c_void_p), ("normal_b", ctypes.c_void_p),
+                ("falloff", c_int32)]
+
+
+class Visibility(ctypes.Structure):
+    """dt_visibility: the planes of dt_points_visibility (a null pointer: not wanted)"""
+    _fields_ = [("bits", ctypes.c_void_p), ("count_a", ctypes.c_void_p), ("count_b", ctypes.c_void_p),
+                ("weight_a", ctypes.c_void_p)]
+
+
 DT_OCCL_MAX_AO_RAYS = 16
 DT_OCCL_MAX_LIGHTS = 8
 DT_OCCL_TRIES = 16
@@ -271,7 +287,8 @@ EXPORTS = ["dt_abi_version", "dt_last_error", "dt_globals_default", "dt_scene_cr
            "dt_camera_rays_rows", "dt_camera_rays", "dt_rays_resolve",
            "dt_rays_transmittance", "dt_points_occlusion_glass",
            "dt_trace_rays_path",
-           "dt_points_irradiance", "dt_irradiance_gather_ray", "dt_irradiance_cosine"]
+           "dt_points_irradiance", "dt_irradiance_gather_ray", "dt_irradiance_cosine",
+           "dt_visibility_params_default", "dt_points_visibility"]
 
 
 class DTError(RuntimeError):
@@ -387,6 +404,9 @@ def _load():
         "dt_irradiance_gather_ray": (c_int32, [ctypes.c_uint32, c_int32, ctypes.c_uint32, ctypes.c_uint32, c_int32,
                                                P(c_double), P(c_double), P(c_double), P(c_double)]),
         "dt_irradiance_cosine": (c_int32, [P(c_double), P(c_double), P(c_double)]),
+        "dt_visibility_params_default": (None, [P(VisibilityParams)]),
+        "dt_points_visibility": (c_int32, [ctypes.c_void_p, P(Globals), c_int64, ctypes.c_void_p, c_int64, ctypes.c_void_p,
+                                           P(VisibilityParams), P(Visibility), c_int32, ctypes.c_void_p, P(Stats)]),
         "dt_camera_rays_rows": (c_int64, [P(Globals), P(Tiles), c_int32, c_int32]),
         "dt_camera_rays": (c_int32, [P(Globals), c_int32, P(Tiles), c_int32, c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                      c_int32, ctypes.c_void_p, P(c_float)]),

@@ -107,6 +107,9 @@ struct AuxLaunch {
     return DT_OK;
   }
 
+  // a device temporary of the launch's own, released with it (contents undefined)
+  int scratch(size_t bytes, void** dev) { return alloc(bytes, dev); }
+
   // the two 3 n double arrays a query reads (rays: start and dir; points: point and normal)
   int plane_pair(const double* a, const double* b, size_t n, bool on_device, const double** da, const double** db)
   {
@@ -926,6 +929,89 @@ int dt_irradiance_cosine(const double n[3], const double dir[3], double* c)
 {
   if (!n || !dir || !c) return fail(DT_E_INVALID, "dt_irradiance_cosine: null argument");
   *c = dtd::irr_cosine(dtm::v3a(n), dtm::v3a(dir));
+  return DT_OK;
+}
+
+// Mutual visibility of two point sets: dt_points_vis_kernel over (waves of 64 sources) x (tiles of DT_PVIS_TILE
+// targets), then dt_points_vis_sum_kernel when weight_a is wanted. As a ray query it takes only the traversal
+// parameters from g (prepare_whole at frame 0, as dt_rays_occluded, so that a pair is answered as that call
+// answers it) and neither reads nor rebuilds the primary-ray lists. Every argument check comes before any
+// device work. The two count planes are zeroed on the stream before the launch (the kernel adds to them); the
+// tiles' partial weight sums live in a temporary of the launch's own.
+void dt_visibility_params_default(dt_visibility_params* p)
+{
+  if (p) memset(p, 0, sizeof(*p));
+}
+
+int dt_points_visibility(const dt_scene* sc_c, const dt_globals* g, int64_t n_a, const double* a, int64_t n_b,
+                         const double* b, const dt_visibility_params* params, const dt_visibility* out,
+                         int32_t on_device, void* stream, dt_stats* stats)
+{
+  dt_scene* sc = const_cast<dt_scene*>(sc_c);
+  const std::string who = "dt_points_visibility: ";
+  if (int rc = query_pointers(who, sc, g, "a", a, "b", b)) return rc;
+  if (!params) return fail(DT_E_INVALID, who + "null params");
+  if (!out) return fail(DT_E_INVALID, who + "null out");
+  if (!out->bits && !out->count_a && !out->count_b && !out->weight_a)
+    return fail(DT_E_INVALID, who + "out wants no plane (every pointer is null)");
+  if (n_a < 0) return fail(DT_E_INVALID, who + "n_a < 0");
+  if (n_b < 0) return fail(DT_E_INVALID, who + "n_b < 0");
+  if (n_a >= (int64_t)1 << 31) return fail(DT_E_INVALID, who + "n_a >= 2^31");
+  if (n_b >= (int64_t)1 << 31) return fail(DT_E_INVALID, who + "n_b >= 2^31");
+  if (out->weight_a && !params->normal_a) return fail(DT_E_INVALID, who + "out->weight_a given without params->normal_a");
+  if (out->weight_a && !params->normal_b) return fail(DT_E_INVALID, who + "out->weight_a given without params->normal_b");
+  if (params->falloff < 0 || params->falloff > 1)
+    return fail(DT_E_INVALID, who + "falloff " + std::to_string(params->falloff) + " outside 0..1");
+  const size_t na = (size_t)n_a, nb = (size_t)n_b, words = (nb + 31) / 32;
+  const size_t n_tiles = (nb + DT_PVIS_TILE - 1) / DT_PVIS_TILE;
+  bool done;
+  if (int rc = query_ready(who, sc, (n_a && n_b) ? 1 : 0, stats, &done)) return rc;
+  void* const host[4] = {out->bits, out->count_a, out->count_b, out->weight_a};
+  const size_t bytes[4] = {na * words * sizeof(uint32_t), na * sizeof(int32_t), nb * sizeof(int32_t), na * sizeof(double)};
+  if (done) {   // no pair: the planes that have entries are zeros
+    hipStream_t st = (hipStream_t)stream;
+    bool any = false;
+    for (int k = 0; k < 4; ++k) {
+      if (!host[k] || !bytes[k]) continue;
+      if (on_device) {
+        HIPCHK(hipMemsetAsync(host[k], 0, bytes[k], st));
+        any = true;
+      } else {
+        memset(host[k], 0, bytes[k]);
+      }
+    }
+    if (any) HIPCHK(hipStreamSynchronize(st));
+    return DT_OK;
+  }
+  dtd::DParams P;
+  if (int rc = prepare_whole(sc, g, 0, P)) return rc;
+  AuxLaunch aux(stream);
+  if (int rc = aux.begin(sc, P, false)) return rc;
+  const double *da = nullptr, *db = nullptr, *dna = nullptr, *dnb = nullptr;
+  void* dskip = nullptr;
+  if (int rc = aux.plane(a, 3 * na * sizeof(double), on_device, true, false, (void**)&da)) return rc;
+  if (int rc = aux.plane(b, 3 * nb * sizeof(double), on_device, true, false, (void**)&db)) return rc;
+  if (int rc = aux.plane(params->skip_b, nb * sizeof(int32_t), on_device, true, false, &dskip)) return rc;
+  if (out->weight_a) {   // the normals are read for the weight alone
+    if (int rc = aux.plane(params->normal_a, 3 * na * sizeof(double), on_device, true, false, (void**)&dna)) return rc;
+    if (int rc = aux.plane(params->normal_b, 3 * nb * sizeof(double), on_device, true, false, (void**)&dnb)) return rc;
+  }
+  void* dev[4];
+  for (int k = 0; k < 4; ++k)
+    if (int rc = aux.plane(host[k], bytes[k], on_device, false, true, &dev[k])) return rc;
+  for (int k = 1; k <= 2; ++k)
+    if (dev[k]) HIPCHK(hipMemsetAsync(dev[k], 0, bytes[k], aux.st));
+  void* partial = nullptr;
+  if (out->weight_a)
+    if (int rc = aux.scratch(n_tiles * na * sizeof(double), &partial)) return rc;
+  const int64_t items = (int64_t)((na + 63) / 64) * (int64_t)n_tiles;
+  if (int rc = aux.run(dt_points_vis_kernel_ptr(), items, [&](int grid) {
+        return dt_launch_points_vis(aux.launch, n_a, da, n_b, db, (const int32_t*)dskip, dna, dnb, params->falloff,
+                                    (uint32_t*)dev[0], (int32_t*)dev[1], (int32_t*)dev[2], (double*)partial,
+                                    (double*)dev[3], grid, aux.st);
+      }))
+    return rc;
+  aux.shadow_stats(stats);
   return DT_OK;
 }
 

@@ -91,6 +91,13 @@ extern "C" hipError_t dt_launch_points_irr(const void* dev_launch, uint32_t seed
                                            const void* lights, int gather_rays, float* direct, float* direct_rgb,
                                            float* indirect_rgb, float* sky, int grid, hipStream_t stream);
 extern "C" const void* dt_points_irr_kernel_ptr(void);
+// partial: n_tiles * n_a doubles the weight reduction reads (null with weight_a: no cosines, no second kernel)
+extern "C" hipError_t dt_launch_points_vis(const void* dev_launch, int64_t n_a, const double* a, int64_t n_b,
+                                           const double* b, const int32_t* skip_b, const double* normal_a,
+                                           const double* normal_b, int falloff, uint32_t* bits, int32_t* count_a,
+                                           int32_t* count_b, double* partial, double* weight_a, int grid,
+                                           hipStream_t stream);
+extern "C" const void* dt_points_vis_kernel_ptr(void);
 // planes: include/dt.h dt_ray_paths holding the device side of every plane (null: not wanted)
 struct dt_ray_paths;
 extern "C" hipError_t dt_launch_rayq_path(const void* dev_launch, int64_t n, const double* start, const double* dir,

@@ -65,6 +65,11 @@
 //                     --bake-gather K (1..16 gather probes per sample, default 0), one diffuse bounce as
 //                     P.indirect.png and the share of probes that left the scene as P.sky.png; RGB clamped to
 //                     0..1, times 255. Without the flag every byte written and printed is the same as before.
+//   --bake-visible SHAPE_A,SHAPE_B  after the frame, how much of SHAPE_B each texel of SHAPE_A sees
+//                     (dt_points_visibility): sources are the --bake-size WxH texels of SHAPE_A, targets the
+//                     --bake-target-size WxH texels of SHAPE_B (both as --bake-occlusion's), skip_b = SHAPE_B; written
+//                     as --bake-out P: P.visible.png, W x H, row v, grey (count_a / targets) * 255. Without the flag
+//                     every byte written and printed is the same as before.
 //   --peel K          after the frame, depth peeling of the frame's own view (K = 1..8 layers; --peel-out P is
 //                     needed; --peel-samples N rays per pixel, 1..1024, default 1): dt_camera_rays, then
 //                     dt_trace_rays_multi(K), then one dt_rays_resolve per rank, written as P.layer<j>.png: layer
@@ -313,6 +318,8 @@ int main(int argc, char** argv)
   bool bake_asked = false;
   int light_shape = -1, bake_gather = 0;
   bool light_asked = false;
+  int vis_a = -1, vis_b = -1, vis_tw = 0, vis_th = 0;
+  bool vis_asked = false;
   int peel = 0, peel_samples = 1;
   bool peel_asked = false;
   std::string peel_prefix;
@@ -346,6 +353,8 @@ int main(int argc, char** argv)
     else if (a == "--bake-occlusion" && i + 1 < argc) { bake_shape = atoi(argv[++i]); bake_asked = true; }
     else if (a == "--bake-light" && i + 1 < argc) { light_shape = atoi(argv[++i]); light_asked = true; }
     else if (a == "--bake-gather" && i + 1 < argc) bake_gather = atoi(argv[++i]);
+    else if (a == "--bake-visible" && i + 1 < argc) { sscanf(argv[++i], "%d,%d", &vis_a, &vis_b); vis_asked = true; }
+    else if (a == "--bake-target-size" && i + 1 < argc) sscanf(argv[++i], "%dx%d", &vis_tw, &vis_th);
     else if (a == "--bake-size" && i + 1 < argc) sscanf(argv[++i], "%dx%d", &bake_w, &bake_h);
     else if (a == "--bake-out" && i + 1 < argc) bake_prefix = argv[++i];
     else if (a == "--bake-samples" && i + 1 < argc) bake_samples = atoi(argv[++i]);
@@ -382,6 +391,11 @@ int main(int argc, char** argv)
                       bake_gather < 0 || bake_gather > DT_OCCL_MAX_AO_RAYS)) {
     fprintf(stderr, "usage: --bake-light SHAPE (>= 0) needs --bake-size WxH, --bake-out PREFIX, --occlusion-lights and "
                     "--bake-gather in 0..%d\n", DT_OCCL_MAX_AO_RAYS);
+    return 2;
+  }
+  if (vis_asked && (vis_a < 0 || vis_b < 0 || bake_w < 1 || bake_h < 1 || vis_tw < 1 || vis_th < 1 || bake_prefix.empty())) {
+    fprintf(stderr, "usage: --bake-visible SHAPE_A,SHAPE_B (>= 0) needs --bake-size WxH, --bake-target-size WxH and "
+                    "--bake-out PREFIX\n");
     return 2;
   }
   if (peel_asked && (peel < 1 || peel > DT_MULTIHIT_MAX || peel_prefix.empty() || peel_samples < 1 ||
@@ -471,6 +485,15 @@ int main(int argc, char** argv)
       return 2;
     }
   }
+  if (vis_asked)
+    for (const int shape : {vis_a, vis_b}) {
+      const int t = shape < desc->n_shapes ? desc->shapes[shape].type : 0;
+      if (t != DT_SHAPE_RECTANGLE && t != DT_SHAPE_CHECKERBOARD && t != DT_SHAPE_TRIANGLE) {
+        fprintf(stderr, "usage: --bake-visible %d: a rectangle, checkerboard or triangle of the scene's %d shapes is needed\n",
+                shape, desc->n_shapes);
+        return 2;
+      }
+    }
   dt_scene* s = nullptr;
   rc = dt_scene_create(desc, &g, &s);
   if (rc) return die("dt_scene_create", rc);
@@ -779,6 +802,37 @@ int main(int argc, char** argv)
            "lights, %d gather rays) in %.3f ms (kernel) -> %s.*.png\n",
            light_shape, bake_w, bake_h, (unsigned long long)keep.size(), (unsigned long long)bst.shadow_rays,
            (unsigned long long)bst.rays, bake_samples, ip.n_lights, bake_gather, bst.kernel_ms, bake_prefix.c_str());
+  }
+  if (vis_asked) {
+    std::vector<double> pa, na, pb, nb;
+    std::vector<size_t> keep, keep_b;   // texel v*W + u of every source; of every target
+    if (!bake_texels(desc->shapes[vis_a], bake_w, bake_h, pa, na, keep) ||
+        !bake_texels(desc->shapes[vis_b], vis_tw, vis_th, pb, nb, keep_b)) {
+      fprintf(stderr, "usage: --bake-visible: a shape has no area\n");
+      return 2;
+    }
+    const std::vector<int32_t> skip(keep_b.size(), vis_b);   // the target shape hides none of its own texels
+    std::vector<int32_t> seen(keep.size() + 1, 0);
+    dt_visibility_params vp;
+    dt_visibility_params_default(&vp);
+    vp.skip_b = skip.data();
+    dt_visibility o;
+    memset(&o, 0, sizeof o);
+    o.count_a = seen.data();
+    dt_stats bst;
+    rc = dt_points_visibility(s, &g, (int64_t)keep.size(), pa.data(), (int64_t)keep_b.size(), pb.data(), &vp, &o, 0,
+                              nullptr, &bst);
+    if (rc) return die("dt_points_visibility", rc);
+    // the share of the targets seen, as float32, times 255 (distraytracer_amd.bake_visibility's `visible` image)
+    std::vector<float> pix(3 * (size_t)bake_w * bake_h, 0.0f);
+    for (size_t i = 0; i < keep.size(); ++i)
+      for (int k = 0; k < 3; ++k) pix[3 * keep[i] + k] = (float)((double)seen[i] / (double)keep_b.size()) * 255.0f;
+    rc = dt_write_png((bake_prefix + ".visible.png").c_str(), bake_w, bake_h, pix.data());
+    if (rc) return die("dt_write_png (bake visible)", rc);
+    printf("bake visible: shape %d, %dx%d texels, %llu sources against %llu targets of shape %d (%dx%d), %llu pairs traced "
+           "in %.3f ms (kernel) -> %s.visible.png\n",
+           vis_a, bake_w, bake_h, (unsigned long long)keep.size(), (unsigned long long)keep_b.size(), vis_b, vis_tw, vis_th,
+           (unsigned long long)bst.shadow_rays, bst.kernel_ms, bake_prefix.c_str());
   }
   if (peel_asked) {
     const int K = peel, n = peel_samples;

@@ -1261,6 +1261,76 @@ int dt_irradiance_gather_ray(uint32_t seed, int32_t frame, uint32_t pixel, uint3
                              const double p[3], const double n[3], double start[3], double dir[3]);
 int dt_irradiance_cosine(const double n[3], const double dir[3], double* c);
 
+/* ---- mutual visibility between two point sets: which of these targets can each of those sources see? ----
+ * No reference counterpart. dt_rays_occluded answers segments the caller builds one by one (48 bytes in and one
+ * out per pair); this call answers all n_a x n_b pairs of two point sets with the segments built on the device:
+ * 24 bytes per point go in, one bit per pair comes out, with the per-source and per-target counts and a
+ * cosine-weighted sum. Line of sight and coverage (sensors against targets), potentially-visible sets,
+ * deterministic area-light quadrature, the form-factor matrix of a radiosity solve.
+ * a holds 3 doubles per source (n_a of them), b 3 per target (n_b); n_a and n_b below 2^31.
+ *
+ * Pair (i, j) is the segment start = a[3i..3i+2], dir = b[3j..3j+2] - start (component-wise, each one rounded
+ * f64 subtraction). It is VISIBLE iff dt_rays_occluded(start, dir, skip_shape = skip_b ? skip_b[j] : -1) would
+ * write 0 for it: the same gather along dir from start + 1e-3*dir, the same intersectShadow(sn, start + 1e-3*sn,
+ * (float)|dir|) on every gathered shape but the skip shape, tree walks only. skip_b[j] is the shape target j is
+ * or lies on (a light, a sensor; -1: none); there is no skip shape on the source's side, and the 1e-3 offset is
+ * applied at the source only, so visibility is not exactly symmetric in a and b.
+ *
+ * A source or a target is VOID if its point has a non-finite component and, when out->weight_a is wanted, also
+ * if its normal has one. A void source is never probed and writes 0 to its row of bits, its count_a and its
+ * weight_a; a void target is never probed, has bit 0 in every row and count_b 0. Neighbours are unaffected.
+ * A pair of two live points whose dir is a void ray by dt_rays_occluded's rule (all zero: a[i] == b[j]; or, by
+ * overflow of the subtraction, non-finite) is not traced and counts as VISIBLE, as that call reports it: bit 1,
+ * counted in count_a and count_b, weight 0.
+ *
+ * Weight (out->weight_a; needs normal_a and normal_b, taken as given: no fixNorm, no normalisation): with
+ *   ca = dt_irradiance_cosine(normal_a[i], dir),  cb = dt_irradiance_cosine(normal_b[j], -dir),
+ *   dd = dot(dir, dir) = (x*x + y*y) + z*z                                  (csrc/dt_math.h's order),
+ *   w_ij = 0.0 for a pair that is not visible or whose dir is void, else ca*cb (falloff 0) or (ca*cb)/dd (1),
+ * weight_a[i] is a sum in a FIXED order, so that the device may split the targets among workgroups:
+ *   1. per tile of DT_PVIS_TILE consecutive targets (tile t: j = t*DT_PVIS_TILE .. min(n_b, (t+1)*DT_PVIS_TILE)-1)
+ *      the f64 sum of w_ij in ascending j, from 0.0, every j of the tile adding its term (a 0.0 included);
+ *   2. then the f64 sum of the tile sums in ascending t, from 0.0.
+ * Every plane is so specified bit for bit. There is no pi and no area in the weight: callers scale. There is no
+ * weight_b (it would need a sum across lanes): swap the sets.
+ *
+ * a, b, skip_b, the normals and the planes of out are all host (on_device=0: staged through temporaries, as
+ * dt_points_occlusion stages its arrays) or all device (1). The call is synchronous, with a launch record,
+ * counters and events of its own; it neither reads nor rebuilds the scene's primary-ray lists, and a render of
+ * the scene afterwards is unaffected. g: as for the ray queries, only what traversal reads matters.
+ * stats (optional): shadow_rays = the pairs traced (both points live, dir not void), kernel_ms; everything else
+ * 0. A plane that is not wanted costs nothing: no cosine is evaluated without weight_a.
+ *
+ * Errors, with a dt_last_error starting "dt_points_visibility: " and naming the argument, all before any device
+ * work: DT_E_INVALID for a null scene, globals, a, b, params or out, every plane NULL, n_a < 0 or n_b < 0, n_a or
+ * n_b >= 2^31, out->weight_a given without both normals, falloff outside 0..1; DT_E_UNSUPPORTED for a scene with
+ * a RectPrismWithCylinder. n_a == 0 or n_b == 0: DT_OK, nothing is launched, and every plane that has entries
+ * (count_a with n_b == 0, count_b with n_a == 0, weight_a) is zeroed.
+ *
+ * The walk is the renders' wave-uniform one. A work item is 64 consecutive sources (a wave, one source per
+ * lane) against DT_PVIS_TILE consecutive targets, one walk per target: the 64 segments of a walk end in one
+ * point and skip one shape, so no grouping by skip shape is needed. Keep both arrays spatially ordered: sources
+ * that are neighbours in a should be neighbours in space (README.md). bits needs n_a * ceil(n_b/32) words. */
+#define DT_PVIS_TILE 256        /* targets per work item; a multiple of 32 */
+typedef struct dt_visibility_params {
+  const int32_t* skip_b;     /* optional, n_b entries: the shape target j is (a light, a sensor); treated per pair
+                                exactly as dt_rays_occluded treats skip_shape */
+  const double*  normal_a;   /* optional, 3 per source; required iff out->weight_a */
+  const double*  normal_b;   /* optional, 3 per target; required iff out->weight_a */
+  int32_t        falloff;    /* 0: weight = ca*cb; 1: weight = (ca*cb)/dd */
+} dt_visibility_params;
+typedef struct dt_visibility {   /* each plane optional, not all NULL; all on one side */
+  uint32_t* bits;      /* n_a rows of W = ceil(n_b/32) words: bit (j & 31) of word j >> 5 of row i = pair (i,j) visible;
+                          the unused high bits of a row's last word are 0 */
+  int32_t*  count_a;   /* n_a: visible targets per source */
+  int32_t*  count_b;   /* n_b: sources that see target j */
+  double*   weight_a;  /* n_a: the weighted sum above */
+} dt_visibility;
+void dt_visibility_params_default(dt_visibility_params* p);   /* no skip shapes, no normals, falloff 0 */
+int  dt_points_visibility(const dt_scene* s, const dt_globals* g, int64_t n_a, const double* a, int64_t n_b,
+                          const double* b, const dt_visibility_params* params, const dt_visibility* out,
+                          int32_t on_device, void* stream, dt_stats* stats);
+
 /* ---- feature-guided denoising of previews: an edge-avoiding a-trous filter ----
  * No reference counterpart. The consumer of the feature buffers: (preview, albedo, normal, depth) ->
  * a clean preview, by the edge-avoiding a-trous wavelet filter of Dammertz et al. 2010, demodulated by
