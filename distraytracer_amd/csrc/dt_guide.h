@@ -1,5 +1,5 @@
 // Specular-path feature buffers: the one definition of "the guide ray goes on from this hit, and with
-// which ray", shared by the kernel (dt_kernels.hip dt_features_path_kernel) and the host export
+// which ray", shared by the kernel (dt_features_path.hip dt_features_path_kernel) and the host export
 // dt_guide_bounce (dt_api.cpp). Both sides are built with -ffp-contract=off, so they run the same IEEE
 // operations in the same order.
 // It restates the trace kernel's bounce arithmetic (dt_kernels.hip run_pass: the mirror ray, the glass

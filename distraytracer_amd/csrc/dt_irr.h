@@ -1,5 +1,5 @@
 // Irradiance queries at surface points: the one definition of what dt_points_irradiance (include/dt.h) adds to
-// the probe generators of dt_occl.h, shared by the kernel (dt_kernels.hip dt_points_irr_kernel) and the host
+// the probe generators of dt_occl.h, shared by the kernel (dt_points_irr.hip dt_points_irr_kernel) and the host
 // exports dt_irradiance_gather_ray / dt_irradiance_cosine (dt_api_aux.cpp): the cosine weight, the gather probe
 // and the light probe from a gather probe's hit. Both sides are built with -ffp-contract=off, so they run the
 // same IEEE operations in the same order; nothing here calls libm beyond the sqrt of dt_math.h's normalized.

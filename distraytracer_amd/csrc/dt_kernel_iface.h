@@ -1,4 +1,5 @@
-// dt_kernel_iface.h — every extern "C" symbol dt_kernels.hip exports to the host library, declared once and
+// dt_kernel_iface.h — every extern "C" symbol the kernel units (dt_kernels.hip and one .hip per auxiliary
+// kernel family) export to the host library, declared once and
 // included by both sides (tests/test_kernel_iface.py): a definition that disagrees with it does not compile.
 #pragma once
 #include <hip/hip_runtime.h>

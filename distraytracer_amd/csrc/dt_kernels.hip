@@ -76,96 +76,6 @@ using namespace dtd;
 #ifndef DT_DONATE
 #define DT_DONATE 0
 #endif
-// DT_ISECT=1 (a fourth compilation, build/dt_kernels_isect.o): only dt_isect_kernel, the intersection
-// micro-benchmark, so that its call sites of the shared device functions stay out of the trace kernel's
-// object
-#ifndef DT_ISECT
-#define DT_ISECT 0
-#endif
-// DT_FEAT=1 (a fifth compilation, build/dt_kernels_feat.o): only dt_features_kernel, the first-hit
-// feature buffers of dt_render_features, for the same reason
-#ifndef DT_FEAT
-#define DT_FEAT 0
-#endif
-// DT_RAYQ=1 (a sixth compilation, build/dt_kernels_rayq.o): only dt_rayq_kernel and dt_rayq_occl_kernel,
-// the ray queries of dt_trace_rays and dt_rays_occluded, for the same reason
-#ifndef DT_RAYQ
-#define DT_RAYQ 0
-#endif
-// DT_MATTE=1 (a seventh compilation, build/dt_kernels_matte.o): only dt_mattes_kernel, the ranked per-pixel
-// group coverage of dt_render_mattes, for the same reason
-#ifndef DT_MATTE
-#define DT_MATTE 0
-#endif
-// DT_FEATP=1 (an eighth compilation, build/dt_kernels_featp.o): only dt_features_path_kernel, the
-// specular-path feature buffers of dt_render_features_path, for the same reason
-#ifndef DT_FEATP
-#define DT_FEATP 0
-#endif
-#if DT_FEATP
-#include "dt_guide.h"
-#endif
-// DT_OCCL=1 (a ninth compilation, build/dt_kernels_occl.o): only dt_occlusion_kernel, the ambient-occlusion
-// and per-light visibility planes of dt_render_occlusion, for the same reason
-#ifndef DT_OCCL
-#define DT_OCCL 0
-#endif
-// DT_POCCL=1 (a tenth compilation, build/dt_kernels_poccl.o): only dt_points_occl_kernel, the occlusion
-// queries of dt_points_occlusion at surface points the caller supplies, for the same reason
-#ifndef DT_POCCL
-#define DT_POCCL 0
-#endif
-#if DT_OCCL || DT_POCCL
-#include "dt_occl.h"
-#endif
-// DT_MHIT=1 (an eleventh compilation, build/dt_kernels_mhit.o): only dt_rayq_multi_kernel, the multi-hit ray
-// query of dt_trace_rays_multi in its four list capacities, for the same reason
-#ifndef DT_MHIT
-#define DT_MHIT 0
-#endif
-// DT_CAMRAYS=1 (a twelfth compilation, build/dt_kernels_camr.o): only dt_camera_rays_kernel, the render's camera
-// rays as arrays (dt_camera_rays), for the same reason
-#ifndef DT_CAMRAYS
-#define DT_CAMRAYS 0
-#endif
-// DT_TRANSMIT=1 (a thirteenth compilation, build/dt_kernels_transmit.o): only dt_rayq_transmit_kernel, the
-// transmittance ray query of dt_rays_transmittance in its five list capacities, for the same reason
-#ifndef DT_TRANSMIT
-#define DT_TRANSMIT 0
-#endif
-// DT_POCCLG=1 (a fourteenth compilation, build/dt_kernels_pocclg.o): only dt_points_occl_glass_kernel, the
-// occlusion queries of dt_points_occlusion_glass, whose probes pass through glass; DT_POCCL's source with the
-// transmittance walk in the place of the any-hit walk, for the same reason
-#ifndef DT_POCCLG
-#define DT_POCCLG 0
-#endif
-#if DT_POCCLG
-#include "dt_occl.h"
-#endif
-// DT_RAYPATH=1 (a fifteenth compilation, build/dt_kernels_rpath.o): only dt_rayq_path_kernel, the path ray query
-// of dt_trace_rays_path (dt_features_path_kernel's chain per caller-supplied ray), for the same reason
-#ifndef DT_RAYPATH
-#define DT_RAYPATH 0
-#endif
-#if DT_RAYPATH
-#include "dt_guide.h"
-#endif
-// DT_PIRR=1 (a sixteenth compilation, build/dt_kernels_pirr.o): only dt_points_irr_kernel, the irradiance queries
-// of dt_points_irradiance at surface points the caller supplies, for the same reason
-#ifndef DT_PIRR
-#define DT_PIRR 0
-#endif
-#if DT_PIRR
-#include "dt_irr.h"
-#endif
-// DT_PVIS=1 (a seventeenth compilation, build/dt_kernels_pvis.o): only dt_points_vis_kernel and
-// dt_points_vis_sum_kernel, the mutual visibility of two point sets (dt_points_visibility), for the same reason
-#ifndef DT_PVIS
-#define DT_PVIS 0
-#endif
-#if DT_PVIS
-#include "dt_irr.h"
-#endif
 // DT_W5=1 (build/dt_kernels_w5.o): the trace kernel at 5 waves per SIMD (96 VGPRs, under 8 KiB of
 // LDS per wave: DT_PSUM_LDS=2), launched for one-pixel-per-wave work (spp >= 64; never
 // with more than 8 pixels per wave, the slots DT_PSUM_LDS=2 keeps)
@@ -1723,127 +1633,6 @@ __device__ __forceinline__ bool closest_hit_walk(const DScene& S, const DParams&
   return any;
 }
 
-// Multi-hit walks (dt_rayq_multi_kernel, include/dt.h dt_trace_rays_multi): a lane's K nearest hits, sorted by
-// the key (t, shape) ascending; an empty slot holds (FLT_MAX, INT_MAX), which every hit's key (t < FLT_MAX)
-// precedes, so the number of hits is the number of slots with t < FLT_MAX and no count is carried. The
-// list must stay in registers: every slot is named by a constant (the recursion over J below, no loop to
-// unroll, no dynamic index that would send the array to scratch).
-template <int K>
-struct HitList {
-  float t[K];
-  int s[K];
-};
-
-template <int K>
-__device__ __forceinline__ void hitlist_clear(HitList<K>& L)
-{
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    L.t[j] = FLT_MAX;
-    L.s[j] = 0x7fffffff;
-  }
-}
-
-__device__ __forceinline__ bool hitkey_less(float t, int s, float t1, int s1)
-{
-  return t < t1 || (t == t1 && s < s1);
-}
-
-// Slots J .. 0 of a compare-and-shift insertion, from the back: slot J takes slot J-1 where the key precedes
-// that one too (read before the step below overwrites it), the key where it precedes slot J only. `here`: on,
-// and the key precedes slot J. One key compare per slot.
-template <int K, int J>
-__device__ __forceinline__ void hitlist_step(HitList<K>& L, bool on, float t, int s, bool here)
-{
-  if constexpr (J > 0) {
-    const bool prev = on && hitkey_less(t, s, L.t[J - 1], L.s[J - 1]);
-    L.t[J] = prev ? L.t[J - 1] : here ? t : L.t[J];
-    L.s[J] = prev ? L.s[J - 1] : here ? s : L.s[J];
-    hitlist_step<K, J - 1>(L, on, t, s, prev);
-  } else {
-    L.t[0] = here ? t : L.t[0];
-    L.s[0] = here ? s : L.s[0];
-  }
-}
-
-template <int K>
-__device__ __forceinline__ void hitlist_insert(HitList<K>& L, bool on, float t, int s)
-{
-  hitlist_step<K, K - 1>(L, on, t, s, on && hitkey_less(t, s, L.t[K - 1], L.s[K - 1]));
-}
-
-// The first entry, and the rest moved up by one (the attribute loop of dt_rayq_multi_kernel takes the hits
-// one by one through slot 0, so its runtime trip count indexes nothing)
-template <int K>
-__device__ __forceinline__ void hitlist_pop(HitList<K>& L, float& t, int& s)
-{
-  t = L.t[0];
-  s = L.s[0];
-#pragma unroll
-  for (int j = 0; j + 1 < K; ++j) {
-    L.t[j] = L.t[j + 1];
-    L.s[j] = L.s[j + 1];
-  }
-  L.t[K - 1] = FLT_MAX;
-  L.s[K - 1] = 0x7fffffff;
-}
-
-// closest_hit_walk's structure at shift 0 (MODE 0: finite rays on the fast tree; 1: the reference tree, exact
-// for any wave), with every gathered shape tested on its own (t enters as FLT_MAX, nothing carried) and kept
-// in the lane's list; a hit is a true return with t < FLT_MAX (false for NaN and for the edge-on
-// checkerboard return, which leaves t alone). The list is a function of the set of gathered shapes only (a
-// total order on (t, shape), every shape in one leaf), so neither tree nor visiting order shows in it, and
-// the edge-on re-walk of closest_hit has no counterpart here.
-// Culling: closest_hit_walk's bound, from the K-th distance once the list is full (tcull = FLT_MAX before).
-// A hit that could still enter the list has t <= t_K, at a point of its shape, hence inside the leaf's box:
-// the box's entry parameter is <= t up to the rounding of the two float computations, which the bound's
-// relative 1e-4 and absolute 1e-4 cover as they do for closest_hit_walk's t_min, so the leaf passes
-// tmin <= tcull, equal t included. t_K only shrinks, so with the monotone finite-ray slab test a lane that
-// failed an ancestor fails below it too (no resume point, as in closest_hit_walk). MODE 1 does not cull
-// (node_hit<true> reads no tcull).
-template <int MODE, int K>
-__device__ __forceinline__ void multi_hit_walk(const DScene& S, const DParams& P, const Walk& w, bool active, V3 ray,
-                                               V3 org, HitList<K>& L)
-{
-  static_assert(MODE == 0 || MODE == 1, "the shift is 0: never the bump tree");
-  constexpr bool GENERAL = MODE == 1;
-  const bool ftree = !GENERAL && P.n_fnodes > 0 && (P.ftree_mode & 1);
-  const DNodeDev* const NODES = ftree ? S.fnodes : S.nodes;
-  const int n_nodes = ftree ? P.n_fnodes : P.n_nodes;
-  int resume = active ? 0 : 0x7fffffff;
-  const unsigned long long am = __ballot(active);
-  int i = 0;
-  while (i < n_nodes) {
-    const DNodeDev nd = cas(NODES)[i];
-    const bool act = GENERAL ? resume <= i : inv(am);
-    const float tk = L.t[K - 1];
-    const float tcull = tk == FLT_MAX ? FLT_MAX : tk * 1.0001f + 1e-4f;
-    const unsigned long long hbm = node_mask<GENERAL>(w, nd, 0.0f, org, tcull, am, act);
-    const bool hb = inv(hbm);
-    if (nd.meta & DN_LEAF) {
-      if (hbm) {
-        const int nq = (nd.meta & DN_SINGLE) ? 1 : nd.aux;
-        for (int q = 0; q < nq; ++q) {
-          int sid, type, off;
-          uint32_t flags;
-          leaf_shape(S, nd, q, sid, type, flags, off);
-          if (inv(hbm)) {
-            float t = FLT_MAX;
-            int ins = 0, cc = -1, edge = 0;
-            const bool ret = shape_hit(S, sid, type, flags, cas(S.geom) + off, ray, org, 0.0f, t, ins, cc, edge);
-            hitlist_insert(L, ret && t < FLT_MAX, t, sid);
-          }
-        }
-      }
-      if (GENERAL && act) resume = nd.skip;
-      i = i + 1;
-    } else {
-      if (GENERAL && act && !hb) resume = nd.skip;
-      i = hbm ? i + 1 : nd.skip;
-    }
-  }
-}
-
 // Closest hit of primary rays over their pixel block's candidate leaves (host_primlists.cpp), in
 // order of the smallest ray parameter each leaf's box can be reached at: once every lane's best hit
 // lies before the next entry, no later leaf can change a result. Same box filter, shape tests and
@@ -2157,126 +1946,6 @@ __device__ __forceinline__ bool occluded_walk(const DScene& S, const DParams& P,
   return inv(om);
 }
 
-#if DT_TRANSMIT || DT_POCCLG
-// Transmittance walks (dt_rayq_transmit_kernel, dt_points_occl_glass_kernel; include/dt.h
-// dt_rays_transmittance): the any-hit walk with a filter. A shape counts for a lane as it occludes it in
-// occluded_walk (not the skip shape, shape_shadow true); a counting shape that is not glass blocks the lane,
-// which retires as an occluded lane does there; a counting glass shape adds one to the lane's `panes` and, for
-// K >= 1, its index to the lane's list, and the lane walks on. The wave leaves the walk when every active lane
-// is blocked or the tree is exhausted.
-// Counting precondition: a plain count is right because every shape sits in exactly one leaf of either tree.
-// The reference tree's leaves are disjoint slices of the index list (host_bvh.cpp generate: each node hands
-// [0, slice) and [slice, n) to its two children), and the fast tree keeps each of those leaves exactly once
-// under new inner nodes (host_fasttree.cpp build_fast_tree: one LeafRef per reference leaf, none split or
-// copied). A lane reaches a leaf at most once in a walk (i only grows), so it tests a shape at most once, and
-// finite waves take the fast tree as occluded_walk<0> does; nothing here falls back to the reference tree.
-// The box cull is occluded_walk's (shadow_tcull): a culled box holds no shape that can count, glass or not.
-// The list holds the K smallest indices of the counting glass shapes, ascending; an empty slot holds INT_MAX.
-// It must stay in registers: every slot is named by a constant, as in HitList (K = 0: no list at all).
-template <int K>
-struct PaneList {
-  int s[K > 0 ? K : 1];
-};
-
-template <int K>
-__device__ __forceinline__ void panelist_clear(PaneList<K>& L)
-{
-#pragma unroll
-  for (int j = 0; j < (K > 0 ? K : 1); ++j) L.s[j] = 0x7fffffff;
-}
-
-// hitlist_step with the shape index alone as the key
-template <int K, int J>
-__device__ __forceinline__ void panelist_step(PaneList<K>& L, bool on, int s, bool here)
-{
-  if constexpr (J > 0) {
-    const bool prev = on && s < L.s[J - 1];
-    L.s[J] = prev ? L.s[J - 1] : here ? s : L.s[J];
-    panelist_step<K, J - 1>(L, on, s, prev);
-  } else {
-    L.s[0] = here ? s : L.s[0];
-  }
-}
-
-template <int K>
-__device__ __forceinline__ void panelist_insert(PaneList<K>& L, bool on, int s)
-{
-  if constexpr (K > 0) panelist_step<K, K - 1>(L, on, s, on && s < L.s[K - 1]);
-}
-
-// the first entry, and the rest moved up by one (hitlist_pop)
-template <int K>
-__device__ __forceinline__ int panelist_pop(PaneList<K>& L)
-{
-  const int s = L.s[0];
-#pragma unroll
-  for (int j = 0; j + 1 < K; ++j) L.s[j] = L.s[j + 1];
-  L.s[K > 0 ? K - 1 : 0] = 0x7fffffff;
-  return s;
-}
-
-// shadow_leaf with the filter: bm collects the blocked lanes
-template <int K>
-__device__ __forceinline__ void transmit_leaf(const DScene& S, const DNodeDev& nd, unsigned long long hbm,
-                                              unsigned long long& bm, int& panes, PaneList<K>& L, V3 sn, V3 sstart,
-                                              float t_max, int skip_shape)
-{
-  const int nq = (nd.meta & DN_SINGLE) ? 1 : nd.aux;
-  for (int q = 0; q < nq; ++q) {
-    int sid, type, off;
-    uint32_t flags;
-    leaf_shape(S, nd, q, sid, type, flags, off);
-    const unsigned long long tm = sid != skip_shape ? hbm & ~bm : 0ull;   // lanes that test this shape
-    if (!tm) continue;
-    bool o = false;
-    if (inv(tm)) o = shape_shadow(type, flags, cas(S.geom) + off, sn, sstart, t_max, 0.0f);
-    if (uni(cas(S.mat)[sid].material) == DT_MAT_GLASS) {   // wave-uniform
-      panes += o ? 1 : 0;
-      panelist_insert(L, o, sid);
-    } else {
-      bm |= __ballot(o);
-    }
-  }
-}
-
-// occluded_walk<0/1> at shift 0 with transmit_leaf: true for a blocked lane
-template <int MODE, int K>
-__device__ __forceinline__ bool transmit_walk(const DScene& S, const DParams& P, const Walk& w, bool active, V3 bstart,
-                                              V3 sn, V3 sstart, float t_max, int skip_shape, int& panes,
-                                              PaneList<K>& L)
-{
-  static_assert(MODE == 0 || MODE == 1, "the shift is 0: never the bump tree");
-  constexpr bool GENERAL = MODE == 1;
-  const bool ftree = !GENERAL && P.n_fnodes > 0 && (P.ftree_mode & 2);
-  const DNodeDev* const NODES = ftree ? S.fnodes : S.nodes;
-  const int n_nodes = ftree ? P.n_fnodes : P.n_nodes;
-  int resume = active ? 0 : 0x7fffffff;
-  const unsigned long long am = __ballot(active);
-  unsigned long long bm = 0;   // blocked lanes
-  const float tcull = shadow_tcull(t_max);
-  int i = 0;
-  while (i < n_nodes) {
-    const DNodeDev nd = cas(NODES)[i];
-    const bool act = GENERAL ? resume <= i : inv(am & ~bm);   // see closest_hit_walk
-    const unsigned long long hbm = node_mask<GENERAL>(w, nd, 0.0f, bstart, tcull, am & ~bm, act);
-    const bool hb = inv(hbm);
-    if (nd.meta & DN_LEAF) {
-      if (hbm) transmit_leaf(S, nd, hbm, bm, panes, L, sn, sstart, t_max, skip_shape);
-      if (GENERAL) {
-        if (act) resume = inv(bm) ? 0x7fffffff : nd.skip;
-        if (!__ballot(resume != 0x7fffffff)) break;
-      } else if (!(am & ~bm)) {
-        break;
-      }
-      i = i + 1;
-    } else {
-      if (GENERAL && act && !hb) resume = nd.skip;
-      i = hbm ? i + 1 : nd.skip;
-    }
-  }
-  return inv(bm);
-}
-#endif
 
 // The shadow test over a cell's candidate list (host_shadowgrid.cpp): the same box test and
 // shape tests as the walk, on the only leaves that can hold an occluder for this cell and light.
@@ -2632,31 +2301,6 @@ struct Ctx {
   Rng rng;
 };
 
-#if DT_FEAT || DT_RAYQ || DT_FEATP || DT_OCCL || DT_MHIT || DT_RAYPATH || DT_PIRR
-// What dt_features_kernel takes from run_pass (dt_rayq_kernel, dt_rayq_multi_kernel and dt_features_path_kernel too), as copies for its build only: with run_pass calling
-// these helpers, some trace builds' objects came out as other bytes (the room builds with hit_color,
-// every build with texel_color), and the product kernels' objects are to stay byte-identical.
-// hit_color: the colour the reference's intersect() leaves in the hit shape (a Checkerboard's square,
-// ccol), else the shape's own.
-__device__ __forceinline__ V3 hit_color(GP g, const DMat& M, int ccol)
-{
-  return ccol >= 0 ? G3(g, ccol) : v3a(M.color);
-}
-
-// texel_color: the texel at (tu, tv) / 255, the light loop's lookup (float products, truncation, the
-// index clamped to the texture).
-__device__ __forceinline__ V3 texel_color(const DScene& S, const DMat& M, double tu, double tv)
-{
-  double dims0 = M.tex_w;
-  int x_tex = (int)((float)(M.tex_w - 1) * (float)tu);
-  int y_tex = (int)((float)(M.tex_h - 1) * (float)tv);
-  int uv_ind = (int)(y_tex * dims0 + x_tex);
-  if (uv_ind < 0) uv_ind = 0;
-  if (uv_ind >= M.tex_w * M.tex_h) uv_ind = M.tex_w * M.tex_h - 1;
-  const uint8_t* px = S.tex + M.tex_off + (int64_t)uv_ind * M.tex_ch;
-  return v3(px[0] / 255.0, px[1] / 255.0, px[2] / 255.0);
-}
-#endif
 
 __device__ __forceinline__ bool is_refl_material(int m)
 {
@@ -3539,1788 +3183,10 @@ struct DLaunch {
 #ifndef DT_TRACE_MIN_WAVES
 #define DT_TRACE_MIN_WAVES 1
 #endif
-#ifndef DT_REPRO
-#define DT_REPRO 0
-#endif
-#if DT_REPRO
-// DT_REPRO=1 (tools/call_repro: never part of libdt.so): the sky of dt_sky_miss_kernel (cpp:1074-1092,
-// cloudColor of mcam * focalPoint per pixel) through cloud_color_lane inlined and through the same
-// function behind a real call, on the same pixels, for the called-function defect
-__device__ __noinline__ V3 cloud_color_lane_call(const DParams& P, const float* __restrict__ zs, V3 ray)
-{
-  return cloud_color_lane(P, zs, ray);
-}
-template <bool CALL>
-__device__ __forceinline__ void repro_sky(const DParams* __restrict__ Pp, const float* __restrict__ zs, int x0, int y0,
-                                          int w, int n, double* __restrict__ out)
-{
-  const DParams& P = *Pp;
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q < n) {
-    const int x = x0 + q % w, y = y0 + q / w;
-    const V3 eye = v3a(P.eye), X = v3a(P.X), Y = v3a(P.Y), Z = v3a(P.Z);
-    float aa = P.l + (P.r - P.l) * (float)x / (float)P.xRes;
-    float bb = P.b + (P.t - P.b) * (float)y / (float)P.yRes;
-    V3 rd = sub(add(mul(aa, X), mul(bb, Y)), mul(P.near_plane, Z));
-    V3 fp = add(eye, mul(P.focal_length, rd));
-    V3 pt;
-    pt.x = ((P.sky_m[0][0] * fp.x + P.sky_m[0][1] * fp.y) + P.sky_m[0][2] * fp.z) + P.sky_m[0][3] * 1.0;
-    pt.y = ((P.sky_m[1][0] * fp.x + P.sky_m[1][1] * fp.y) + P.sky_m[1][2] * fp.z) + P.sky_m[1][3] * 1.0;
-    pt.z = ((P.sky_m[2][0] * fp.x + P.sky_m[2][1] * fp.y) + P.sky_m[2][2] * fp.z) + P.sky_m[2][3] * 1.0;
-    const V3 c = CALL ? cloud_color_lane_call(P, zs, pt) : cloud_color_lane(P, zs, pt);
-    out[3 * q] = c.x;
-    out[3 * q + 1] = c.y;
-    out[3 * q + 2] = c.z;
-  }
-}
-extern "C" __global__ void __launch_bounds__(256) dt_repro_inline(const DParams* Pp, const float* zs, int x0, int y0,
-                                                                  int w, int n, double* out)
-{
-  repro_sky<false>(Pp, zs, x0, y0, w, n, out);
-}
-extern "C" __global__ void __launch_bounds__(256) dt_repro_call(const DParams* Pp, const float* zs, int x0, int y0,
-                                                                int w, int n, double* out)
-{
-  repro_sky<true>(Pp, zs, x0, y0, w, n, out);
-}
-extern "C" hipError_t dt_repro_launch(int call, const void* Pp, const float* zs, int x0, int y0, int w, int n,
-                                      double* out)
-{
-  if (call)
-    hipLaunchKernelGGL(dt_repro_call, dim3((n + 255) / 256), dim3(256), 0, 0, (const DParams*)Pp, zs, x0, y0, w, n, out);
-  else
-    hipLaunchKernelGGL(dt_repro_inline, dim3((n + 255) / 256), dim3(256), 0, 0, (const DParams*)Pp, zs, x0, y0, w, n, out);
-  return hipGetLastError();
-}
-#else   // !DT_REPRO
-#if DT_ISECT
-// Intersection micro-benchmark (2^24 primary rays of the C3 camera): rayColor's first
-// step for the camera's primary rays (getDOFSamples + getPerspEyeRay, cpp:195-210 / 1044-1072; the
-// BVH gather and closest hit, cpp:491-538), taken exactly as the trace kernel takes it for a root
-// ray -- the pixel block's primary list when the wave's rays share a block, else the fast tree --
-// one ray per lane. Ray r (pixel-major, DT_ISECT_RPP rays per pixel): q = r / RPP, pixel q mod W*H
-// (raster order), sample r mod RPP + RPP * (q div W*H). Out: the hit shape (-1: none) and its t
-// (FLT_MAX: none), as oracle/oracle.c or_primary_hit.
-#define DT_ISECT_RPP 8
-extern "C" __global__ void __launch_bounds__(64)
-dt_isect_kernel(const DLaunch* __restrict__ Lp, int64_t first, int64_t n, int32_t* __restrict__ hit_shape,
-                float* __restrict__ hit_t)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  Counters cnt;
-  cnt.wc = wc_lds;
-  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
-  Ctx c;
-  c.S = &S;
-  c.P = &P;
-  c.rng.k0 = P.seed;
-  c.rng.k1 = (uint32_t)P.frame;
-  const int64_t npx = (int64_t)P.xRes * P.yRes;
-  const bool lists = P.pl_block > 0 && P.n_fnodes > 0 && (P.ftree_mode & 1);
-  for (int64_t base = (int64_t)blockIdx.x * DT_WAVE; base < n; base += (int64_t)gridDim.x * DT_WAVE) {
-    const int64_t i = base + lane;
-    const bool act = i < n;
-    const int64_t r = first + i;
-    const int64_t q = r / DT_ISECT_RPP;
-    const int64_t p = q % npx;
-    const int x = (int)(p % P.xRes), y = (int)(p / P.xRes);
-    c.rng.pixel = (uint32_t)(y * P.xRes + x);
-    c.rng.sample = (uint32_t)(r % DT_ISECT_RPP + DT_ISECT_RPP * (q / npx));
-    V3 eye_sample = v3a(P.eye), ray0 = v3(0, 0, 0);
-    if (act) camera_ray(c, P, x, y, eye_sample, ray0);
-    int pblock = -1;
-    if (lists) {
-      const int blk = (y / P.pl_block) * P.pl_nbx + x / P.pl_block;
-      const int b0 = uni(blk);
-      if (!__ballot(act && blk != b0)) pblock = b0;
-    }
-    HitRec h;
-    const bool any = closest_hit(S, P, act, ray0, eye_sample, 0.0f, h, cnt, pblock);
-    if (act) {
-      const bool hit = any && h.shape >= 0;
-      hit_shape[i] = hit ? h.shape : -1;
-      hit_t[i] = hit ? h.t_min : FLT_MAX;
-    }
-  }
-  if (lane == 0) atomicAdd(S.stats + ST_WNODES, (unsigned long long)cnt.wnodes);
-}
-extern "C" hipError_t dt_launch_isect(const void* dev_launch, int64_t first, int64_t n, int32_t* hit_shape, float* hit_t,
-                                      int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_isect_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, first, n, hit_shape,
-                     hit_t);
-  return hipGetLastError();
-}
-extern "C" const void* dt_isect_kernel_ptr(void) { return (const void*)dt_isect_kernel; }
-#elif DT_FEAT
-// First-hit feature buffers (include/dt.h dt_render_features; no reference counterpart): for the samples
-// 0 .. n_samples-1 of every owned pixel, the render's own primary ray (the trace kernel's RNG pixel,
-// sample and key, camera_ray, closest_hit at shift 0 as dt_isect_kernel calls it) and, per hit, the
-// base colour (hit_color; texel_color or the border colour for textured shapes, as the shading loop
-// takes them), the root ray's normal (shape_norm + fixNorm) and the distance t * |ray|.
-// Items and lanes as the trace kernel's: spp >= 64, one pixel per wave, lane = sample, the pixel's
-// chunks in turn (the pixel block's primary list stays wave-uniform); spp < 64, P.ppw pixels per wave.
-// The per-pixel sums are f64, left to right in sample order: every lane writes its FT_N values to LDS
-// and lane FT_N * jj + k walks column k of pixel jj; one wave owns all chunks of a pixel, so the
-// sums carry over in LDS (fsum) from chunk to chunk. A miss writes zeros: the sums start at +0 and
-// x + 0 == x in every bit for every x a sum from +0 can hold (never -0), so it contributes nothing.
-enum { FT_A = 0, FT_N0 = 3, FT_D = 6, FT_H = 7, FT_N = 8 };
-extern "C" __global__ void __launch_bounds__(64)
-dt_features_kernel(const DLaunch* __restrict__ Lp, int n_samples, float* __restrict__ albedo,
-                   float* __restrict__ normal, float* __restrict__ depth, float* __restrict__ coverage,
-                   int32_t* __restrict__ shape_out)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  // (a row is 65 doubles: the FT_N column walkers of a pixel start 130 banks apart, not on one bank)
-  __shared__ double val[FT_N][DT_WAVE + 1];
-  __shared__ double fsum[FT_N][DT_WAVE];
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  Counters cnt;
-  cnt.wc = wc_lds;
-  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
-  Ctx c;
-  c.S = &S;
-  c.P = &P;
-  c.rng.k0 = P.seed;
-  c.rng.k1 = (uint32_t)P.frame;
-  const bool lists = P.pl_block > 0 && P.n_fnodes > 0 && (P.ftree_mode & 1);
-  const int group = P.ppw;
-  const int per = P.spp < DT_WAVE ? P.spp : DT_WAVE;
-  const int j = lane / per, sl = lane - j * per;
-  const int chunks = (n_samples + DT_WAVE - 1) / DT_WAVE;
-  for (int64_t item = blockIdx.x; item < P.n_items; item += gridDim.x) {
-    for (int idx = lane; idx < group * FT_N; idx += DT_WAVE) fsum[idx % FT_N][idx / FT_N] = 0;
-    int px_x = 0, px_y = 0;
-    int64_t px_off = 0;
-    bool px_valid = false;
-    pixel_of(P, item * group + (j < group ? j : 0), px_x, px_y, px_off, px_valid);
-    px_valid = px_valid && j < group;
-    for (int chunk = 0; chunk < chunks; ++chunk) {
-      const int sample = chunk * DT_WAVE + sl;
-      const bool valid = px_valid && sample < n_samples;
-      c.rng.pixel = (uint32_t)(px_y * P.xRes + px_x);
-      c.rng.sample = (uint32_t)sample;
-      V3 eye_sample = v3a(P.eye), ray0 = v3(0, 0, 0);
-      if (valid) camera_ray(c, P, px_x, px_y, eye_sample, ray0);
-      const unsigned long long vm = __ballot(valid);
-      bool hit = false;
-      HitRec h;
-      h.t_min = FLT_MAX; h.shape = -1; h.ccol = -1;
-      if (vm) {
-        int pblock = -1;
-        if (lists) {   // the block of the wave's valid pixels, when they share one
-          const int blk = (px_y / P.pl_block) * P.pl_nbx + px_x / P.pl_block;
-          const int b0 = __shfl(blk, (int)__builtin_ctzll(vm));
-          if (!__ballot(valid && blk != b0)) pblock = b0;
-        }
-        const bool any = closest_hit(S, P, valid, ray0, eye_sample, 0.0f, h, cnt, pblock);
-        hit = any && valid && h.shape >= 0;
-      }
-      V3 col = v3(0, 0, 0), nrm = v3(0, 0, 0);
-      double dist = 0;
-      if (hit) {
-        const int sid = h.shape;
-        const DShapeHdr hd = S.hdr[sid];
-        GP g = cas(S.geom) + hd.off;
-        const DMat& M = S.mat[sid];
-        const V3 p = add(eye_sample, mul(h.t_min, ray0));
-        nrm = shape_norm(hd.type, hd.flags, g, p, 0.0f, cnt.wc + WC_PRISM, h.ccol);
-        const V3 in = normalized(ray0);
-        if (dot(mul(1e4, in), nrm) >= 0) nrm = mul(-1, nrm);   // fixNorm
-        col = hit_color(g, M, h.ccol);
-        if (M.flags & DT_F_TEXTURE) {
-          double tu = 0, tv = 0;
-          const int uvt = shape_uv(hd.type, hd.flags, g, p, 0.0f, tu, tv);
-          if (uvt == 2) {
-            col = v3a(M.bordercolor);
-          } else if (uvt == 1 && M.tex >= 0) {
-            col = texel_color(S, M, tu, tv);
-            atomicAdd(cnt.wc + WC_TEX, 1u);
-          }
-          if (uvt != 0 && (tu < 0 || tv < 0 || tu > 1 || tv > 1)) atomicAdd(cnt.wc + WC_UV, 1u);
-        }
-        dist = (double)h.t_min * norm(ray0);
-      }
-      val[FT_A + 0][lane] = col.x; val[FT_A + 1][lane] = col.y; val[FT_A + 2][lane] = col.z;
-      val[FT_N0 + 0][lane] = nrm.x; val[FT_N0 + 1][lane] = nrm.y; val[FT_N0 + 2][lane] = nrm.z;
-      val[FT_D][lane] = dist;
-      val[FT_H][lane] = hit ? 1.0 : 0.0;
-      if (valid && sample == 0 && shape_out)
-        shape_out[P.layout == DT_OUT_SLAB ? px_off / 3 : (int64_t)(P.yRes - 1 - px_y) * P.xRes + px_x] = hit ? h.shape : -1;
-      __syncthreads();
-      int ns = n_samples - chunk * DT_WAVE;
-      if (ns > per) ns = per;
-      for (int idx = lane; idx < group * FT_N; idx += DT_WAVE) {
-        const int jj = idx / FT_N, k = idx - jj * FT_N, base = jj * per;
-        double s = fsum[k][jj];
-        for (int i = 0; i < ns; ++i) s = s + val[k][base + i];
-        fsum[k][jj] = s;
-      }
-      __syncthreads();
-    }
-    if (lane < group) {
-      int qx, qy;
-      int64_t qo;
-      bool qv;
-      pixel_of(P, item * group + lane, qx, qy, qo, qv);
-      if (qv) {
-        const int64_t q = P.layout == DT_OUT_SLAB ? qo / 3 : (int64_t)(P.yRes - 1 - qy) * P.xRes + qx;
-        const double n = (double)n_samples, H = fsum[FT_H][lane];
-        if (albedo)
-          for (int k = 0; k < 3; ++k) albedo[3 * q + k] = (float)(fsum[FT_A + k][lane] / n);
-        if (normal)
-          for (int k = 0; k < 3; ++k) normal[3 * q + k] = (float)(fsum[FT_N0 + k][lane] / n);
-        if (coverage) coverage[q] = (float)(H / n);
-        if (depth) depth[q] = H > 0 ? (float)(fsum[FT_D][lane] / H) : 0.0f;
-      }
-    }
-    __syncthreads();   // the sums are read before the next item clears them
-  }
-  __syncthreads();
-  const int st_of[WC_N] = {ST_RAYS, ST_SHADOW, ST_TEX, ST_STACK, ST_REFL, ST_GLOSSY, ST_UV, ST_PRISM, ST_SPHL};
-  if (lane < WC_N) {
-    const unsigned long long v = wc_lds[lane];
-    if (v) atomicAdd(S.stats + st_of[lane], v);
-  }
-}
-extern "C" hipError_t dt_launch_features(const void* dev_launch, int n_samples, float* albedo, float* normal, float* depth,
-                                         float* coverage, int32_t* shape, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_features_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n_samples, albedo,
-                     normal, depth, coverage, shape);
-  return hipGetLastError();
-}
-extern "C" const void* dt_features_kernel_ptr(void) { return (const void*)dt_features_kernel; }
-#elif DT_FEATP
-// Specular-path feature buffers (include/dt.h dt_render_features_path; no reference counterpart): the
-// samples, items, lanes and LDS column sums of dt_features_kernel, but a sample's guide ray follows up to
-// max_bounces perfect specular bounces (dt_guide.h guide_bounce: the trace kernel's mirror and glass
-// arithmetic without the Fresnel weights) and the planes describe the surface it ends on. Segment 0 is
-// the primary ray through the pixel block's primary list, as dt_features_kernel takes it; the later
-// segments go as dt_rayq_kernel's rays do (pblock -1, the lanes still travelling as the mask, a void ray
-// -- the refraction at normal incidence, 1 / sin_theta = inf -- not traced: the sample is a miss).
-// The bounce loop is wave-uniform and capped by max_bounces: after the first bounce the wave visits the
-// union of its lanes' nodes, and lanes whose sample has ended wait for the others.
-// One more column than dt_features_kernel: the segments a sample followed beyond the first (counted for
-// samples that end as a miss too).
-enum { FP_A = 0, FP_N0 = 3, FP_D = 6, FP_H = 7, FP_B = 8, FP_N = 9 };
-extern "C" __global__ void __launch_bounds__(64)
-dt_features_path_kernel(const DLaunch* __restrict__ Lp, int n_samples, int max_bounces, float* __restrict__ albedo,
-                        float* __restrict__ normal, float* __restrict__ depth, float* __restrict__ coverage,
-                        int32_t* __restrict__ shape_out, float* __restrict__ bounces)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  // (a row is 65 doubles: the FP_N column walkers of a pixel start 130 banks apart, not on one bank)
-  __shared__ double val[FP_N][DT_WAVE + 1];
-  __shared__ double fsum[FP_N][DT_WAVE];
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  Counters cnt;
-  cnt.wc = wc_lds;
-  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
-  Ctx c;
-  c.S = &S;
-  c.P = &P;
-  c.rng.k0 = P.seed;
-  c.rng.k1 = (uint32_t)P.frame;
-  const bool lists = P.pl_block > 0 && P.n_fnodes > 0 && (P.ftree_mode & 1);
-  const int group = P.ppw;
-  const int per = P.spp < DT_WAVE ? P.spp : DT_WAVE;
-  const int j = lane / per, sl = lane - j * per;
-  const int chunks = (n_samples + DT_WAVE - 1) / DT_WAVE;
-  unsigned long long traced = 0;   // wave-uniform: the segments traced
-  for (int64_t item = blockIdx.x; item < P.n_items; item += gridDim.x) {
-    for (int idx = lane; idx < group * FP_N; idx += DT_WAVE) fsum[idx % FP_N][idx / FP_N] = 0;
-    int px_x = 0, px_y = 0;
-    int64_t px_off = 0;
-    bool px_valid = false;
-    pixel_of(P, item * group + (j < group ? j : 0), px_x, px_y, px_off, px_valid);
-    px_valid = px_valid && j < group;
-    for (int chunk = 0; chunk < chunks; ++chunk) {
-      const int sample = chunk * DT_WAVE + sl;
-      const bool valid = px_valid && sample < n_samples;
-      c.rng.pixel = (uint32_t)(px_y * P.xRes + px_x);
-      c.rng.sample = (uint32_t)sample;
-      V3 org = v3a(P.eye), ray = v3(0, 0, 0);
-      if (valid) camera_ray(c, P, px_x, px_y, org, ray);
-      bool live = valid;     // the sample's guide ray is still travelling
-      bool ended = false;    // ... it ended on a surface
-      int end_shape = -1, followed = 0;
-      V3 col = v3(0, 0, 0), nrm = v3(0, 0, 0);
-      double len = 0;        // the path's length so far
-      for (int k = 0; k <= max_bounces && __ballot(live); ++k) {
-        int pblock = -1;
-        if (k == 0) {
-          if (lists) {   // the block of the wave's valid pixels, when they share one
-            const int blk = (px_y / P.pl_block) * P.pl_nbx + px_x / P.pl_block;
-            const int b0 = __shfl(blk, (int)__builtin_ctzll(__ballot(live)));
-            if (!__ballot(live && blk != b0)) pblock = b0;
-          }
-        } else {
-          // a void ray is not traced: its sample is a miss
-          live = live && isfinite(org.x) && isfinite(org.y) && isfinite(org.z) && isfinite(ray.x) &&
-                 isfinite(ray.y) && isfinite(ray.z) && (ray.x != 0 || ray.y != 0 || ray.z != 0);
-          if (!live) { org = v3a(P.eye); ray = v3(0, 0, 0); }
-        }
-        const unsigned long long am = __ballot(live);
-        if (!am) break;
-        traced += (unsigned long long)__popcll(am);
-        HitRec h;
-        h.t_min = FLT_MAX; h.shape = -1; h.ccol = -1; h.inside = 0;
-        const bool any = closest_hit(S, P, live, ray, org, 0.0f, h, cnt, pblock);
-        const bool hit = any && live && h.shape >= 0;
-        live = hit;   // a miss ends the sample and adds nothing
-        if (hit) {
-          const int sid = h.shape;
-          const DShapeHdr hd = S.hdr[sid];
-          GP g = cas(S.geom) + hd.off;
-          const DMat& M = S.mat[sid];
-          const V3 p = add(org, mul(h.t_min, ray));
-          V3 nk = shape_norm(hd.type, hd.flags, g, p, 0.0f, cnt.wc + WC_PRISM, h.ccol);
-          const V3 in = normalized(ray);
-          if (dot(mul(1e4, in), nk) >= 0) nk = mul(-1, nk);   // fixNorm
-          len = len + (double)h.t_min * norm(ray);
-          int go = DT_GUIDE_STOP;
-          V3 ndir = v3(0, 0, 0), nstart = v3(0, 0, 0);
-          if (k < max_bounces) {
-            bool refl_err = false;
-            go = guide_bounce(P.reflect, P.nogloss, P.refr_air, P.refr_glass, M.material, M.flags, h.inside, in, nk, p,
-                              ndir, nstart, refl_err);
-            if (refl_err) atomicAdd(cnt.wc + WC_REFL, 1u);
-          }
-          if (go != DT_GUIDE_STOP) {
-            ray = ndir;
-            org = nstart;
-            followed += 1;
-          } else {
-            live = false;
-            ended = true;
-            end_shape = sid;
-            nrm = nk;
-            col = hit_color(g, M, h.ccol);
-            if (M.flags & DT_F_TEXTURE) {
-              double tu = 0, tv = 0;
-              const int uvt = shape_uv(hd.type, hd.flags, g, p, 0.0f, tu, tv);
-              if (uvt == 2) {
-                col = v3a(M.bordercolor);
-              } else if (uvt == 1 && M.tex >= 0) {
-                col = texel_color(S, M, tu, tv);
-                atomicAdd(cnt.wc + WC_TEX, 1u);
-              }
-              if (uvt != 0 && (tu < 0 || tv < 0 || tu > 1 || tv > 1)) atomicAdd(cnt.wc + WC_UV, 1u);
-            }
-          }
-        }
-      }
-      val[FP_A + 0][lane] = col.x; val[FP_A + 1][lane] = col.y; val[FP_A + 2][lane] = col.z;
-      val[FP_N0 + 0][lane] = nrm.x; val[FP_N0 + 1][lane] = nrm.y; val[FP_N0 + 2][lane] = nrm.z;
-      val[FP_D][lane] = ended ? len : 0.0;
-      val[FP_H][lane] = ended ? 1.0 : 0.0;
-      val[FP_B][lane] = (double)followed;
-      if (valid && sample == 0 && shape_out)
-        shape_out[P.layout == DT_OUT_SLAB ? px_off / 3 : (int64_t)(P.yRes - 1 - px_y) * P.xRes + px_x] = ended ? end_shape : -1;
-      __syncthreads();
-      int ns = n_samples - chunk * DT_WAVE;
-      if (ns > per) ns = per;
-      for (int idx = lane; idx < group * FP_N; idx += DT_WAVE) {
-        const int jj = idx / FP_N, kk = idx - jj * FP_N, base = jj * per;
-        double s = fsum[kk][jj];
-        for (int i = 0; i < ns; ++i) s = s + val[kk][base + i];
-        fsum[kk][jj] = s;
-      }
-      __syncthreads();
-    }
-    if (lane < group) {
-      int qx, qy;
-      int64_t qo;
-      bool qv;
-      pixel_of(P, item * group + lane, qx, qy, qo, qv);
-      if (qv) {
-        const int64_t q = P.layout == DT_OUT_SLAB ? qo / 3 : (int64_t)(P.yRes - 1 - qy) * P.xRes + qx;
-        const double n = (double)n_samples, H = fsum[FP_H][lane];
-        if (albedo)
-          for (int k = 0; k < 3; ++k) albedo[3 * q + k] = (float)(fsum[FP_A + k][lane] / n);
-        if (normal)
-          for (int k = 0; k < 3; ++k) normal[3 * q + k] = (float)(fsum[FP_N0 + k][lane] / n);
-        if (coverage) coverage[q] = (float)(H / n);
-        if (depth) depth[q] = H > 0 ? (float)(fsum[FP_D][lane] / H) : 0.0f;
-        if (bounces) bounces[q] = (float)(fsum[FP_B][lane] / n);
-      }
-    }
-    __syncthreads();   // the sums are read before the next item clears them
-  }
-  __syncthreads();
-  const int st_of[WC_N] = {ST_RAYS, ST_SHADOW, ST_TEX, ST_STACK, ST_REFL, ST_GLOSSY, ST_UV, ST_PRISM, ST_SPHL};
-  if (lane < WC_N) {
-    const unsigned long long v = lane == WC_RAYS ? traced : wc_lds[lane];
-    if (v) atomicAdd(S.stats + st_of[lane], v);
-  }
-}
-extern "C" hipError_t dt_launch_features_path(const void* dev_launch, int n_samples, int max_bounces, float* albedo,
-                                              float* normal, float* depth, float* coverage, int32_t* shape,
-                                              float* bounces, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_features_path_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n_samples,
-                     max_bounces, albedo, normal, depth, coverage, shape, bounces);
-  return hipGetLastError();
-}
-extern "C" const void* dt_features_path_kernel_ptr(void) { return (const void*)dt_features_path_kernel; }
-#elif DT_RAYQ || DT_MHIT || DT_TRANSMIT || DT_RAYPATH
-// Ray queries (include/dt.h dt_trace_rays, dt_rays_occluded, dt_trace_rays_multi, dt_rays_transmittance, dt_trace_rays_path; no reference counterpart): rays the caller
-// hands over in memory, 3 doubles of start and of direction each, one ray per lane, 64 consecutive rays
-// per wave, grid-stride over the waves as dt_isect_kernel. The walks are the wave-uniform ones of the
-// trace kernel (node and shape data through scalar loads, the lanes' decisions as masks), so a wave
-// visits the union of its lanes' nodes: rays that lie together in memory should lie together in space.
-//
-// A void ray (a non-finite component, or an all-zero direction) is an inactive lane: it is never traced
-// and does not reach make_walk's ballots, so it neither sends its wave down the exact walk nor changes
-// a neighbour's answer.
-__device__ __forceinline__ bool rayq_load(const double* __restrict__ start, const double* __restrict__ dir, int64_t i,
-                                          bool in, V3& org, V3& ray)
-{
-  org = v3(0, 0, 0);
-  ray = v3(0, 0, 0);
-  if (!in) return false;
-  const V3 o = v3(start[3 * i], start[3 * i + 1], start[3 * i + 2]);
-  const V3 d = v3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
-  const bool live = isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(d.x) && isfinite(d.y) &&
-                    isfinite(d.z) && (d.x != 0 || d.y != 0 || d.z != 0);
-  if (live) {
-    org = o;
-    ray = d;
-  }
-  return live;
-}
-
-#if DT_RAYQ
-// dt_trace_rays: rayColor's gather and closest hit (cpp:491-538) at shift 0, as dt_isect_kernel takes it
-// without a primary list (pblock -1: the fast tree; the exact walk for a wave with an axis-parallel ray
-// and after an edge-on checkerboard hit), and per hit what dt_features_kernel computes for one sample.
-// Every plane is optional; the normal and the colour are computed only for the planes that take them, so
-// the counters belong to the planes: prism_norm_fallback to `normal`, tex_fetches and uv_out_of_range
-// to `albedo`.
-extern "C" __global__ void __launch_bounds__(64)
-dt_rayq_kernel(const DLaunch* __restrict__ Lp, int64_t n, const double* __restrict__ start,
-               const double* __restrict__ dir, int32_t* __restrict__ shape_out, float* __restrict__ t_out,
-               double* __restrict__ point, double* __restrict__ normal, double* __restrict__ albedo)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  Counters cnt;
-  cnt.wc = wc_lds;
-  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
-  unsigned long long traced = 0;   // wave-uniform
-  for (int64_t base = (int64_t)blockIdx.x * DT_WAVE; base < n; base += (int64_t)gridDim.x * DT_WAVE) {
-    const int64_t i = base + lane;
-    const bool in = i < n;
-    V3 org, ray;
-    const bool act = rayq_load(start, dir, i, in, org, ray);
-    const unsigned long long am = __ballot(act);
-    traced += (unsigned long long)__popcll(am);
-    HitRec h;
-    h.t_min = FLT_MAX; h.shape = -1; h.ccol = -1;
-    bool hit = false;
-    if (am) {
-      const bool any = closest_hit(S, P, act, ray, org, 0.0f, h, cnt, /*pblock*/ -1);
-      hit = any && act && h.shape >= 0;
-    }
-    V3 p = v3(0, 0, 0), nrm = v3(0, 0, 0), col = v3(0, 0, 0);
-    if (hit && (point || normal || albedo)) {
-      const int sid = h.shape;
-      const DShapeHdr hd = S.hdr[sid];
-      GP g = cas(S.geom) + hd.off;
-      const DMat& M = S.mat[sid];
-      p = add(org, mul(h.t_min, ray));
-      if (normal) {
-        nrm = shape_norm(hd.type, hd.flags, g, p, 0.0f, cnt.wc + WC_PRISM, h.ccol);
-        const V3 in_dir = normalized(ray);
-        if (dot(mul(1e4, in_dir), nrm) >= 0) nrm = mul(-1, nrm);   // fixNorm
-      }
-      if (albedo) {
-        col = hit_color(g, M, h.ccol);
-        if (M.flags & DT_F_TEXTURE) {
-          double tu = 0, tv = 0;
-          const int uvt = shape_uv(hd.type, hd.flags, g, p, 0.0f, tu, tv);
-          if (uvt == 2) {
-            col = v3a(M.bordercolor);
-          } else if (uvt == 1 && M.tex >= 0) {
-            col = texel_color(S, M, tu, tv);
-            atomicAdd(cnt.wc + WC_TEX, 1u);
-          }
-          if (uvt != 0 && (tu < 0 || tv < 0 || tu > 1 || tv > 1)) atomicAdd(cnt.wc + WC_UV, 1u);
-        }
-      }
-    }
-    if (in) {
-      if (shape_out) shape_out[i] = hit ? h.shape : -1;
-      if (t_out) t_out[i] = hit ? h.t_min : FLT_MAX;
-      if (point) { point[3 * i] = p.x; point[3 * i + 1] = p.y; point[3 * i + 2] = p.z; }
-      if (normal) { normal[3 * i] = nrm.x; normal[3 * i + 1] = nrm.y; normal[3 * i + 2] = nrm.z; }
-      if (albedo) { albedo[3 * i] = col.x; albedo[3 * i + 1] = col.y; albedo[3 * i + 2] = col.z; }
-    }
-  }
-  __syncthreads();
-  const int st_of[WC_N] = {ST_RAYS, ST_SHADOW, ST_TEX, ST_STACK, ST_REFL, ST_GLOSSY, ST_UV, ST_PRISM, ST_SPHL};
-  if (lane < WC_N) {
-    const unsigned long long v = lane == WC_RAYS ? traced : wc_lds[lane];
-    if (v) atomicAdd(S.stats + st_of[lane], v);
-  }
-}
-
-// dt_rays_occluded: the light loop's shadow test (cpp:806-852) with sray = dir: the gather along dir from
-// start + 1e-3 dir, intersectShadow along sn = normalized(dir) from start + 1e-3 sn up to t_max = |dir|, on
-// every gathered shape but the lane's skip_shape. Tree walks only: the shadow grid's lists are per light
-// and culled by the render's origin box. The walks skip one wave-uniform shape (the light's own, in the
-// trace kernel), so the lanes of a wave are served in groups of equal skip_shape, one walk per group:
-// one walk for a wave whose rays skip the same shape (or none), as many as it holds distinct values
-// otherwise.
-extern "C" __global__ void __launch_bounds__(64)
-dt_rayq_occl_kernel(const DLaunch* __restrict__ Lp, int64_t n, const double* __restrict__ start,
-                    const double* __restrict__ dir, const int32_t* __restrict__ skip_shape,
-                    uint8_t* __restrict__ occluded)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  Counters cnt;
-  cnt.wc = wc_lds;
-  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
-  unsigned long long traced = 0;   // wave-uniform
-  for (int64_t base = (int64_t)blockIdx.x * DT_WAVE; base < n; base += (int64_t)gridDim.x * DT_WAVE) {
-    const int64_t i = base + lane;
-    const bool in = i < n;
-    V3 org, sray;
-    const bool act = rayq_load(start, dir, i, in, org, sray);
-    const int skip = (act && skip_shape) ? skip_shape[i] : -1;
-    const float t_max = (float)norm(sray);
-    const V3 sn = act ? normalized(sray) : v3(1, 0, 0);
-    const V3 bstart = add(org, mul(1e-3, sray)), sstart = add(org, mul(1e-3, sn));
-    bool occl = false;
-    unsigned long long todo = __ballot(act);
-    traced += (unsigned long long)__popcll(todo);
-    while (todo) {
-      const int k0 = __builtin_amdgcn_readlane(skip, (int)__builtin_ctzll(todo));
-      const bool mine = inv(todo) && skip == k0;
-      todo &= ~__ballot(mine);
-      const Walk w = make_walk(P, mine, sray, bstart, 0.0f);
-      const bool o = w.inf_wave ? occluded_walk<1>(S, P, w, mine, bstart, sn, sstart, t_max, k0, 0.0f, cnt)
-                                : occluded_walk<0>(S, P, w, mine, bstart, sn, sstart, t_max, k0, 0.0f, cnt);
-      occl = occl || (mine && o);
-    }
-    if (in) occluded[i] = occl ? 1 : 0;
-  }
-  if (lane == 0 && traced) atomicAdd(S.stats + ST_SHADOW, traced);
-}
-
-extern "C" hipError_t dt_launch_rayq(const void* dev_launch, int64_t n, const double* start, const double* dir,
-                                     int32_t* shape, float* t, double* point, double* normal, double* albedo, int grid,
-                                     hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_rayq_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n, start, dir, shape, t,
-                     point, normal, albedo);
-  return hipGetLastError();
-}
-extern "C" hipError_t dt_launch_rayq_occl(const void* dev_launch, int64_t n, const double* start, const double* dir,
-                                          const int32_t* skip_shape, uint8_t* occluded, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_rayq_occl_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n, start, dir,
-                     skip_shape, occluded);
-  return hipGetLastError();
-}
-extern "C" const void* dt_rayq_kernel_ptr(void) { return (const void*)dt_rayq_kernel; }
-extern "C" const void* dt_rayq_occl_kernel_ptr(void) { return (const void*)dt_rayq_occl_kernel; }
-#elif DT_TRANSMIT
-// dt_rays_transmittance: dt_rayq_occl_kernel's rays, groups of equal skip_shape and walks (make_walk, the
-// inf_wave split), with transmit_walk in the place of occluded_walk: per ray -1 when a counting shape that is
-// not glass blocks it, else the number of counting glass shapes, and the k smallest of their indices from a
-// list of K >= k register slots per lane (K: 0, 1, 2, 4 or 8; the host launches the smallest that holds k). A
-// lane belongs to one group, so its count and list are written by one walk only. Every element of every
-// wanted plane is written: a void ray writes 0 and -1s, a blocked ray -1 and -1s. No workgroup waits on
-// another.
-template <int K>
-__global__ void __launch_bounds__(64)
-dt_rayq_transmit_kernel(const DLaunch* __restrict__ Lp, int64_t n, const double* __restrict__ start,
-                        const double* __restrict__ dir, const int32_t* __restrict__ skip_shape, int k,
-                        int32_t* __restrict__ panes_out, int32_t* __restrict__ pane_shape)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  unsigned long long traced = 0;   // wave-uniform
-  for (int64_t base = (int64_t)blockIdx.x * DT_WAVE; base < n; base += (int64_t)gridDim.x * DT_WAVE) {
-    const int64_t i = base + lane;
-    const bool in = i < n;
-    V3 org, sray;
-    const bool act = rayq_load(start, dir, i, in, org, sray);
-    const int skip = (act && skip_shape) ? skip_shape[i] : -1;
-    const float t_max = (float)norm(sray);
-    const V3 sn = act ? normalized(sray) : v3(1, 0, 0);
-    const V3 bstart = add(org, mul(1e-3, sray)), sstart = add(org, mul(1e-3, sn));
-    bool blocked = false;
-    int panes = 0;
-    PaneList<K> L;
-    panelist_clear(L);
-    unsigned long long todo = __ballot(act);
-    traced += (unsigned long long)__popcll(todo);
-    while (todo) {
-      const int k0 = __builtin_amdgcn_readlane(skip, (int)__builtin_ctzll(todo));
-      const bool mine = inv(todo) && skip == k0;
-      todo &= ~__ballot(mine);
-      const Walk w = make_walk(P, mine, sray, bstart, 0.0f);
-      const bool b = w.inf_wave ? transmit_walk<1>(S, P, w, mine, bstart, sn, sstart, t_max, k0, panes, L)
-                                : transmit_walk<0>(S, P, w, mine, bstart, sn, sstart, t_max, k0, panes, L);
-      blocked = blocked || (mine && b);
-    }
-    if (in && panes_out) panes_out[i] = blocked ? -1 : panes;
-    if constexpr (K > 0) {
-      if (pane_shape) {
-        for (int j = 0; j < k; ++j) {   // through slot 0: the runtime trip count indexes nothing
-          const int sj = panelist_pop(L);
-          if (in) pane_shape[(int64_t)k * i + j] = (!blocked && sj != 0x7fffffff) ? sj : -1;
-        }
-      }
-    }
-  }
-  if (lane == 0 && traced) atomicAdd(S.stats + ST_SHADOW, traced);
-}
-
-// the list capacity a launch with k takes: the smallest of 0, 1, 2, 4, 8 that holds it
-static int rayq_transmit_capacity(int k) { return k <= 0 ? 0 : k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
-
-extern "C" hipError_t dt_launch_rayq_transmit(const void* dev_launch, int64_t n, const double* start, const double* dir,
-                                              const int32_t* skip_shape, int k, int32_t* panes, int32_t* pane_shape,
-                                              int grid, hipStream_t stream)
-{
-#define DT_TRANSMIT_LAUNCH(K)                                                                                       \
-  hipLaunchKernelGGL(dt_rayq_transmit_kernel<K>, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n,    \
-                     start, dir, skip_shape, k, panes, pane_shape)
-  switch (rayq_transmit_capacity(pane_shape ? k : 0)) {
-    case 0: DT_TRANSMIT_LAUNCH(0); break;
-    case 1: DT_TRANSMIT_LAUNCH(1); break;
-    case 2: DT_TRANSMIT_LAUNCH(2); break;
-    case 4: DT_TRANSMIT_LAUNCH(4); break;
-    default: DT_TRANSMIT_LAUNCH(8); break;
-  }
-#undef DT_TRANSMIT_LAUNCH
-  return hipGetLastError();
-}
-extern "C" const void* dt_rayq_transmit_kernel_ptr(int k)
-{
-  switch (rayq_transmit_capacity(k)) {
-    case 0: return (const void*)dt_rayq_transmit_kernel<0>;
-    case 1: return (const void*)dt_rayq_transmit_kernel<1>;
-    case 2: return (const void*)dt_rayq_transmit_kernel<2>;
-    case 4: return (const void*)dt_rayq_transmit_kernel<4>;
-    default: return (const void*)dt_rayq_transmit_kernel<8>;
-  }
-}
-#elif DT_RAYPATH
-// dt_trace_rays_path: dt_features_path_kernel's chain per caller-supplied ray (include/dt.h): segment 0 is the
-// caller's ray as dt_rayq_kernel loads it, every segment goes without a primary list (pblock -1) with the lanes
-// still travelling as the mask, and the bounce loop is wave-uniform and capped by max_bounces: lanes whose path
-// has ended wait for the others. A lane's path ends as DT_PATH_VOID until a traced segment says otherwise: a
-// bounce leaves it so, and the void-ray test before the next segment decides.
-// What a lane would have to carry to the end of the loop goes straight to memory instead: a segment's shape and
-// point, the last ray and the terminal hit's point, normal and colour are stored where they are known (each lane
-// its own row, vector stores), and the entries nobody wrote are filled after the loop. Only the ray, the length
-// so far and three integers live across a walk.
-extern "C" __global__ void __launch_bounds__(64)
-dt_rayq_path_kernel(const DLaunch* __restrict__ Lp, int64_t n, const double* __restrict__ start,
-                    const double* __restrict__ dir, int max_bounces, const dt_ray_paths O)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  Counters cnt;
-  cnt.wc = wc_lds;
-  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
-  const int per = max_bounces + 1;   // per-segment entries of a ray
-  unsigned long long traced = 0;     // wave-uniform: the segments traced
-  for (int64_t base = (int64_t)blockIdx.x * DT_WAVE; base < n; base += (int64_t)gridDim.x * DT_WAVE) {
-    const int64_t i = base + lane;
-    const bool in = i < n;
-    V3 org, ray;
-    bool live = rayq_load(start, dir, i, in, org, ray);   // the path is still travelling
-    int end = DT_PATH_VOID, segs = 0, end_shape = -1;
-    double len = 0;   // the path's length so far
-    for (int k = 0; k <= max_bounces && __ballot(live); ++k) {
-      if (k > 0) {
-        // a void ray is not traced: its path stays DT_PATH_VOID
-        live = live && isfinite(org.x) && isfinite(org.y) && isfinite(org.z) && isfinite(ray.x) &&
-               isfinite(ray.y) && isfinite(ray.z) && (ray.x != 0 || ray.y != 0 || ray.z != 0);
-        if (!live) { org = v3(0, 0, 0); ray = v3(0, 0, 0); }
-      }
-      const unsigned long long am = __ballot(live);
-      if (!am) break;
-      traced += (unsigned long long)__popcll(am);
-      HitRec h;
-      h.t_min = FLT_MAX; h.shape = -1; h.ccol = -1; h.inside = 0;
-      const bool any = closest_hit(S, P, live, ray, org, 0.0f, h, cnt, /*pblock*/ -1);
-      const bool hit = any && live && h.shape >= 0;
-      if (live) {
-        const int64_t e = (int64_t)per * i + k;
-        segs = k + 1;
-        if (!hit) end = DT_PATH_MISS;
-        if (O.last_start) { O.last_start[3 * i] = org.x; O.last_start[3 * i + 1] = org.y; O.last_start[3 * i + 2] = org.z; }
-        if (O.last_dir) { O.last_dir[3 * i] = ray.x; O.last_dir[3 * i + 1] = ray.y; O.last_dir[3 * i + 2] = ray.z; }
-        if (O.seg_shape) O.seg_shape[e] = hit ? h.shape : -1;
-        if (O.seg_point && !hit) { O.seg_point[3 * e] = 0; O.seg_point[3 * e + 1] = 0; O.seg_point[3 * e + 2] = 0; }
-      }
-      int goes_on = 0;   // the lane's path goes on with another segment (a miss ends it)
-      if (hit) {
-        const int sid = h.shape;
-        const DShapeHdr hd = S.hdr[sid];
-        GP g = cas(S.geom) + hd.off;
-        const DMat& M = S.mat[sid];
-        const V3 p = add(org, mul(h.t_min, ray));
-        len = len + (double)h.t_min * norm(ray);
-        if (O.seg_point) {
-          const int64_t e = (int64_t)per * i + k;
-          O.seg_point[3 * e] = p.x; O.seg_point[3 * e + 1] = p.y; O.seg_point[3 * e + 2] = p.z;
-        }
-        V3 nk = v3(0, 0, 0);
-        int go = DT_GUIDE_STOP;
-        V3 ndir = v3(0, 0, 0), nstart = v3(0, 0, 0);
-        if (k < max_bounces || O.normal) {
-          nk = shape_norm(hd.type, hd.flags, g, p, 0.0f, cnt.wc + WC_PRISM, h.ccol);
-          const V3 in_dir = normalized(ray);
-          if (dot(mul(1e4, in_dir), nk) >= 0) nk = mul(-1, nk);   // fixNorm
-          if (k < max_bounces) {
-            bool refl_err = false;
-            go = guide_bounce(P.reflect, P.nogloss, P.refr_air, P.refr_glass, M.material, M.flags, h.inside, in_dir, nk,
-                              p, ndir, nstart, refl_err);
-            if (refl_err) atomicAdd(cnt.wc + WC_REFL, 1u);
-          }
-        }
-        const bool goes = go != DT_GUIDE_STOP;
-        goes_on = goes ? 1 : 0;
-        if (goes) {
-          ray = ndir;
-          org = nstart;
-          end = DT_PATH_VOID;   // until the next segment is traced
-        }
-        if (!goes) {
-          end = k < max_bounces ? DT_PATH_SURFACE : DT_PATH_CUT;
-          end_shape = sid;
-          if (O.point) { O.point[3 * i] = p.x; O.point[3 * i + 1] = p.y; O.point[3 * i + 2] = p.z; }
-          if (O.normal) { O.normal[3 * i] = nk.x; O.normal[3 * i + 1] = nk.y; O.normal[3 * i + 2] = nk.z; }
-          if (O.albedo) {
-            V3 col = hit_color(g, M, h.ccol);
-            if (M.flags & DT_F_TEXTURE) {
-              double tu = 0, tv = 0;
-              const int uvt = shape_uv(hd.type, hd.flags, g, p, 0.0f, tu, tv);
-              if (uvt == 2) {
-                col = v3a(M.bordercolor);
-              } else if (uvt == 1 && M.tex >= 0) {
-                col = texel_color(S, M, tu, tv);
-                atomicAdd(cnt.wc + WC_TEX, 1u);
-              }
-              if (uvt != 0 && (tu < 0 || tv < 0 || tu > 1 || tv > 1)) atomicAdd(cnt.wc + WC_UV, 1u);
-            }
-            O.albedo[3 * i] = col.x; O.albedo[3 * i + 1] = col.y; O.albedo[3 * i + 2] = col.z;
-          }
-        }
-      }
-      // `live` must leave the hit's code as a per-lane VGPR value, not as a lane mask. The lanes that end run a
-      // divergent region that holds the wave-uniform branch `if (O.albedo)`. With `live` assigned inside the
-      // hit's code (in either arm, or before both), the mask of the lanes that go on reaches the join after that
-      // branch on two edges: as ~(ending lanes) on the edge that skips the colour code, and as the constant 0 on
-      // the edge through it (gfx950 ISA of this build: `s_xor_b64 m, exec, -1` before the branch, `s_mov_b64 m, 0`
-      // after the colour code, `s_and_b64 live, m, exec` at the join). So with albedo wanted, one ending lane
-      // stopped the whole wave after that segment. Supposed cause, not proven: the Makefile's
-      // -structurizecfg-skip-uniform-regions leaves that uniform branch unstructurized inside a divergent region.
-      // dt_features_path_kernel has no uniform branch there. The empty asm keeps the value opaque, so the mask is
-      // formed from the VGPR here, after the region. tests/test_gpu_raypath.py case 2 (K >= 1, albedo wanted,
-      // paths of mixed lengths in one wave) fails without it.
-      asm volatile("" : "+v"(goes_on));
-      live = goes_on != 0;
-    }
-    if (in) {
-      if (O.end) O.end[i] = end;
-      if (O.segments) O.segments[i] = segs;
-      if (O.shape) O.shape[i] = end_shape;
-      if (O.length) O.length[i] = len;
-      if (end_shape < 0) {   // no terminal hit
-        if (O.point) { O.point[3 * i] = 0; O.point[3 * i + 1] = 0; O.point[3 * i + 2] = 0; }
-        if (O.normal) { O.normal[3 * i] = 0; O.normal[3 * i + 1] = 0; O.normal[3 * i + 2] = 0; }
-        if (O.albedo) { O.albedo[3 * i] = 0; O.albedo[3 * i + 1] = 0; O.albedo[3 * i + 2] = 0; }
-      }
-      if (segs == 0) {
-        if (O.last_start) { O.last_start[3 * i] = 0; O.last_start[3 * i + 1] = 0; O.last_start[3 * i + 2] = 0; }
-        if (O.last_dir) { O.last_dir[3 * i] = 0; O.last_dir[3 * i + 1] = 0; O.last_dir[3 * i + 2] = 0; }
-      }
-      for (int k = segs; k < per; ++k) {   // the segments never traced
-        const int64_t e = (int64_t)per * i + k;
-        if (O.seg_shape) O.seg_shape[e] = -1;
-        if (O.seg_point) { O.seg_point[3 * e] = 0; O.seg_point[3 * e + 1] = 0; O.seg_point[3 * e + 2] = 0; }
-      }
-    }
-  }
-  __syncthreads();
-  const int st_of[WC_N] = {ST_RAYS, ST_SHADOW, ST_TEX, ST_STACK, ST_REFL, ST_GLOSSY, ST_UV, ST_PRISM, ST_SPHL};
-  if (lane < WC_N) {
-    const unsigned long long v = lane == WC_RAYS ? traced : wc_lds[lane];
-    if (v) atomicAdd(S.stats + st_of[lane], v);
-  }
-}
-
-extern "C" hipError_t dt_launch_rayq_path(const void* dev_launch, int64_t n, const double* start, const double* dir,
-                                          int max_bounces, const struct dt_ray_paths* planes, int grid,
-                                          hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_rayq_path_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n, start, dir,
-                     max_bounces, *planes);
-  return hipGetLastError();
-}
-extern "C" const void* dt_rayq_path_kernel_ptr(void) { return (const void*)dt_rayq_path_kernel; }
-#else   // DT_MHIT
-// dt_trace_rays_multi: per ray the k nearest of the shapes dt_trace_rays gathers, each tested on its own
-// (multi_hit_walk: the fast tree for finite waves, the reference tree for a wave with an axis-parallel ray),
-// in a list of K >= k register slots per lane (K: 1, 2, 4 or 8; the host launches the smallest that holds k),
-// of which the first k are written. Then per rank j < k, at wave-uniform control flow, what dt_rayq_kernel
-// computes for its one hit, for the lanes with j < count; the other lanes write -1, FLT_MAX and zeros, so
-// every element of every wanted plane is written. The walk carries no checker colour per slot (8 more live
-// registers at K = 8): where albedo is wanted, a recorded checkerboard is tested once more (t reset) for
-// its square.
-template <int K>
-__global__ void __launch_bounds__(64)
-dt_rayq_multi_kernel(const DLaunch* __restrict__ Lp, int64_t n, const double* __restrict__ start,
-                     const double* __restrict__ dir, int k, int32_t* __restrict__ count_out,
-                     int32_t* __restrict__ shape_out, float* __restrict__ t_out, double* __restrict__ point,
-                     double* __restrict__ normal, double* __restrict__ albedo)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  unsigned int* const wc = wc_lds;
-  unsigned long long traced = 0;   // wave-uniform
-  for (int64_t base = (int64_t)blockIdx.x * DT_WAVE; base < n; base += (int64_t)gridDim.x * DT_WAVE) {
-    const int64_t i = base + lane;
-    const bool in = i < n;
-    V3 org, ray;
-    const bool act = rayq_load(start, dir, i, in, org, ray);
-    const unsigned long long am = __ballot(act);
-    traced += (unsigned long long)__popcll(am);
-    HitList<K> L;
-    hitlist_clear(L);
-    if (am) {
-      const Walk w = make_walk(P, act, ray, org, 0.0f);
-      if (w.inf_wave) multi_hit_walk<1>(S, P, w, act, ray, org, L);
-      else multi_hit_walk<0>(S, P, w, act, ray, org, L);
-    }
-    if (in && count_out) {
-      int c = 0;
-#pragma unroll
-      for (int j = 0; j < K; ++j) c += L.t[j] < FLT_MAX ? 1 : 0;
-      count_out[i] = c < k ? c : k;
-    }
-    for (int j = 0; j < k; ++j) {
-      float tj;
-      int sj;
-      hitlist_pop(L, tj, sj);
-      const bool hit = act && tj < FLT_MAX;   // j < count
-      V3 p = v3(0, 0, 0), nrm = v3(0, 0, 0), col = v3(0, 0, 0);
-      if (hit && (point || normal || albedo)) {
-        const DShapeHdr hd = S.hdr[sj];
-        GP g = cas(S.geom) + hd.off;
-        const DMat& M = S.mat[sj];
-        p = add(org, mul(tj, ray));
-        int ccol = -1;
-        if (albedo && (hd.type == DT_SHAPE_CHECKERBOARD || hd.type == DT_SHAPE_CHECKERBOARD_HOLE)) {
-          float t2 = FLT_MAX;
-          int ins = 0, edge = 0;
-          shape_hit(S, sj, hd.type, hd.flags, g, ray, org, 0.0f, t2, ins, ccol, edge);
-        }
-        if (normal) {
-          nrm = shape_norm(hd.type, hd.flags, g, p, 0.0f, wc + WC_PRISM, ccol);
-          const V3 in_dir = normalized(ray);
-          if (dot(mul(1e4, in_dir), nrm) >= 0) nrm = mul(-1, nrm);   // fixNorm
-        }
-        if (albedo) {
-          col = hit_color(g, M, ccol);
-          if (M.flags & DT_F_TEXTURE) {
-            double tu = 0, tv = 0;
-            const int uvt = shape_uv(hd.type, hd.flags, g, p, 0.0f, tu, tv);
-            if (uvt == 2) {
-              col = v3a(M.bordercolor);
-            } else if (uvt == 1 && M.tex >= 0) {
-              col = texel_color(S, M, tu, tv);
-              atomicAdd(wc + WC_TEX, 1u);
-            }
-            if (uvt != 0 && (tu < 0 || tv < 0 || tu > 1 || tv > 1)) atomicAdd(wc + WC_UV, 1u);
-          }
-        }
-      }
-      if (in) {
-        const int64_t e = (int64_t)k * i + j;
-        if (shape_out) shape_out[e] = hit ? sj : -1;
-        if (t_out) t_out[e] = hit ? tj : FLT_MAX;
-        if (point) { point[3 * e] = p.x; point[3 * e + 1] = p.y; point[3 * e + 2] = p.z; }
-        if (normal) { normal[3 * e] = nrm.x; normal[3 * e + 1] = nrm.y; normal[3 * e + 2] = nrm.z; }
-        if (albedo) { albedo[3 * e] = col.x; albedo[3 * e + 1] = col.y; albedo[3 * e + 2] = col.z; }
-      }
-    }
-  }
-  __syncthreads();
-  const int st_of[WC_N] = {ST_RAYS, ST_SHADOW, ST_TEX, ST_STACK, ST_REFL, ST_GLOSSY, ST_UV, ST_PRISM, ST_SPHL};
-  if (lane < WC_N) {
-    const unsigned long long v = lane == WC_RAYS ? traced : wc_lds[lane];
-    if (v) atomicAdd(S.stats + st_of[lane], v);
-  }
-}
-
-// the list capacity a launch with k takes: the smallest of 1, 2, 4, 8 that holds it
-static int rayq_multi_capacity(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
-
-extern "C" hipError_t dt_launch_rayq_multi(const void* dev_launch, int64_t n, const double* start, const double* dir,
-                                           int k, int32_t* count, int32_t* shape, float* t, double* point,
-                                           double* normal, double* albedo, int grid, hipStream_t stream)
-{
-#define DT_MHIT_LAUNCH(K)                                                                                            \
-  hipLaunchKernelGGL(dt_rayq_multi_kernel<K>, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n, start, \
-                     dir, k, count, shape, t, point, normal, albedo)
-  switch (rayq_multi_capacity(k)) {
-    case 1: DT_MHIT_LAUNCH(1); break;
-    case 2: DT_MHIT_LAUNCH(2); break;
-    case 4: DT_MHIT_LAUNCH(4); break;
-    default: DT_MHIT_LAUNCH(8); break;
-  }
-#undef DT_MHIT_LAUNCH
-  return hipGetLastError();
-}
-extern "C" const void* dt_rayq_multi_kernel_ptr(int k)
-{
-  switch (rayq_multi_capacity(k)) {
-    case 1: return (const void*)dt_rayq_multi_kernel<1>;
-    case 2: return (const void*)dt_rayq_multi_kernel<2>;
-    case 4: return (const void*)dt_rayq_multi_kernel<4>;
-    default: return (const void*)dt_rayq_multi_kernel<8>;
-  }
-}
-#endif
-#elif DT_OCCL
-// Occlusion feature buffers (include/dt.h dt_render_occlusion; no reference counterpart): for the samples
-// 0 .. n_samples-1 of every owned pixel the render's own primary ray to its closest hit, as
-// dt_features_kernel takes it (items and lanes, camera_ray, closest_hit at shift 0, the primary-list block
-// rule, shape_norm + fixNorm), and from every hit ao_rays ambient-occlusion probes and one probe per listed
-// light, generated in registers (dt_occl.h: one definition for this kernel and the host exports) and
-// answered as dt_rayq_occl_kernel answers a ray: make_walk + occluded_walk<0/1> over the lanes that hit,
-// pblock -1, tree walks only. The probe index k is wave-uniform (k < ao_rays: AO probe k; else light slot
-// k - ao_rays, whose skip shape is the light's own, one value for the wave), so a probe is one walk and the
-// AO loop and the light loop share one call site of the walk code.
-// The lanes of a chunk are the samples of one pixel (spp >= 64) or of P.ppw pixels (spp < 64): their
-// probes start next to each other. Counting is by ballot: lane jj < P.ppw owns pixel jj of the wave and
-// adds the popcount of its segment's unoccluded lanes to its own LDS entry (integers: no summation order);
-// a void probe is not traced and counts as unoccluded. One wave owns all chunks of a pixel, so the
-// counts carry over in LDS from chunk to chunk; the owning lane stores the planes after the last chunk.
-extern "C" __global__ void __launch_bounds__(64)
-dt_occlusion_kernel(const DLaunch* __restrict__ Lp, int n_samples, int ao_rays, float ao_radius, int n_lights,
-                    const dtd::OcclLight* __restrict__ lights, float* __restrict__ ao_out, float* __restrict__ light_out)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  __shared__ unsigned int occ[DT_OCCL_MAX_LIGHTS + 1][DT_WAVE];   // row 0: AO, row 1 + j: light slot j
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  Counters cnt;
-  cnt.wc = wc_lds;
-  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
-  Ctx c;
-  c.S = &S;
-  c.P = &P;
-  c.rng.k0 = P.seed;
-  c.rng.k1 = (uint32_t)P.frame;
-  const bool lists = P.pl_block > 0 && P.n_fnodes > 0 && (P.ftree_mode & 1);
-  const int group = P.ppw;
-  const int per = P.spp < DT_WAVE ? P.spp : DT_WAVE;
-  const int j = lane / per, sl = lane - j * per;
-  // the lanes of the pixel this lane owns (lane < group only)
-  const unsigned long long segmask =
-      per < DT_WAVE ? (lane < group ? ((1ull << per) - 1ull) << (lane * per) : 0ull) : ~0ull;
-  const int chunks = (n_samples + DT_WAVE - 1) / DT_WAVE;
-  const int n_probes = ao_rays + n_lights;
-  unsigned long long traced = 0;   // wave-uniform
-  for (int64_t item = blockIdx.x; item < P.n_items; item += gridDim.x) {
-    if (lane < group)
-      for (int r = 0; r <= DT_OCCL_MAX_LIGHTS; ++r) occ[r][lane] = 0;
-    int px_x = 0, px_y = 0;
-    int64_t px_off = 0;
-    bool px_valid = false;
-    pixel_of(P, item * group + (j < group ? j : 0), px_x, px_y, px_off, px_valid);
-    px_valid = px_valid && j < group;
-    for (int chunk = 0; chunk < chunks; ++chunk) {
-      const int sample = chunk * DT_WAVE + sl;
-      const bool valid = px_valid && sample < n_samples;
-      c.rng.pixel = (uint32_t)(px_y * P.xRes + px_x);
-      c.rng.sample = (uint32_t)sample;
-      V3 eye_sample = v3a(P.eye), ray0 = v3(0, 0, 0);
-      if (valid) camera_ray(c, P, px_x, px_y, eye_sample, ray0);
-      const unsigned long long vm = __ballot(valid);
-      bool hit = false;
-      HitRec h;
-      h.t_min = FLT_MAX; h.shape = -1; h.ccol = -1;
-      if (vm) {
-        int pblock = -1;
-        if (lists) {   // the block of the wave's valid pixels, when they share one
-          const int blk = (px_y / P.pl_block) * P.pl_nbx + px_x / P.pl_block;
-          const int b0 = __shfl(blk, (int)__builtin_ctzll(vm));
-          if (!__ballot(valid && blk != b0)) pblock = b0;
-        }
-        const bool any = closest_hit(S, P, valid, ray0, eye_sample, 0.0f, h, cnt, pblock);
-        hit = any && valid && h.shape >= 0;
-      }
-      V3 p = v3(0, 0, 0), nrm = v3(0, 0, 0);
-      if (hit) {
-        const int sid = h.shape;
-        const DShapeHdr hd = S.hdr[sid];
-        GP g = cas(S.geom) + hd.off;
-        p = add(eye_sample, mul(h.t_min, ray0));
-        nrm = shape_norm(hd.type, hd.flags, g, p, 0.0f, cnt.wc + WC_PRISM, h.ccol);
-        const V3 in = normalized(ray0);
-        if (dot(mul(1e4, in), nrm) >= 0) nrm = mul(-1, nrm);   // fixNorm
-      }
-      if (!__ballot(hit)) continue;   // wave-uniform: a chunk of misses adds nothing
-      for (int k = 0; k < n_probes; ++k) {
-        V3 sray = v3(0, 0, 0);
-        int skip = -1;
-        if (k < ao_rays) {
-          if (hit) sray = dtd::occl_ao_dir(P.seed, P.frame, c.rng.pixel, c.rng.sample, k, ao_radius, nrm);
-        } else {
-          const dtd::OcclLight L = lights[k - ao_rays];   // wave-uniform
-          skip = uni(L.shape_index);
-          if (hit) sray = dtd::occl_light_dir(P.seed, P.frame, c.rng.pixel, c.rng.sample, k - ao_rays, L, p);
-        }
-        // a void probe (dt_rays_occluded's rule) is an inactive lane, as in dt_rayq_occl_kernel
-        const bool act = hit && isfinite(sray.x) && isfinite(sray.y) && isfinite(sray.z) && isfinite(p.x) &&
-                         isfinite(p.y) && isfinite(p.z) && (sray.x != 0 || sray.y != 0 || sray.z != 0);
-        if (!act) sray = v3(0, 0, 0);
-        const V3 org = act ? p : v3(0, 0, 0);
-        const float t_max = (float)norm(sray);
-        const V3 sn = act ? normalized(sray) : v3(1, 0, 0);
-        const V3 bstart = add(org, mul(1e-3, sray)), sstart = add(org, mul(1e-3, sn));
-        const unsigned long long am = __ballot(act);
-        traced += (unsigned long long)__popcll(am);
-        bool occl = false;
-        if (am) {
-          const Walk w = make_walk(P, act, sray, bstart, 0.0f);
-          const bool o = w.inf_wave ? occluded_walk<1>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt)
-                                    : occluded_walk<0>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt);
-          occl = act && o;
-        }
-        const unsigned long long um = __ballot(hit && !occl);
-        const int row = k < ao_rays ? 0 : 1 + k - ao_rays;
-        if (lane < group) occ[row][lane] += (unsigned int)__popcll(um & segmask);
-      }
-    }
-    if (lane < group) {
-      int qx, qy;
-      int64_t qo;
-      bool qv;
-      pixel_of(P, item * group + lane, qx, qy, qo, qv);
-      if (qv) {
-        const int64_t q = P.layout == DT_OUT_SLAB ? qo / 3 : (int64_t)(P.yRes - 1 - qy) * P.xRes + qx;
-        const double n = (double)n_samples;
-        if (ao_out) ao_out[q] = (float)((double)occ[0][lane] / (n * (double)ao_rays));
-        if (light_out)
-          for (int l = 0; l < n_lights; ++l) light_out[(int64_t)n_lights * q + l] = (float)((double)occ[1 + l][lane] / n);
-      }
-    }
-  }
-  __syncthreads();
-  if (lane == 0) {
-    if (traced) atomicAdd(S.stats + ST_SHADOW, traced);
-    if (wc_lds[WC_PRISM]) atomicAdd(S.stats + ST_PRISM, (unsigned long long)wc_lds[WC_PRISM]);
-  }
-}
-extern "C" hipError_t dt_launch_occlusion(const void* dev_launch, int n_samples, int ao_rays, float ao_radius, int n_lights,
-                                          const void* lights, float* ao, float* light, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_occlusion_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n_samples, ao_rays,
-                     ao_radius, n_lights, (const dtd::OcclLight*)lights, ao, light);
-  return hipGetLastError();
-}
-extern "C" const void* dt_occlusion_kernel_ptr(void) { return (const void*)dt_occlusion_kernel; }
-#elif DT_POCCL || DT_POCCLG
-// Occlusion queries at surface points (include/dt.h dt_points_occlusion; no reference counterpart): the probes
-// of dt_occlusion_kernel from points and normals the caller hands over, 3 doubles each, in place of the
-// camera's first hits. One point per lane, 64 consecutive points per wave, grid-stride over the waves as
-// dt_rayq_occl_kernel; the lane's point is the RNG counter's pixel, its sample loop the counter's sample.
-// Probes are generated in registers (dt_occl.h, the one definition) and answered as dt_rayq_occl_kernel
-// answers a ray: make_walk + occluded_walk<0/1>, tree walks only, one call site.
-// The loops are wave-uniform: row 0 is the AO plane (probe t = sample * ao_rays + r), row 1 + j light slot j
-// (probe t = sample), whose skip shape is the light's own, one value for the wave: one walk per probe index,
-// never one per lane. A lane counts its own unoccluded probes in a register and stores one float per row
-// (integers: no summation order). A tail lane or a void point (a non-finite component) is an inactive lane
-// of every walk: it stays in the wave, is never probed, and a void point stores 0.
-//
-// DT_POCCLG: the same source as dt_points_occl_glass_kernel (include/dt.h dt_points_occlusion_glass), a build of
-// its own; the preprocessor leaves DT_POCCL's build the tokens it had. There a probe is answered by
-// transmit_walk<0/1, 0> (a count, no list): it is unoccluded iff it is not blocked and crosses at most
-// max_panes panes; beside its unoccluded probes a lane sums their panes (integers again), for the two optional
-// pane planes, and every store is guarded, as a row runs for either of its two planes.
-extern "C" __global__ void __launch_bounds__(64)
-#if DT_POCCLG
-dt_points_occl_glass_kernel(const DLaunch* __restrict__ Lp, uint32_t seed, int32_t frame, int64_t n,
-                            const double* __restrict__ point, const double* __restrict__ normal, int n_samples,
-                            int ao_rays, float ao_radius, int n_lights, const dtd::OcclLight* __restrict__ lights,
-                            int max_panes, float* __restrict__ ao_out, float* __restrict__ light_out,
-                            float* __restrict__ ao_panes_out, float* __restrict__ light_panes_out)
-#else
-dt_points_occl_kernel(const DLaunch* __restrict__ Lp, uint32_t seed, int32_t frame, int64_t n,
-                      const double* __restrict__ point, const double* __restrict__ normal, int n_samples, int ao_rays,
-                      float ao_radius, int n_lights, const dtd::OcclLight* __restrict__ lights,
-                      float* __restrict__ ao_out, float* __restrict__ light_out)
-#endif
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  Counters cnt;
-  cnt.wc = wc_lds;
-  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
-  unsigned long long traced = 0;   // wave-uniform
-  for (int64_t base = (int64_t)blockIdx.x * DT_WAVE; base < n; base += (int64_t)gridDim.x * DT_WAVE) {
-    const int64_t i = base + lane;
-    const bool in = i < n;
-    V3 p = v3(0, 0, 0), nrm = v3(0, 0, 0);
-    bool live = false;
-    if (in) {
-      const V3 pi = v3(point[3 * i], point[3 * i + 1], point[3 * i + 2]);
-      const V3 ni = v3(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]);
-      live = isfinite(pi.x) && isfinite(pi.y) && isfinite(pi.z) && isfinite(ni.x) && isfinite(ni.y) && isfinite(ni.z);
-      if (live) {
-        p = pi;
-        nrm = ni;
-      }
-    }
-    const uint32_t pixel = (uint32_t)i;
-    const bool any_live = __ballot(live) != 0;   // wave-uniform: a wave of void points runs no probe loop
-    for (int row = ao_rays > 0 ? 0 : 1; row <= n_lights; ++row) {
-      const int per = row == 0 ? ao_rays : 1;
-      const int n_probes = any_live ? n_samples * per : 0;
-      dtd::OcclLight L = {};
-      int skip = -1;
-      if (row > 0) {
-        L = lights[row - 1];   // wave-uniform
-        skip = uni(L.shape_index);
-      }
-      unsigned int V = 0;
-#if DT_POCCLG
-      unsigned int VP = 0;   // the panes of the unoccluded probes
-#endif
-      for (int t = 0; t < n_probes; ++t) {
-        const int sample = t / per, r = t - sample * per;
-        V3 sray = v3(0, 0, 0);
-        if (live) {
-          if (row == 0) sray = dtd::occl_ao_dir(seed, frame, pixel, (uint32_t)sample, r, ao_radius, nrm);
-          else sray = dtd::occl_light_dir(seed, frame, pixel, (uint32_t)sample, row - 1, L, p);
-        }
-        // a void probe (dt_rays_occluded's rule) is an inactive lane, as in dt_rayq_occl_kernel
-        const bool act = live && isfinite(sray.x) && isfinite(sray.y) && isfinite(sray.z) &&
-                         (sray.x != 0 || sray.y != 0 || sray.z != 0);
-        if (!act) sray = v3(0, 0, 0);
-        const V3 org = act ? p : v3(0, 0, 0);
-        const float t_max = (float)norm(sray);
-        const V3 sn = act ? normalized(sray) : v3(1, 0, 0);
-        const V3 bstart = add(org, mul(1e-3, sray)), sstart = add(org, mul(1e-3, sn));
-        const unsigned long long am = __ballot(act);
-        traced += (unsigned long long)__popcll(am);
-        bool occl = false;
-#if DT_POCCLG
-        int panes = 0;
-        if (am) {
-          const Walk w = make_walk(P, act, sray, bstart, 0.0f);
-          PaneList<0> none;
-          const bool b = w.inf_wave ? transmit_walk<1>(S, P, w, act, bstart, sn, sstart, t_max, skip, panes, none)
-                                    : transmit_walk<0>(S, P, w, act, bstart, sn, sstart, t_max, skip, panes, none);
-          occl = act && (b || panes > max_panes);
-        }
-        if (live && !occl) {
-          ++V;
-          VP += (unsigned int)panes;
-        }
-#else
-        if (am) {
-          const Walk w = make_walk(P, act, sray, bstart, 0.0f);
-          const bool o = w.inf_wave ? occluded_walk<1>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt)
-                                    : occluded_walk<0>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt);
-          occl = act && o;
-        }
-        if (live && !occl) ++V;
-#endif
-      }
-#if DT_POCCLG
-      if (in) {
-        const double den = row == 0 ? (double)n_samples * (double)ao_rays : (double)n_samples;
-        float* const vis = row == 0 ? ao_out : light_out;
-        float* const pan = row == 0 ? ao_panes_out : light_panes_out;
-        const int64_t e = row == 0 ? i : (int64_t)n_lights * i + (row - 1);
-        if (vis) vis[e] = live ? (float)((double)V / den) : 0.0f;
-        if (pan) pan[e] = live ? (float)((double)VP / den) : 0.0f;
-      }
-#else
-      if (in) {
-        if (row == 0) ao_out[i] = live ? (float)((double)V / ((double)n_samples * (double)ao_rays)) : 0.0f;
-        else light_out[(int64_t)n_lights * i + (row - 1)] = live ? (float)((double)V / (double)n_samples) : 0.0f;
-      }
-#endif
-    }
-  }
-  if (lane == 0 && traced) atomicAdd(S.stats + ST_SHADOW, traced);
-}
-#if DT_POCCLG
-extern "C" hipError_t dt_launch_points_occl_glass(const void* dev_launch, uint32_t seed, int32_t frame, int64_t n,
-                                                  const double* point, const double* normal, int n_samples,
-                                                  int ao_rays, float ao_radius, int n_lights, const void* lights,
-                                                  int max_panes, float* ao, float* light, float* ao_panes,
-                                                  float* light_panes, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_points_occl_glass_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, seed,
-                     frame, n, point, normal, n_samples, ao_rays, ao_radius, n_lights, (const dtd::OcclLight*)lights,
-                     max_panes, ao, light, ao_panes, light_panes);
-  return hipGetLastError();
-}
-extern "C" const void* dt_points_occl_glass_kernel_ptr(void) { return (const void*)dt_points_occl_glass_kernel; }
-#else
-extern "C" hipError_t dt_launch_points_occl(const void* dev_launch, uint32_t seed, int32_t frame, int64_t n,
-                                            const double* point, const double* normal, int n_samples, int ao_rays,
-                                            float ao_radius, int n_lights, const void* lights, float* ao, float* light,
-                                            int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_points_occl_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, seed, frame, n,
-                     point, normal, n_samples, ao_rays, ao_radius, n_lights, (const dtd::OcclLight*)lights, ao, light);
-  return hipGetLastError();
-}
-extern "C" const void* dt_points_occl_kernel_ptr(void) { return (const void*)dt_points_occl_kernel; }
-#endif
-#elif DT_PIRR
-// Irradiance queries at surface points (include/dt.h dt_points_irradiance; no reference counterpart):
-// dt_points_occl_kernel's points, lanes and light probes, each unoccluded probe weighted by the cosine at the
-// point (dt_irr.h irr_cosine) and the means combined with the lights' colours, which travel in the launch's
-// light records (dt_irr.h IrrLight); then one diffuse gather bounce. Every loop is wave-uniform:
-//   the direct rows: per light slot j and sample s one probe (dt_occl.h occl_light_dir, unchanged), answered by
-//     make_walk + occluded_walk<0/1> as dt_rayq_occl_kernel answers a ray, the slot's skip shape for the wave;
-//   the gather: per (s, r) one closest-hit walk for the wave's gather probes (dt_irr.h irr_gather_ray) with
-//     the attributes as dt_rayq_kernel computes them (point, shape_norm + fixNorm, hit_color / texel), and from
-//     the lanes' own hits one occluded_walk per light slot (irr_light_dir under OCCL_P_GLIGHT).
-// A tail lane, a void point, a void probe, a lane that missed or hit an emitter is an inactive lane of the
-// walks it has no part in and stays in the wave. A lane keeps its sums in registers (f64, in the header's
-// order) and stores each plane entry once, every store guarded by the plane's pointer; rows and loops whose
-// planes are all NULL run no walk: the direct rows for direct or direct_rgb, the gather for indirect_rgb or
-// sky, its light loop and attributes for indirect_rgb.
-extern "C" __global__ void __launch_bounds__(64)
-dt_points_irr_kernel(const DLaunch* __restrict__ Lp, uint32_t seed, int32_t frame, int64_t n,
-                     const double* __restrict__ point, const double* __restrict__ normal, int n_samples, int n_lights,
-                     const dtd::IrrLight* __restrict__ lights, int gather_rays, float* __restrict__ direct_out,
-                     float* __restrict__ direct_rgb_out, float* __restrict__ indirect_rgb_out,
-                     float* __restrict__ sky_out)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  Counters cnt;
-  cnt.wc = wc_lds;
-  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
-  const int direct_rows = (direct_out || direct_rgb_out) ? n_lights : 0;
-  const int gathers = (indirect_rgb_out || sky_out) ? gather_rays : 0;
-  const int gather_lights = indirect_rgb_out ? n_lights : 0;
-  unsigned long long shadowed = 0, gathered = 0;   // wave-uniform: the non-void shadow and gather probes
-  for (int64_t base = (int64_t)blockIdx.x * DT_WAVE; base < n; base += (int64_t)gridDim.x * DT_WAVE) {
-    const int64_t i = base + lane;
-    const bool in = i < n;
-    V3 p = v3(0, 0, 0), nrm = v3(0, 0, 0);
-    bool live = false;
-    if (in) {
-      const V3 pi = v3(point[3 * i], point[3 * i + 1], point[3 * i + 2]);
-      const V3 ni = v3(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]);
-      live = isfinite(pi.x) && isfinite(pi.y) && isfinite(pi.z) && isfinite(ni.x) && isfinite(ni.y) && isfinite(ni.z);
-      if (live) {
-        p = pi;
-        nrm = ni;
-      }
-    }
-    const uint32_t pixel = (uint32_t)i;
-    const bool any_live = __ballot(live) != 0;   // wave-uniform: a wave of void points runs no probe loop
-    const double den = (double)n_samples;
-    V3 D = v3(0, 0, 0);   // direct_rgb's sums over the slots
-    for (int j = 0; j < direct_rows; ++j) {
-      const dtd::IrrLight L = lights[j];   // wave-uniform
-      const int skip = uni(L.L.shape_index);
-      double C = 0.0;
-      for (int s = 0; any_live && s < n_samples; ++s) {
-        V3 sray = v3(0, 0, 0);
-        if (live) sray = dtd::occl_light_dir(seed, frame, pixel, (uint32_t)s, j, L.L, p);
-        // a void probe (dt_rays_occluded's rule) is an inactive lane, as in dt_rayq_occl_kernel
-        const bool act = live && !dtd::irr_void_dir(sray);
-        if (!act) sray = v3(0, 0, 0);
-        const V3 org = act ? p : v3(0, 0, 0);
-        const float t_max = (float)norm(sray);
-        const V3 sn = act ? normalized(sray) : v3(1, 0, 0);
-        const V3 bstart = add(org, mul(1e-3, sray)), sstart = add(org, mul(1e-3, sn));
-        const unsigned long long am = __ballot(act);
-        shadowed += (unsigned long long)__popcll(am);
-        bool occl = false;
-        if (am) {
-          const Walk w = make_walk(P, act, sray, bstart, 0.0f);
-          const bool o = w.inf_wave ? occluded_walk<1>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt)
-                                    : occluded_walk<0>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt);
-          occl = act && o;
-        }
-        C = C + (occl ? 0.0 : dtd::irr_cosine(nrm, sray));
-      }
-      const double mean = C / den;
-      if (in && direct_out) direct_out[(int64_t)n_lights * i + j] = live ? (float)mean : 0.0f;
-      D = add(D, mul(mean, v3a(L.color)));
-    }
-    if (in && direct_rgb_out) {
-      direct_rgb_out[3 * i] = live ? (float)D.x : 0.0f;
-      direct_rgb_out[3 * i + 1] = live ? (float)D.y : 0.0f;
-      direct_rgb_out[3 * i + 2] = live ? (float)D.z : 0.0f;
-    }
-    if (gathers <= 0) continue;   // wave-uniform
-    V3 G = v3(0, 0, 0);       // indirect_rgb's sums over (s, r)
-    unsigned int missed = 0;  // the gather probes that hit nothing
-    for (int t = 0; any_live && t < n_samples * gathers; ++t) {
-      const int s = t / gathers, r = t - s * gathers;
-      V3 gstart = v3(0, 0, 0), gdir = v3(0, 0, 0);
-      bool gl = false;
-      if (live) gl = dtd::irr_gather_ray(seed, frame, pixel, (uint32_t)s, r, p, nrm, gstart, gdir);
-      if (!gl) {
-        gstart = v3(0, 0, 0);
-        gdir = v3(0, 0, 0);
-      }
-      const unsigned long long gm = __ballot(gl);
-      gathered += (unsigned long long)__popcll(gm);
-      HitRec h;
-      h.t_min = FLT_MAX; h.shape = -1; h.ccol = -1;
-      bool hit = false;
-      if (gm) {
-        const bool any = closest_hit(S, P, gl, gdir, gstart, 0.0f, h, cnt, /*pblock*/ -1);
-        hit = any && gl && h.shape >= 0;
-      }
-      if (gl && !hit) ++missed;
-      if (!indirect_rgb_out || !__ballot(hit)) continue;   // wave-uniform
-      V3 q = v3(0, 0, 0), nq = v3(0, 0, 0), col = v3(0, 0, 0);
-      bool shade = false;   // a hit that is no emitter: it runs the light loop
-      if (hit) {
-        const int sid = h.shape;
-        const DShapeHdr hd = S.hdr[sid];
-        GP g = cas(S.geom) + hd.off;
-        const DMat& M = S.mat[sid];
-        q = add(gstart, mul(h.t_min, gdir));
-        col = hit_color(g, M, h.ccol);
-        if (M.flags & DT_F_TEXTURE) {
-          double tu = 0, tv = 0;
-          const int uvt = shape_uv(hd.type, hd.flags, g, q, 0.0f, tu, tv);
-          if (uvt == 2) col = v3a(M.bordercolor);
-          else if (uvt == 1 && M.tex >= 0) col = texel_color(S, M, tu, tv);
-        }
-        if (M.flags & DT_F_LIGHT) {
-          G = add(G, col);
-        } else {
-          shade = true;
-          nq = shape_norm(hd.type, hd.flags, g, q, 0.0f, cnt.wc + WC_PRISM, h.ccol);
-          const V3 in_dir = normalized(gdir);
-          if (dot(mul(1e4, in_dir), nq) >= 0) nq = mul(-1, nq);   // fixNorm
-        }
-      }
-      if (!__ballot(shade)) continue;   // wave-uniform
-      V3 E = v3(0, 0, 0);
-      for (int j = 0; j < gather_lights; ++j) {
-        const dtd::IrrLight L = lights[j];   // wave-uniform
-        const int skip = uni(L.L.shape_index);
-        V3 sray = v3(0, 0, 0);
-        if (shade)
-          sray = dtd::irr_light_dir(seed, frame, pixel, (uint32_t)s, dtd::OCCL_P_GLIGHT, r * DT_OCCL_MAX_LIGHTS + j, L.L, q);
-        const bool act = shade && !dtd::irr_void_dir(sray) && isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
-        if (!act) sray = v3(0, 0, 0);
-        const V3 org = act ? q : v3(0, 0, 0);
-        const float t_max = (float)norm(sray);
-        const V3 sn = act ? normalized(sray) : v3(1, 0, 0);
-        const V3 bstart = add(org, mul(1e-3, sray)), sstart = add(org, mul(1e-3, sn));
-        const unsigned long long am = __ballot(act);
-        shadowed += (unsigned long long)__popcll(am);
-        bool occl = false;
-        if (am) {
-          const Walk w = make_walk(P, act, sray, bstart, 0.0f);
-          const bool o = w.inf_wave ? occluded_walk<1>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt)
-                                    : occluded_walk<0>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt);
-          occl = act && o;
-        }
-        E = add(E, mul(occl ? 0.0 : dtd::irr_cosine(nq, sray), v3a(L.color)));
-      }
-      if (shade) G = add(G, cwise(col, E));
-    }
-    if (in) {
-      const double gden = den * (double)gather_rays;
-      if (indirect_rgb_out) {
-        indirect_rgb_out[3 * i] = live ? (float)(G.x / gden) : 0.0f;
-        indirect_rgb_out[3 * i + 1] = live ? (float)(G.y / gden) : 0.0f;
-        indirect_rgb_out[3 * i + 2] = live ? (float)(G.z / gden) : 0.0f;
-      }
-      if (sky_out) sky_out[i] = live ? (float)((double)missed / gden) : 0.0f;
-    }
-  }
-  if (lane == 0) {
-    if (shadowed) atomicAdd(S.stats + ST_SHADOW, shadowed);
-    if (gathered) atomicAdd(S.stats + ST_RAYS, gathered);
-  }
-}
-extern "C" hipError_t dt_launch_points_irr(const void* dev_launch, uint32_t seed, int32_t frame, int64_t n,
-                                           const double* point, const double* normal, int n_samples, int n_lights,
-                                           const void* lights, int gather_rays, float* direct, float* direct_rgb,
-                                           float* indirect_rgb, float* sky, int grid, hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_points_irr_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, seed, frame, n,
-                     point, normal, n_samples, n_lights, (const dtd::IrrLight*)lights, gather_rays, direct, direct_rgb,
-                     indirect_rgb, sky);
-  return hipGetLastError();
-}
-extern "C" const void* dt_points_irr_kernel_ptr(void) { return (const void*)dt_points_irr_kernel; }
-#elif DT_PVIS
-// Mutual visibility of two point sets (include/dt.h dt_points_visibility; no reference counterpart): every pair
-// (source i, target j) answered as dt_rayq_occl_kernel answers the ray (a_i, b_j - a_i, skip_b[j]), with the
-// segment built in registers as dt_points_occl_kernel builds a probe: make_walk + occluded_walk<0/1>, tree walks
-// only, one call site.
-// A work item is (a wave of 64 consecutive sources) x (a tile of DT_PVIS_TILE consecutive targets), item =
-// wave * n_tiles + tile, grid-stride over the items: few sources against many targets still fill the machine. One
-// source per lane, loaded once per item; the target, its normal and its skip shape are wave-uniform loads (the
-// skip through uni(), as dt_points_occl_kernel takes a light's shape), so the 64 lanes of a walk aim at one
-// point and skip one shape: one walk per target, never one per lane. A void target runs no walk for the wave;
-// a tail lane, a void source or a void segment is an inactive lane of its walks and stays in the wave.
-// bits: a lane ORs 32 verdicts into a register and stores one word per 32 targets (at the word's end or at the
-// tile's; tiles are multiples of 32, so no word is shared between items). count_a: one integer atomicAdd per
-// lane and item; count_b: the ballot's popcount added by one lane, as ST_SHADOW is counted; the host zeroed
-// both, and integers show no order. weight_a: the lane's f64 sum over the tile in ascending j goes to
-// partial[tile * n_a + i]; dt_points_vis_sum_kernel then adds the tiles in ascending order (the header's fixed
-// order). The cosines run only with `partial` (out->weight_a); every store is guarded by its plane's pointer.
-static_assert(DT_PVIS_TILE % 32 == 0 && DT_PVIS_TILE > 0, "a bits word must not straddle two tiles");
-extern "C" __global__ void __launch_bounds__(64)
-dt_points_vis_kernel(const DLaunch* __restrict__ Lp, int64_t n_a, const double* __restrict__ a, int64_t n_b,
-                     const double* __restrict__ b, const int32_t* __restrict__ skip_b,
-                     const double* __restrict__ normal_a, const double* __restrict__ normal_b, int falloff,
-                     uint32_t* __restrict__ bits, int32_t* __restrict__ count_a, int32_t* __restrict__ count_b,
-                     double* __restrict__ partial)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  Counters cnt;
-  cnt.wc = wc_lds;
-  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
-  const int64_t n_tiles = (n_b + DT_PVIS_TILE - 1) / DT_PVIS_TILE, n_waves = (n_a + DT_WAVE - 1) / DT_WAVE;
-  const int64_t words = (n_b + 31) / 32;   // per row of bits
-  unsigned long long traced = 0;   // wave-uniform
-  for (int64_t item = blockIdx.x; item < n_waves * n_tiles; item += gridDim.x) {
-    const int64_t wave = item / n_tiles, tile = item - wave * n_tiles;
-    const int64_t i = wave * DT_WAVE + lane;
-    const bool in = i < n_a;
-    V3 p = v3(0, 0, 0), na = v3(0, 0, 0);
-    bool live = false;
-    if (in) {
-      const V3 pi = v3(a[3 * i], a[3 * i + 1], a[3 * i + 2]);
-      live = isfinite(pi.x) && isfinite(pi.y) && isfinite(pi.z);
-      if (partial) {
-        const V3 ni = v3(normal_a[3 * i], normal_a[3 * i + 1], normal_a[3 * i + 2]);
-        live = live && isfinite(ni.x) && isfinite(ni.y) && isfinite(ni.z);
-        if (live) na = ni;
-      }
-      if (live) p = pi;
-    }
-    const bool any_live = __ballot(live) != 0;   // wave-uniform: a wave of void sources runs no walk
-    const int64_t j0 = tile * DT_PVIS_TILE, j1 = j0 + DT_PVIS_TILE < n_b ? j0 + DT_PVIS_TILE : n_b;
-    uint32_t word = 0;
-    int seen = 0;        // the lane's visible targets of this tile
-    double wsum = 0.0;   // ... and their weights, ascending j
-    for (int64_t j = j0; j < j1; ++j) {
-      // the target: wave-uniform
-      const V3 q = v3(b[3 * j], b[3 * j + 1], b[3 * j + 2]);
-      bool live_b = any_live && isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
-      V3 nb = v3(0, 0, 0);
-      if (partial && live_b) {
-        nb = v3(normal_b[3 * j], normal_b[3 * j + 1], normal_b[3 * j + 2]);
-        live_b = isfinite(nb.x) && isfinite(nb.y) && isfinite(nb.z);
-      }
-      bool visible = false;
-      if (live_b) {
-        const int skip = skip_b ? uni(skip_b[j]) : -1;
-        V3 sray = live ? sub(q, p) : v3(0, 0, 0);
-        // a void segment (dt_rays_occluded's rule) is an inactive lane, as in dt_rayq_occl_kernel
-        const bool act = live && !dtd::irr_void_dir(sray);
-        if (!act) sray = v3(0, 0, 0);
-        const V3 org = act ? p : v3(0, 0, 0);
-        const float t_max = (float)norm(sray);
-        const V3 sn = act ? normalized(sray) : v3(1, 0, 0);
-        const V3 bstart = add(org, mul(1e-3, sray)), sstart = add(org, mul(1e-3, sn));
-        const unsigned long long am = __ballot(act);
-        traced += (unsigned long long)__popcll(am);
-        bool occl = false;
-        if (am) {
-          const Walk w = make_walk(P, act, sray, bstart, 0.0f);
-          const bool o = w.inf_wave ? occluded_walk<1>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt)
-                                    : occluded_walk<0>(S, P, w, act, bstart, sn, sstart, t_max, skip, 0.0f, cnt);
-          occl = act && o;
-        }
-        visible = live && !occl;
-        if (partial) {
-          double wij = 0.0;
-          if (visible && act) {
-            const double cc = dtd::irr_cosine(na, sray) * dtd::irr_cosine(nb, mul(-1, sray));
-            wij = falloff ? cc / dot(sray, sray) : cc;
-          }
-          wsum = wsum + wij;
-        }
-        const unsigned long long vm = __ballot(visible);
-        if (count_b && vm && lane == 0) atomicAdd(count_b + j, (int)__popcll(vm));
-      }
-      if (visible) {
-        word |= 1u << (unsigned)(j & 31);
-        ++seen;
-      }
-      if ((j & 31) == 31 || j + 1 == j1) {
-        if (in && bits) bits[i * words + (j >> 5)] = word;
-        word = 0;
-      }
-    }
-    if (in && count_a && seen) atomicAdd(count_a + i, seen);
-    if (in && partial) partial[tile * n_a + i] = wsum;
-  }
-  if (lane == 0 && traced) atomicAdd(S.stats + ST_SHADOW, traced);
-}
-// weight_a[i] = the f64 sum of source i's tile sums in ascending tile order, from 0.0; one lane per source
-extern "C" __global__ void __launch_bounds__(256)
-dt_points_vis_sum_kernel(int64_t n_a, int64_t n_tiles, const double* __restrict__ partial, double* __restrict__ weight_a)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_a) return;
-  double s = 0.0;
-  for (int64_t t = 0; t < n_tiles; ++t) s = s + partial[t * n_a + i];
-  weight_a[i] = s;
-}
-extern "C" hipError_t dt_launch_points_vis(const void* dev_launch, int64_t n_a, const double* a, int64_t n_b,
-                                           const double* b, const int32_t* skip_b, const double* normal_a,
-                                           const double* normal_b, int falloff, uint32_t* bits, int32_t* count_a,
-                                           int32_t* count_b, double* partial, double* weight_a, int grid,
-                                           hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_points_vis_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n_a, a, n_b, b,
-                     skip_b, normal_a, normal_b, falloff, bits, count_a, count_b, partial);
-  if (hipError_t e = hipGetLastError()) return e;
-  if (!weight_a) return hipSuccess;
-  const int64_t n_tiles = (n_b + DT_PVIS_TILE - 1) / DT_PVIS_TILE;
-  hipLaunchKernelGGL(dt_points_vis_sum_kernel, dim3((unsigned)((n_a + 255) / 256)), dim3(256), 0, stream, n_a, n_tiles,
-                     partial, weight_a);
-  return hipGetLastError();
-}
-extern "C" const void* dt_points_vis_kernel_ptr(void) { return (const void*)dt_points_vis_kernel; }
-#elif DT_MATTE
-// Object mattes (include/dt.h dt_render_mattes; no reference counterpart): for the samples 0 .. n_samples-1 of
-// every owned pixel the render's own primary ray to its closest hit, as dt_features_kernel takes it (items
-// and lanes, camera_ray, closest_hit at shift 0, the primary-list block rule), and per pixel the histogram
-// of the hit shapes' groups (gmap[shape], or the shape itself), ranked.
-// A segment is the `per` lanes of one pixel (spp >= 64: the wave; spp < 64: spp lanes, P.ppw segments). Its
-// table lives in its own lanes' registers: lane sl holds entry sl (tid, tcnt), tsize is the same in every
-// lane of the segment. A pixel has at most min(n_samples, DT_MATTE_TABLE) entries, so they fit (spp < 64:
-// one chunk of `per` samples; spp >= 64: 64 lanes = DT_MATTE_TABLE), and the table carries over from chunk
-// to chunk in registers.
-// A chunk is merged by a distinct-value loop, one pass per distinct group of the segment and every segment
-// at once: the segment's lowest pending lane names the group, a ballot finds its equals (popcount: how many
-// samples), a ballot finds its entry; without one the group takes entry tsize, or with the table full it is
-// dropped and the pixel overflows. Lowest pending lane first = order of first appearance in ascending sample
-// order, the table's insertion order; no atomics, no per-sample loop.
-// Ranking by counting: an entry's layer is the number of entries of its table that come before it (count
-// descending, group ascending; groups are distinct, so the order is total), found in tsize shuffle steps;
-// typical pixels hold one to three groups.
-static_assert(DT_MATTE_TABLE == DT_WAVE, "one table entry per lane");
-extern "C" __global__ void __launch_bounds__(64)
-dt_mattes_kernel(const DLaunch* __restrict__ Lp, int n_samples, const int32_t* __restrict__ gmap, int layers,
-                 int32_t* __restrict__ id_out, float* __restrict__ weight_out, int32_t* __restrict__ distinct_out,
-                 unsigned long long* __restrict__ overflow)
-{
-  const DScene& S = Lp->S;
-  const DParams& P = Lp->P;
-  const int lane = threadIdx.x;
-  __shared__ unsigned int wc_lds[WC_N];
-  if (lane < WC_N) wc_lds[lane] = 0;
-  __syncthreads();
-  Counters cnt;
-  cnt.wc = wc_lds;
-  cnt.box = 0; cnt.prim = 0; cnt.wnodes = 0;
-  Ctx c;
-  c.S = &S;
-  c.P = &P;
-  c.rng.k0 = P.seed;
-  c.rng.k1 = (uint32_t)P.frame;
-  const bool lists = P.pl_block > 0 && P.n_fnodes > 0 && (P.ftree_mode & 1);
-  const int group = P.ppw;
-  const int per = P.spp < DT_WAVE ? P.spp : DT_WAVE;
-  const int j = lane / per, sl = lane - j * per, base = j * per;
-  const unsigned long long segmask = per < DT_WAVE ? ((1ull << per) - 1ull) << base : ~0ull;
-  const int chunks = (n_samples + DT_WAVE - 1) / DT_WAVE;
-  unsigned int n_over = 0;
-  for (int64_t item = blockIdx.x; item < P.n_items; item += gridDim.x) {
-    int px_x = 0, px_y = 0;
-    int64_t px_off = 0;
-    bool px_valid = false;
-    pixel_of(P, item * group + (j < group ? j : 0), px_x, px_y, px_off, px_valid);
-    px_valid = px_valid && j < group;
-    int tid = -1, tcnt = 0, tsize = 0;
-    bool over = false;
-    for (int chunk = 0; chunk < chunks; ++chunk) {
-      const int sample = chunk * DT_WAVE + sl;
-      const bool valid = px_valid && sample < n_samples;
-      c.rng.pixel = (uint32_t)(px_y * P.xRes + px_x);
-      c.rng.sample = (uint32_t)sample;
-      V3 eye_sample = v3a(P.eye), ray0 = v3(0, 0, 0);
-      if (valid) camera_ray(c, P, px_x, px_y, eye_sample, ray0);
-      const unsigned long long vm = __ballot(valid);
-      int gid = -1;   // the sample's group; -1: a miss, or no sample
-      if (vm) {
-        int pblock = -1;
-        if (lists) {   // the block of the wave's valid pixels, when they share one
-          const int blk = (px_y / P.pl_block) * P.pl_nbx + px_x / P.pl_block;
-          const int b0 = __shfl(blk, (int)__builtin_ctzll(vm));
-          if (!__ballot(valid && blk != b0)) pblock = b0;
-        }
-        HitRec h;
-        h.t_min = FLT_MAX; h.shape = -1; h.ccol = -1;
-        const bool any = closest_hit(S, P, valid, ray0, eye_sample, 0.0f, h, cnt, pblock);
-        if (any && valid && h.shape >= 0) gid = gmap ? gmap[h.shape] : h.shape;
-      }
-      bool todo = gid >= 0;
-      unsigned long long tm;
-      while ((tm = __ballot(todo)) != 0) {
-        const unsigned long long mine = tm & segmask;   // the segment's pending lanes
-        const int gv = __shfl(gid, mine ? (int)__builtin_ctzll(mine) : lane);
-        const bool eq = todo && gid == gv;
-        const int n_eq = (int)__popcll(__ballot(eq) & segmask);
-        const unsigned long long fm = __ballot(sl < tsize && tid == gv) & segmask;   // its entry, if any
-        if (mine) {
-          if (fm) {
-            if (lane == (int)__builtin_ctzll(fm)) tcnt += n_eq;
-          } else if (tsize < DT_MATTE_TABLE) {
-            if (sl == tsize) { tid = gv; tcnt = n_eq; }
-            ++tsize;
-          } else {
-            over = true;
-          }
-        }
-        todo = todo && !eq;
-      }
-    }
-    n_over += (unsigned int)__popcll(__ballot(over && sl == 0));
-    // rank = the entries of the segment's table that come before this lane's
-    const bool ent = px_valid && sl < tsize;
-    int rank = 0;
-    for (int i = 0; __ballot(i < tsize) != 0; ++i) {
-      const int src = (base + i) & (DT_WAVE - 1);
-      const int kc = __shfl(tcnt, src), ki = __shfl(tid, src);
-      if (i < tsize && (kc > tcnt || (kc == tcnt && ki < tid))) ++rank;
-    }
-    if (px_valid) {
-      const int64_t q = P.layout == DT_OUT_SLAB ? px_off / 3 : (int64_t)(P.yRes - 1 - px_y) * P.xRes + px_x;
-      if (ent && rank < layers) {
-        if (id_out) id_out[layers * q + rank] = tid;
-        if (weight_out) weight_out[layers * q + rank] = (float)((double)tcnt / (double)n_samples);
-      }
-      for (int jj = sl; jj < layers; jj += per)
-        if (jj >= tsize) {
-          if (id_out) id_out[layers * q + jj] = -1;
-          if (weight_out) weight_out[layers * q + jj] = 0.0f;
-        }
-      if (sl == 0 && distinct_out) distinct_out[q] = tsize;
-    }
-  }
-  if (lane == 0 && n_over) atomicAdd(overflow, (unsigned long long)n_over);
-}
-extern "C" hipError_t dt_launch_mattes(const void* dev_launch, int n_samples, const int32_t* gmap, int layers, int32_t* id,
-                                       float* weight, int32_t* distinct, unsigned long long* overflow, int grid,
-                                       hipStream_t stream)
-{
-  hipLaunchKernelGGL(dt_mattes_kernel, dim3(grid), dim3(64), 0, stream, (const DLaunch*)dev_launch, n_samples, gmap, layers,
-                     id, weight, distinct, overflow);
-  return hipGetLastError();
-}
-extern "C" const void* dt_mattes_kernel_ptr(void) { return (const void*)dt_mattes_kernel; }
-#elif DT_CAMRAYS
-// Camera rays as arrays (include/dt.h dt_camera_rays; the CPU oracle's or_primary_ray is its counterpart): for
-// the samples sample_begin .. sample_begin+ns-1 of every owned pixel the ray the trace kernel starts from --
-// its RNG pixel, sample and key, and camera_ray itself -- written out as 3 doubles of start (the eye sample)
-// and 3 of dir (the unnormalised ray through the focal point). No scene: only Lp->P is read.
-// One ray per lane, rows in ascending order: row i is sample sample_begin + i % ns of output slot i / ns
-// (dtd::slot_pixel), so a wave's 64 rows are 1536 contiguous bytes of each array in both layouts, whole
-// cache lines but for the wave's two ends. The rows of slots the tile share does not own are not written.
-// Below 2^32 rows (wave-uniform) the slot comes from a 32-bit division.
-extern "C" __global__ void __launch_bounds__(256)
-dt_camera_rays_kernel(const DLaunch* __restrict__ Lp, int sample_begin, int ns, int64_t n_rows,
-                      double* __restrict__ start, double* __restrict__ dir)
-{
-  const DParams& P = Lp->P;
-  Ctx c;
-  c.S = &Lp->S;
-  c.P = &P;
-  c.rng.k0 = P.seed;
-  c.rng.k1 = (uint32_t)P.frame;
-  const bool small = n_rows <= 0xffffffffll;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_rows; i += (int64_t)gridDim.x * 256) {
-    const int64_t q = small ? (int64_t)((uint32_t)i / (uint32_t)ns) : i / ns;
-    const int s = (int)(i - q * ns);
-    int x, y;
-    if (!dtd::slot_pixel(P, q, x, y)) continue;
-    c.rng.pixel = (uint32_t)(y * P.xRes + x);
-    c.rng.sample = (uint32_t)(sample_begin + s);
-    V3 eye_sample, ray0;
-    camera_ray(c, P, x, y, eye_sample, ray0);
-    start[3 * i] = eye_sample.x; start[3 * i + 1] = eye_sample.y; start[3 * i + 2] = eye_sample.z;
-    dir[3 * i] = ray0.x; dir[3 * i + 1] = ray0.y; dir[3 * i + 2] = ray0.z;
-  }
-}
-extern "C" hipError_t dt_launch_camera_rays(const void* dev_launch, int sample_begin, int ns, int64_t n_rows,
-                                            double* start, double* dir, hipStream_t stream)
-{
-  int64_t blocks = (n_rows + 255) / 256;
-  if (blocks > (1 << 22)) blocks = 1 << 22;   // grid-stride past that
-  hipLaunchKernelGGL(dt_camera_rays_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const DLaunch*)dev_launch,
-                     sample_begin, ns, n_rows, start, dir);
-  return hipGetLastError();
-}
-#else
+// DT_LIBRARY_ONLY (dt_device.h): everything above is the device library the auxiliary units share (one unit
+// per auxiliary kernel family); what follows is this unit's own: the trace kernel, the DT_HELPERS
+// kernels and the build's launch trio.
+#ifndef DT_LIBRARY_ONLY
 // The launch record: a device copy per counter parity (dt_api.cpp), uploaded only when it changed
 extern "C" __global__ void __launch_bounds__(64, DT_TRACE_MIN_WAVES)
 DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
@@ -5775,8 +3641,6 @@ DT_TRACE_KERNEL(const DLaunch* __restrict__ Lp, float* __restrict__ out)
   }
 }
 
-#endif   // !DT_ISECT
-
 #if DT_HELPERS
 // The sky of the pixels a 1-spp trace launch flagged as missed (P.sky_defer): renderImage's miss
 // branch (cpp:1074-1092: cloudColor of mcam * focalPoint) one pixel per lane, at the occupancy of a
@@ -6204,8 +4068,6 @@ extern "C" hipError_t dt_launch_unpack(const void* dev_launch, int world, int64_
 }
 #endif
 
-#if !DT_ISECT && !DT_FEAT && !DT_RAYQ && !DT_MATTE && !DT_FEATP && !DT_OCCL && !DT_POCCL && !DT_MHIT && !DT_CAMRAYS && \
-    !DT_TRANSMIT && !DT_POCCLG && !DT_RAYPATH && !DT_PIRR && !DT_PVIS
 // every trace-kernel build: <kernel>_launch and <kernel>_ptr (dt_api.cpp's kernel table)
 #if DT_W5
 static_assert(DT_TRACE_MIN_WAVES == 5 && DT_PSUM_LDS == 2, "5-wave build: Makefile W5FLAGS");
@@ -6224,5 +4086,4 @@ extern "C" int DT_CAT(DT_TRACE_KERNEL, _traits)(void)
 {
   return (DT_SKY_AGAIN ? 1 : 0) | (DT_CHUNK_ITEMS ? 2 : 0) | (DT_WINDOW ? 4 : 0) | (DT_ADAPT ? 8 : 0) | (int)(((DT_FEATURES) & 0xFFFFu) << 8);
 }
-#endif
-#endif   // !DT_REPRO
+#endif   // !DT_LIBRARY_ONLY

@@ -1,5 +1,5 @@
 // Occlusion feature buffers: the one definition of the two probe-ray generators of dt_render_occlusion
-// (include/dt.h), shared by the kernel (dt_kernels.hip dt_occlusion_kernel) and the host exports
+// (include/dt.h), shared by the kernel (dt_occlusion.hip dt_occlusion_kernel) and the host exports
 // dt_occlusion_ao_ray / dt_occlusion_light_ray (dt_api.cpp). Both sides are built with -ffp-contract=off,
 // so they run the same IEEE operations in the same order; nothing here calls libm.
 // The draws are the render's counter RNG (Philox4x32-10, key (seed, frame), counter (pixel, sample,

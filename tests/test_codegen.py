@@ -24,20 +24,20 @@ def _make_var(name):
     return subprocess.check_output(["make", "-s", "-C", CSRC, "var-" + name], text=True).split()
 
 
-def _asm(extra, out):
+def _asm(extra, out, unit="dt_kernels.hip"):
     base = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
             "-fhip-fp32-correctly-rounded-divide-sqrt"]
     return subprocess.Popen([HIPCC] + base + extra + ["-I" + CSRC, "--cuda-device-only", "-S",
-                            os.path.join(CSRC, "dt_kernels.hip"), "-o", out],
+                            os.path.join(CSRC, unit), "-o", out],
                             stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
 
 
 def test_reproducer_pins_the_defect(tmp_path):
-    """The reproducer's TU (dt_kernels.hip DT_REPRO) under -disable-machine-cse holds unencodable
+    """The reproducer's unit (dt_repro.hip) under -disable-machine-cse holds unencodable
     literal moves; without that flag it holds none."""
     a, b = str(tmp_path / "cse.s"), str(tmp_path / "nocse.s")
-    pa = _asm(["-DDT_REPRO=1", "-mllvm", "-disable-machine-cse"], a)
-    pb = _asm(["-DDT_REPRO=1"], b)
+    pa = _asm(["-mllvm", "-disable-machine-cse"], a, "dt_repro.hip")
+    pb = _asm([], b, "dt_repro.hip")
     assert pa.wait() == 0 and pb.wait() == 0
     bad = bad_literals(open(a).read())
     assert bad and all("0x3ff8000000000000" in ins for _, ins in bad), bad   # the 1.5 of sky_color

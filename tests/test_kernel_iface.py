@@ -1,9 +1,11 @@
-"""The host/kernel boundary is declared once (distraytracer_amd/csrc/dt_kernel_iface.h): dt_kernels.hip includes
-the header, so a definition that disagrees with its declaration does not compile; the two host units declare
-none of its symbols themselves; and every such extern "C" function the kernels' file defines is in the header.
+"""The host/kernel boundary is declared once (distraytracer_amd/csrc/dt_kernel_iface.h): every kernel unit
+(dt_kernels.hip and one .hip per auxiliary kernel family, the Makefile's SRC_* list) includes the header, so a
+definition that disagrees with its declaration does not compile; the two host units declare none of its symbols
+themselves; and every such extern "C" function a kernel unit defines is in the header.
 Plain regular expressions over the sources. No GPU."""
 import os
 import re
+import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "distraytracer_amd", "csrc")
 # the names of the boundary: launch wrappers, kernel pointers, the trace builds' trios, the record's layout
@@ -40,14 +42,36 @@ def test_the_host_units_declare_no_interface_symbol():
     assert '#include "dt_kernel_iface.h"' in read("dt_api_internal.h")
 
 
+def kernel_units():
+    """dt_kernels.hip and the unit of every auxiliary build (Makefile AUX_BUILDS, SRC_<build>)."""
+    def var(name):
+        return subprocess.check_output(["make", "-s", "-C", CSRC, "var-" + name], text=True).split()
+    aux = var("AUX_BUILDS")
+    assert len(aux) == 14
+    units = []
+    for b in aux:
+        src = var("SRC_" + b)
+        assert len(src) == 1 and src[0].endswith(".hip"), b
+        units.append(src[0])
+    assert len(set(units)) == 13, "one unit per family, dt_points_occl.hip built twice"
+    return ["dt_kernels.hip"] + sorted(set(units))
+
+
 def test_every_interface_function_the_kernels_define_is_declared_in_the_header():
-    hip, header = read("dt_kernels.hip"), read("dt_kernel_iface.h")
-    assert re.search(r'^#include "dt_kernel_iface.h"$', hip, re.M)
-    assert not re.search(r"^#if", hip[:hip.index('#include "dt_kernel_iface.h"')], re.M), "included in every build"
+    header = read("dt_kernel_iface.h")
     declared = extern_c_names(header)
-    defined = {n for n in extern_c_names(hip) if IFACE.match(n)}
+    defined = set()
+    for unit in kernel_units():
+        text = read(unit)
+        assert re.search(r'^#include "dt_kernel_iface.h"$', text, re.M), unit
+        assert not re.search(r"^#if", text[:text.index('#include "dt_kernel_iface.h"')], re.M), (unit, "included in every build")
+        own = {n for n in extern_c_names(text) if IFACE.match(n)}
+        assert own, unit
+        assert not (own & defined), (unit, sorted(own & defined))
+        defined |= own
     assert len(defined) >= 30
     assert sorted(defined - declared) == []
+    hip = read("dt_kernels.hip")
     # the trace builds' trio is defined through DT_CAT(DT_TRACE_KERNEL, _launch | _ptr | _traits), DT_TRACE_KERNEL
     # being the build's kernel name (the Makefile's -DDT_KNAME, DT_WINDOW's _win / _awin): the header declares the
     # trio for every name of its list in all three modes

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds tools/call_repro/build/repro_<tag> for the called-function defect: the sky
-# kernels of dt_kernels.hip's DT_REPRO mode (cloud_color_lane inlined vs called) under the product's
+# kernels of csrc/dt_repro.hip (cloud_color_lane inlined vs called) under the product's
 # code-generation flags (csrc/Makefile CODEGEN: "all"), none of them ("none"), each flag alone
 # ("only_<k>") and all but one ("drop_<k>"). No GPU needed; run them with tools/call_repro/run.sh.
 set -euo pipefail
@@ -17,7 +17,7 @@ BASE="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-mat
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -std=c++17 -I"$R" -c "$R/tools/call_repro/repro_main.cpp" -o "$B/main.o" 2>/dev/null
 build() {   # tag, codegen flags
   local tag=$1; shift
-  /opt/rocm/bin/hipcc $BASE "$@" -DDT_REPRO=1 -I"$C" -c "$C/dt_kernels.hip" -o "$B/k_$tag.o" 2>/dev/null
+  /opt/rocm/bin/hipcc $BASE "$@" -I"$C" -c "$C/dt_repro.hip" -o "$B/k_$tag.o" 2>/dev/null
   /opt/rocm/bin/hipcc --offload-arch=gfx950 "$B/main.o" "$B/k_$tag.o" \
     -o "$B/repro_$tag" -L"$R/distraytracer_amd" -ldt -Wl,-rpath,"\$ORIGIN/../../../distraytracer_amd" 2>/dev/null
 }

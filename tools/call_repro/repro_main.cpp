@@ -1,7 +1,7 @@
 // Minimal reproducer of the called-function defect: the sky of C5 frame 2200's pixels
 // (buildFinal(2200) at 3840x2160, the deferred 1-spp sky of dt_sky_miss_kernel: cloudColor of
 // mcam * focalPoint, render_final_project.cpp:164-192, 1074-1092) computed by cloud_color_lane inlined
-// into one kernel and behind a real call in another (dt_kernels.hip DT_REPRO, compiled with the flags
+// into one kernel and behind a real call in another (csrc/dt_repro.hip, compiled with the flags
 // under test, tools/call_repro/build.sh). Prints how many pixels differ; exit 1 if any.
 #include <hip/hip_runtime.h>
 
